@@ -9,9 +9,13 @@ A "step" is one pass of the DCRNN hot path over one batch of synthetic clips tha
 resident in HBM: zero_grad -> forward -> loss -> full BPTT backward (all parameter gradients) ->
 [RCCL all-reduce of one flat gradient bucket] -> clip_grad_norm_(5) -> Adam.  Weak scaling: the
 per-GPU batch is fixed (256 clips), ranks hold different clips, no data-path collective except
-the gradient all-reduce.  Rank 0 prints ONE JSON line (contract in the task statement), extended
-with `roofline` (live HIP-event timing of every kernel, algorithmic FLOPs/bytes from DESIGN.md)
-and `cpu_baseline` (the torch-eager oracle timed on the host cores on a bounded sample).
+the gradient all-reduce.  Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, warms up, times the K steps, [writes the last step's outputs: --dump-outputs DIR] and prints the line.
+Everything else runs only with --full: the streamed-input pass, `roofline` (live HIP-event timing of every kernel, algorithmic
+FLOPs/bytes from DESIGN.md), the exchange + optimiser tail timing, the device-graph check against the host pipeline, the
+secondary workloads, the split-bf16 and sustained passes, `aten_gpu_baseline` and `cpu_baseline` (the torch-eager oracle timed
+on the host cores on a bounded sample).
 """
 import argparse
 import ctypes
@@ -490,8 +494,34 @@ def parse_prof_report(text):
     return prof
 
 
+DUMP_SAMPLE_ELEMS = 1 << 22      # arrays beyond 4 Mi elements are written as a fixed, seeded sample (64 MB cap in all)
+
+
+def dump_outputs(out_dir, stepper, loss):
+    """What the timed path computed in its last step, as a caller of the step receives it: the loss, the logits (fused
+    classification head), the gradient norm the clip used, and every parameter's gradient and updated value (fp32 .npy files)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(-1), "grad_norm": stepper.grad_norm}
+    if stepper.last_logits is not None:
+        arrays["logits"] = stepper.last_logits.detach()
+    for name, p in stepper.model.named_parameters():       # (a shared parameter appears once)
+        arrays["param." + name] = p.detach()
+        arrays["grad." + name] = p.grad
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    return sorted(arrays)
+
+
 def measure(ctx, workload, steps, warmup, primary):
-    """One workload: build, capture, the contract's timed region, [streamed-input pass], live per-kernel event pass.
+    """One workload: build, capture, the contract's timed region, [--dump-outputs of its last step], and with --full the device-graph
+    check, the streamed-input pass, the live per-kernel event pass and the tail timing.
     Returns the bench line of that workload (rank 0) or None (other ranks).  primary=False: the short secondary passes of
     the other BASELINE configs (no streamed-input pass, no tail timing)."""
     args, world, rank, dev, log = ctx.args, ctx.world, ctx.rank, ctx.dev, ctx.log
@@ -520,8 +550,8 @@ def measure(ctx, workload, steps, warmup, primary):
     stepper = TrainStep(model, task=task, lr=3e-4, weight_decay=5e-4, max_grad_norm=5.0, always_reduce=args.force_dist, **raw_kw)
     device_graph = filt == "dual_random_walk" and not args.host_supports
     # the host-side per-clip graph loop (numpy, 256-512 clips) is only needed to CHECK the device graphs: rank 0 of a
-    # single-GPU run does it; data-parallel ranks build their supports on the GPU only
-    check_graphs = device_graph and world == 1
+    # single-GPU --full run does it; data-parallel ranks and plain runs build their supports on the GPU only
+    check_graphs = device_graph and world == 1 and args.full
     if raw_in:
         if not device_graph:
             raise SystemExit("--workload raw builds its graphs on the device (no --host-supports)")
@@ -628,6 +658,9 @@ def measure(ctx, workload, steps, warmup, primary):
     sclk_mhz = round(cyc / ticks * 100.0, 1) if ticks > 0 else None
     log(f"{workload}: timed {steps} steps ({'graph replay' if graphed else 'eager'}): {elapsed / steps * 1e3:.3f} ms/step "
         f"(first {step_ms[0]:.3f}, median {sorted(step_ms)[len(step_ms) // 2]:.3f}, last {step_ms[-1]:.3f}; shader clock under MFMA load behind the last step {sclk_mhz} MHz)")
+    if primary and args.dump_outputs and rank == 0:           # before any later pass moves the parameters on
+        names = dump_outputs(args.dump_outputs, stepper, loss)
+        log(f"{workload}: outputs of the last timed step -> {args.dump_outputs} ({len(names)} arrays)")
 
     # second timed pass: every step first receives a FRESH batch from pinned host memory (the trainer's situation: at
     # 85 k clips/s the input stream is ~40 GB/s per GPU).  The step is captured on TWO input sets; the host-to-device copy
@@ -635,7 +668,7 @@ def measure(ctx, workload, steps, warmup, primary):
     # buffer and no device-to-device refresh (round 2 paid 0.39 ms/step for that).  Eager launches: one input set, the copy
     # waits for the step that reads it.
     streamed = None
-    if primary and not args.no_stream_inputs:
+    if primary and args.full and not args.no_stream_inputs:
         pin = [t.pin_memory() for t in (hx, hy)]
         side = ctx.copy_stream
         sets = [(x, y)]
@@ -691,7 +724,7 @@ def measure(ctx, workload, steps, warmup, primary):
 
     prof = {}
     kernel_clock_mhz = {}
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         # per-kernel durations: the SAME K steps once more, launched eagerly with a HIP-event pair
         # around every launch on the launch stream (events cannot be read back from a graph replay;
         # the pairs themselves cost ~0.2 ms/step, which is why they are kept out of the timed region)
@@ -717,7 +750,7 @@ def measure(ctx, workload, steps, warmup, primary):
     # (with a process group every call all-reduces -- SUMS -- the bucket in place, so the same finite gradient is re-installed
     # before every call)
     tail_ms = None
-    if primary:
+    if primary and args.full:
         snap = stepper.snapshot()
         keep_grad = stepper.fp.flat_grad.clone()
         e0, e1 = ctx.event(), ctx.event()
@@ -960,6 +993,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="cfg2", choices=list(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the device-graph check against the host "
+                    "pipeline, the streamed-input pass, per-kernel roofline, tail timing, the secondary workloads, the split-bf16 and "
+                    "sustained passes and the ATen / CPU baselines (off by default: a plain run sets up, warms up, times --steps "
+                    "steps, [dumps] and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last timed step "
+                    "computed (loss, logits, gradient norm, every parameter's gradient and updated value) as DIR/<name>.npy (fp32); "
+                    "inputs and initial parameters are seeded, so two builds can be compared output for output")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch override (default: workload's)")
     ap.add_argument("--layers", type=int, default=LAYERS, help="num_rnn_layers (BASELINE's configs: 2; the reference's SSL recipe "
                     "README.md:91 and its shipped checkpoints use 3 -- decoder layers >= 1 then share one cell)")
@@ -970,12 +1010,12 @@ def main():
     ap.add_argument("--curriculum", action="store_true", help="SSL workloads: use_curriculum_learning (model.py:194-200), teacher-"
                     "forcing flags drawn on the device by eeg_dcrnn_teacher_flags inside the captured step")
     ap.add_argument("--secondary", default=None, help="comma-separated workloads measured by short captured passes BEHIND the "
-                    "primary workload's timed region and reported under `secondary_workloads` of the same line (default at one "
+                    "primary workload's timed region and reported under `secondary_workloads` of the same line (default of --full at one "
                     "GPU with the default workload: cfg3,cfg4,cfg5 = the other BASELINE configs + raw = cfg3 from raw signals; 'none' switches them off)")
     ap.add_argument("--secondary-steps", type=int, default=None, help="timed steps of every secondary pass (default: max(10, --steps))")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the host-side legs: `cpu_baseline` (the oracle on the host "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the host-side legs: `cpu_baseline` (the oracle on the host "
                     "cores) and `aten_gpu_baseline` (the oracle's op sequence on stock ATen kernels on this GPU)")
-    ap.add_argument("--no-prof", action="store_true", help="disable the live per-kernel HIP-event timing")
+    ap.add_argument("--no-prof", action="store_true", help="--full: disable the live per-kernel HIP-event timing")
     ap.add_argument("--host-supports", action="store_true", help="correlation-graph workloads: use supports prepared "
                     "on the host (the reference's DataLoader path) instead of building them on the GPU every step")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying the "
@@ -984,7 +1024,7 @@ def main():
                     "(RCCL all-reduce when a process group exists, fused clip/Adam with device-resident step count / learning "
                     "rate): ONE launch per rank and step.  Off by default: the driver's line keeps the launch sequence of "
                     "rounds 1-4 (graph + eager tail)")
-    ap.add_argument("--no-stream-inputs", action="store_true", help="skip the second timed pass that feeds a fresh pinned "
+    ap.add_argument("--no-stream-inputs", action="store_true", help="--full: skip the second timed pass that feeds a fresh pinned "
                     "host batch into the step's input tensors on a side stream every step")
     ap.add_argument("--force-dist", action="store_true", help="single process: create a world-size-1 process group over "
                     "the nccl (= RCCL) backend and issue the gradient all-reduce every step (exercises the RCCL path on one GPU)")
@@ -995,10 +1035,10 @@ def main():
                     "bf16 split of the hoisted NN GEMMs (ops.set_gemm_mode(1): x-part pre-activations and input gradient on "
                     "v_mfma_f32_16x16x32_bf16, fp32 operands / results / accumulation, fp32-level error) and report it under "
                     "`experimental_split_bf16_step` BESIDE the fp32 line: `value` / `dtype` stay the fp32-MFMA measurement (the default "
-                    "single-GPU cfg2 line carries it anyway, behind the secondary workloads)")
-    ap.add_argument("--no-split-bf16", action="store_true", help="leave the experimental split-bf16 pass out of the default single-GPU line")
+                    "single-GPU cfg2 line of --full carries it anyway, behind the secondary workloads)")
+    ap.add_argument("--no-split-bf16", action="store_true", help="leave the experimental split-bf16 pass out of the default single-GPU --full line")
     ap.add_argument("--sustained-steps", type=int, default=1500, help="replays of the long pass behind everything else in the default single-GPU "
-                    "line (`sustained` in the line: the rate once the part's clocks have settled; never `value`); 0: leave it out")
+                    "--full line (`sustained` in the line: the rate once the part's clocks have settled; never `value`); 0: leave it out")
     ap.add_argument("--tune", action="append", default=[], help="development knob key=value (eeg_dcrnn_set_tuning); loads "
                     "the DEV build libeeg_dcrnn_hip_dev.so instead of the product library")
     ap.add_argument("--lib", default=None, help="development A/B runs only: load this build of the C ABI (e.g. a library built "
@@ -1046,7 +1086,8 @@ def main():
     # the other BASELINE configs, by short captured passes behind the primary workload's timed region (same process, same
     # library, same launch mode); `value` above is untouched by them
     if args.secondary is None:
-        sec = ["cfg3", "cfg4", "cfg5", "raw"] if (world == 1 and args.workload == "cfg2" and not args.batch and not args.tune and not args.lib) else []
+        sec = ["cfg3", "cfg4", "cfg5", "raw"] if (args.full and world == 1 and args.workload == "cfg2" and not args.batch and not args.tune
+                                                  and not args.lib) else []
     else:
         sec = [w for w in args.secondary.split(",") if w and w != "none"]
     sec_lines = {}
@@ -1066,7 +1107,8 @@ def main():
     # opt-in second line (never the headline): the same workload with the hoisted NN GEMMs as a three-term bf16 split
     # (part of the default single-GPU line, behind everything else: it cannot touch `value` or the secondary workloads)
     bf_line, bf_error = None, None
-    default_line = world == 1 and args.workload == "cfg2" and not args.batch and not args.tune and not args.lib and args.secondary is None
+    default_line = (args.full and world == 1 and args.workload == "cfg2" and not args.batch and not args.tune and not args.lib
+                    and args.secondary is None)
     if args.split_bf16 or (default_line and not args.no_split_bf16):
         from eeg_gnn_ssl_amd import ops as _ops
         prev_mode = _ops.set_gemm_mode(1)
@@ -1126,7 +1168,7 @@ def main():
                         for k, v in (r3.get("by_symbol") or {}).items() if "bf3" in k or "nnr" in k or "nn_dma" in k},
             "nn_gemm_ms_per_step_fp32": round(sum(v["ms_per_step"] for k, v in ((out["roofline"] or {}).get("kernels") or {}).items() if k.startswith("gemm_nn")), 4),
             "nn_gemm_ms_per_step_split": round(sum(v["ms_per_step"] for k, v in (r3.get("kernels") or {}).items() if k.startswith("gemm_nn")), 4)}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         ctx.log("aten gpu baseline (the oracle's op sequence on stock ATen kernels, same GPU, outside the timed region)")
         base_wl = "cfg3" if args.workload == "raw" else args.workload      # (the baselines time the model step on features)
         out["aten_gpu_baseline"] = aten_gpu_baseline(base_wl, ctx.dev, out["value"])

@@ -1,12 +1,12 @@
 #!/bin/bash
 # A/B of library builds inside ONE GPU visit: ab_libs.sh [--workload W] [--rounds R] lib1.so lib2.so ...  ("-" = the product library)
-cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; TOOLS_OUT="${TOOLS_OUT:-tools_out}"; export TOOLS_OUT; mkdir -p "$TOOLS_OUT"
 WL=cfg2; R=2
 while [[ "${1:-}" == --* ]]; do case "$1" in --workload) WL=$2; shift 2;; --rounds) R=$2; shift 2;; esac; done
 for r in $(seq 1 $R); do
   for t in "$@"; do
     args=""; [ "$t" != "-" ] && args="--lib $t"
-    python bench.py --workload $WL --steps 30 --warmup 10 --no-cpu-baseline --no-stream-inputs --secondary none $args 2>/dev/null | python -c "
+    python bench.py --full --workload $WL --steps 30 --warmup 10 --no-cpu-baseline --no-stream-inputs --secondary none $args 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if not l.startswith('{'): continue

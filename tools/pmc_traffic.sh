@@ -2,14 +2,14 @@
 # HBM traffic per launch of every kernel class from PMC counters, as MI355X_MICROARCH.md prescribes:
 # separate passes for FETCH_SIZE and WRITE_SIZE (counters only + kernel trace, no other trace domains);
 # read bytes = 2 * FETCH_SIZE * 1024 on gfx950 (wide coalesced reads are tallied at half their size),
-# write bytes = WRITE_SIZE * 1024.  Writes gpurun_out/pmc_traffic_<workload>.json (copy into profiles/).
+# write bytes = WRITE_SIZE * 1024.  Writes $TOOLS_OUT/pmc_traffic_<workload>.json (copy into profiles/).
 # usage: pmc_traffic.sh [workload] [extra bench args, e.g. --tune 14=64]
 W="${1:-cfg2}"; shift
-cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; TOOLS_OUT="${TOOLS_OUT:-tools_out}"; export TOOLS_OUT; mkdir -p "$TOOLS_OUT"; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OLDPWD/gpurun_out/pmc_${W}_$c" -o pmc -- \
-      python "$OLDPWD/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-prof --no-graph --no-stream-inputs --secondary none "$@" > "$OLDPWD/gpurun_out/pmc_${W}_$c.log" 2>&1 )
-  tail -3 "gpurun_out/pmc_${W}_$c.log" | cut -c1-400
+  ( cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OLDPWD/$TOOLS_OUT/pmc_${W}_$c" -o pmc -- \
+      python "$OLDPWD/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-prof --no-graph --no-stream-inputs --secondary none "$@" > "$OLDPWD/$TOOLS_OUT/pmc_${W}_$c.log" 2>&1 )
+  tail -3 "$TOOLS_OUT/pmc_${W}_$c.log" | cut -c1-400
 done
 python - "$W" <<'PY'
 import csv, glob, collections, json, os, sys
@@ -46,7 +46,7 @@ def short(name):
 
 
 for c in tot:
-    files = glob.glob(f"gpurun_out/pmc_{w}_{c}/**/*counter_collection.csv", recursive=True)
+    files = glob.glob(f"{os.environ['TOOLS_OUT']}/pmc_{w}_{c}/**/*counter_collection.csv", recursive=True)
     if not files:
         print("no counter csv for", c); sys.exit(1)
     for r in csv.DictReader(open(files[0])):
@@ -72,6 +72,6 @@ doc = {"workload": w, "kernel_sources_sha256": bench.kernel_sources_sha256(),
        "traffic_bytes_per_launch_by_symbol": {k: int(2.0 * sum(d["FETCH_SIZE"]) / len(d["FETCH_SIZE"]) * 1024 + sum(d["WRITE_SIZE"]) / len(d["WRITE_SIZE"]) * 1024)
                                               for k, d in bysym.items() if d.get("FETCH_SIZE") and d.get("WRITE_SIZE")},
        "per_variant_avg_KB": {k: {c: round(sum(v) / len(v), 1) for c, v in d.items()} for k, d in variants.items()}}
-json.dump(doc, open(f"gpurun_out/pmc_traffic_{w}.json", "w"), indent=1)
+json.dump(doc, open(f"{os.environ['TOOLS_OUT']}/pmc_traffic_{w}.json", "w"), indent=1)
 print(json.dumps(doc, indent=1))
 PY

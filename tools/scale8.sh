@@ -7,20 +7,20 @@
 #   EXTRA="--graph-update" ...       # the all-reduce + clip/Adam captured into the step's HIP graph (ONE launch per rank and step)
 # Each run prints the bench line of rank 0 (value = aggregate clips/s over all N GPUs, MAX over ranks of the timed region).
 set -u
-cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; TOOLS_OUT="${TOOLS_OUT:-tools_out}"; export TOOLS_OUT; mkdir -p "$TOOLS_OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0          # dmabuf IPC (RCCL across processes needs it on this image)
 NPROCS="${NPROCS:-1 2 4 8}"; WORKLOADS="${WORKLOADS:-cfg2 cfg4 cfg5}"; EXTRA="${EXTRA:-}"
 STEPS="${STEPS:-30}"; WARMUP="${WARMUP:-10}"; PORT=29611
 for w in $WORKLOADS; do
   for n in $NPROCS; do
     PORT=$((PORT + 1))
-    out=gpurun_out/scale_${w}_n${n}.json
+    out=$TOOLS_OUT/scale_${w}_n${n}.json
     if [ "$n" == "1" ]; then
       # (N = 1 is a plain process for the driver; --force-dist adds a world-size-1 RCCL group so that the exchange is issued)
-      python bench.py --gpus 1 --workload $w --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-stream-inputs --secondary none --force-dist $EXTRA > $out 2> ${out%.json}.err
+      python bench.py --full --gpus 1 --workload $w --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-stream-inputs --secondary none --force-dist $EXTRA > $out 2> ${out%.json}.err
     else
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT \
-        bench.py --gpus $n --workload $w --steps $STEPS --warmup $WARMUP --no-stream-inputs $EXTRA > $out 2> ${out%.json}.err
+        bench.py --full --gpus $n --workload $w --steps $STEPS --warmup $WARMUP --no-stream-inputs $EXTRA > $out 2> ${out%.json}.err
     fi
     python - "$out" "$w" "$n" <<'PY'
 import json, sys
