@@ -1026,6 +1026,52 @@ int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const i
     return check_launch("fft_features");
 }
 
+int eeg_dcrnn_fft_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
+                                const float* log_scale, float mean, float std_, float* feat_raw_x, float* x_std, float* y_std,
+                                void* stream) {
+    if (raw_x == nullptr || raw_y == nullptr) return fail("fft_features_pair: null input (raw_x=%p, raw_y=%p)", (const void*)raw_x, (const void*)raw_y);
+    if (B < 1 || N < 1 || Tx < 1 || Ty < 1) return fail("fft_features_pair: empty input (B=%d, N=%d, Tx=%d, Ty=%d)", B, N, Tx, Ty);
+    if (W < 4 || W % 4 != 0 || W / 4 + 1 > 64) return fail("fft_features_pair: window=%d unsupported (multiple of 4, <= 252)", W);
+    if (x_std == nullptr || y_std == nullptr)
+        return fail("fft_features_pair: null output (x_std=%p, y_std=%p): the pair is the standardised input and target", (void*)x_std, (void*)y_std);
+    if (!(std_ != 0.f)) return fail("fft_features_pair: std must be non-zero");
+    if (W != kFftWin) {                               // no paired kernel for a window nobody trains with: the general kernel, once per half
+        if (eeg_dcrnn_fft_features(raw_x, B, N, Tx, W, perm, log_scale, mean, std_, feat_raw_x, x_std, stream)) return 1;
+        return eeg_dcrnn_fft_features(raw_y, B, N, Ty, W, perm, log_scale, mean, std_, nullptr, y_std, stream);
+    }
+    const FftHalf hx = {raw_x, Tx, (long long)B * N * Tx, feat_raw_x, x_std}, hy = {raw_y, Ty, (long long)B * N * Ty, nullptr, y_std};
+    const long long n_items = (hx.n_windows + kFftPerWave - 1) / kFftPerWave + (hy.n_windows + kFftPerWave - 1) / kFftPerWave;
+    long long blocks = (n_items + 3) / 4;
+    const long long cap = (long long)platform_num_cus() * kFftWgPerCu;      // persistent, as the single-buffer launch
+    if (blocks > cap) blocks = cap;
+    const size_t lds = 4 * (size_t)kFftWaveDoubles * sizeof(double);
+    EEG_SET_MAX_LDS(fft200_features_pair_kernel, lds);
+    EEG_LAUNCH_P("fft_features_pair", fft200_features_pair_kernel, dim3((unsigned)blocks), dim3(256), lds, S_(stream), hx, hy, N,
+                 reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_);
+    return check_launch("fft_features_pair");
+}
+
+int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, int Ty, int N, int D, const int32_t* perm, const float* shift,
+                               float* x_out, float* y_out, void* stream) {
+    if (x == nullptr || y == nullptr || perm == nullptr || shift == nullptr) return fail("augment_features: null input / perm / shift");
+    if (x_out == nullptr || y_out == nullptr) return fail("augment_features: null output (x_out=%p, y_out=%p)", (void*)x_out, (void*)y_out);
+    if (x_out == x || y_out == y) return fail("augment_features: in-place call (rows move between nodes: outputs must not alias inputs)");
+    if (B < 1 || N < 1 || Tx < 1 || Ty < 1) return fail("augment_features: empty input (B=%d, N=%d, Tx=%d, Ty=%d)", B, N, Tx, Ty);
+    if (D < 4 || D % 4 != 0) return fail("augment_features: feature dim=%d unsupported (positive multiple of 4)", D);
+    if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_out | (uintptr_t)y_out) & 15) != 0) return fail("augment_features: tensors must be 16-byte aligned");
+    const long long pieces = (long long)(Tx + Ty) * N * (D / 4);            // 16-byte pieces per clip
+    const long long chunks = (pieces + kAugPerBlock - 1) / kAugPerBlock;
+    if (chunks > 65535) return fail("augment_features: %lld values per clip exceed one launch (limit %lld)", 4 * pieces, 4LL * 65535 * kAugPerBlock);
+    const dim3 grid((unsigned)B, (unsigned)chunks);
+    if (D == 100)
+        EEG_LAUNCH_P("augment_features", augment_features_kernel<25>, grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, D / 4,
+                     reinterpret_cast<const int*>(perm), shift, x_out, y_out);
+    else
+        EEG_LAUNCH_P("augment_features", augment_features_kernel<0>, grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, D / 4,
+                     reinterpret_cast<const int*>(perm), shift, x_out, y_out);
+    return check_launch("augment_features");
+}
+
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
 static int corr_nsplit(int B, int T) {
     int ns = ceil_div(g_tune[7] > 0 ? g_tune[7] : 1024, B);         // dev knob 7: target number of workgroups

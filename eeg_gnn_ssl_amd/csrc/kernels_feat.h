@@ -117,6 +117,115 @@ constexpr int kFftWin = 200, kFftBins = 100, kFftPerWave = 6, kFftWgPerCu = EEG_
 constexpr int kFftRow = 11;                                              // transposed tile: 16-byte entries, row stride 11 (conflict-free)
 constexpr int kFftWaveDoubles = kFftPerWave * 10 * kFftRow * 2;          // 1320 doubles = 10.3 KB per wave (the Z and output tiles alias it)
 
+// twiddles of a lane: stage 1 -> 2: W100^{q k1}, k1 = 0..9; real-input split: W200^{q + 10 k2}, k2 = 0..9
+__device__ __forceinline__ void fft200_twiddles(int q, cplx (&tw1)[10], cplx (&tw2)[10]) {
+    // two sincos per lane; the other 18 twiddles by complex rotation (error ~10 eps; twenty library sincos calls were 3 000
+    // instructions = 5 us in front of every wave's first window)
+    double sn, cs;
+    sincos(6.283185307179586476925286766559 * (double)q / 100.0, &sn, &cs);
+    const cplx r1 = {cs, -sn};                                           // W100^q
+    sincos(6.283185307179586476925286766559 * (double)q / 200.0, &sn, &cs);
+    const cplx r2 = {cs, sn};                                            // (cos, sin) of 2 pi q / 200
+    const cplx s2 = {0.95105651629515357212, 0.30901699437494742410};    // (cos, sin) of 2 pi 10 / 200
+    tw1[0] = {1.0, 0.0};
+    tw2[0] = r2;
+#pragma unroll
+    for (int j = 1; j < 10; ++j) {
+        tw1[j] = cmul(tw1[j - 1], r1);
+        tw2[j] = cmul(tw2[j - 1], s2);                                   // (cos, sin) of 2 pi (q + 10 j) / 200: the split uses both signs explicitly
+    }
+}
+
+// One item = 6 consecutive (b, t, node) windows of ONE (B, N, T*200) buffer, transformed by one wave (the body shared by the
+// single-buffer and the paired kernel: the same instructions on the same operands, so both give the same bits).
+__device__ __forceinline__ void fft200_item(const float* __restrict__ raw, int N, int T, long long n_windows, const int* __restrict__ perm,
+                                            const float* __restrict__ log_scale, float mean, float inv_std, float* __restrict__ feat_raw,
+                                            float* __restrict__ feat_std, long long item, cplx* tile, int lane, const cplx (&tw1)[10],
+                                            const cplx (&tw2)[10], double log_floor) {
+    float* ftile = reinterpret_cast<float*>(tile);                       // [6][100] log amplitudes (aliases the tile, behind a wave sync)
+    const int w = lane / 10, q = lane - 10 * w;                          // window of the wave, position (n2 in stage 1, k1 in stage 2)
+    const bool active = w < kFftPerWave;
+    const long long w0 = item * kFftPerWave, wg = w0 + w;
+    const bool live = active && wg < n_windows;
+    cplx a[10], A[10];
+    if (live) {
+        const int nd = (int)(wg % N);
+        const long long bt = wg / N;
+        const int t = (int)(bt % T), b = (int)(bt / T);
+        const int src = perm_source(perm, b, N, nd);     // EEG_seq_reflect[:, pair] = EEG_seq[:, swapped pair]
+        const float* sig = raw + (((size_t)b * N + src) * T + t) * kFftWin;
+#pragma unroll
+        for (int n1 = 0; n1 < 10; ++n1) {
+            const f32x2 v = *reinterpret_cast<const f32x2*>(sig + 20 * n1 + 2 * q);        // z[10 n1 + q]
+            a[n1] = {(double)v[0], (double)v[1]};
+        }
+        dft10(a, A);                                                 // over n1 -> k1
+#pragma unroll
+        for (int k1 = 0; k1 < 10; ++k1) tile[(w * 10 + q) * kFftRow + k1] = cmul(A[k1], tw1[k1]);
+    }
+    EEG_WAVE_SYNC();
+    if (live) {
+#pragma unroll
+        for (int n2 = 0; n2 < 10; ++n2) a[n2] = tile[(w * 10 + n2) * kFftRow + q];
+        dft10(a, A);                                                 // over n2 -> k2: A[k2] = Z[q + 10 k2]
+    }
+    EEG_WAVE_SYNC();
+    if (live) {
+#pragma unroll
+        for (int k2 = 0; k2 < 10; ++k2) tile[w * 110 + q + 10 * k2] = A[k2];              // Z[k] at [w][k]
+    }
+    EEG_WAVE_SYNC();
+    float v[10];
+    if (live) {
+#pragma unroll
+        for (int k2 = 0; k2 < 10; ++k2) {
+            const int k = q + 10 * k2;
+            const cplx zp = tile[w * 110 + (k == 0 ? 0 : 100 - k)];
+            const double ar = A[k2].re + zp.re, ai = A[k2].im - zp.im;                    // Z[k] + conj Z[100-k]
+            const double br = A[k2].re - zp.re, bi = A[k2].im + zp.im;                    // Z[k] - conj Z[100-k]
+            const double xr = ar + (tw2[k2].re * bi - tw2[k2].im * br);
+            const double xi = ai - (tw2[k2].re * br + tw2[k2].im * bi);
+            const double pw = 0.25 * (xr * xr + xi * xi);
+            // log|X| = ln2/2 * (e + log2 m), |X|^2 = m 2^e with m in [0.5, 1): the exponent split is exact in fp64, the mantissa's
+            // log2 is one v_log_f32 (absolute error ~1e-7 on a value in (-1, 0]) and the two parts are combined in fp64 -- the fp64
+            // library log (~70 fp64 instructions per bin) was 60 % of this kernel's instructions
+            int ex;
+            const double mant = frexp(pw, &ex);
+            const double lg = 0.34657359027997264 * ((double)ex + (double)fast_log2((float)mant));
+            v[k2] = (float)(pw == 0.0 ? log_floor : lg);
+        }
+    }
+    EEG_WAVE_SYNC();                                                 // every partner read is done: the tile becomes the output tile
+    if (live) {
+#pragma unroll
+        for (int k2 = 0; k2 < 10; ++k2) ftile[w * kFftBins + q + 10 * k2] = v[k2];
+    }
+    EEG_WAVE_SYNC();
+    // 6 windows x 100 floats leave as 16-byte pieces: feat_std at the window's own (b, t, node) slot (6 windows = one 2400-byte
+    // stretch), feat_raw at the SOURCE node's slot (perm is a permutation: every slot is written once)
+    for (int c = lane; c < kFftPerWave * kFftBins / 4; c += 64) {
+        const int j = c / 25, pos = 4 * (c - 25 * j);
+        const long long wj = w0 + j;
+        if (wj >= n_windows) continue;
+        const f32x4 val = *reinterpret_cast<const f32x4*>(ftile + 4 * c);
+        const int nd = (int)(wj % N);
+        const long long bt = wj / N;
+        const int b = (int)(bt / T);
+        if (feat_raw != nullptr) {
+            const int src = perm_source(perm, b, N, nd);
+            *reinterpret_cast<f32x4*>(feat_raw + ((size_t)bt * N + src) * kFftBins + pos) = val;
+        }
+        if (feat_std != nullptr) {
+            const double ls = log_scale != nullptr ? (double)log_scale[b] : 0.0;
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (float)((((double)val[e] + ls) - (double)mean) * (double)inv_std);
+            *reinterpret_cast<f32x4*>(feat_std + (size_t)wj * kFftBins + pos) = o;
+        }
+    }
+    EEG_WAVE_SYNC();                                                 // the output tile is free again
+}
+
 __global__ __launch_bounds__(256, EEG_FFT_MINW) void fft200_features_kernel(const float* __restrict__ raw, int N, int T, long long n_windows,
                                                               const int* __restrict__ perm, const float* __restrict__ log_scale,
                                                               float mean, float inv_std, float* __restrict__ feat_raw,
@@ -124,110 +233,84 @@ __global__ __launch_bounds__(256, EEG_FFT_MINW) void fft200_features_kernel(cons
     EEG_DYN_SMEM(sm);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     cplx* tile = reinterpret_cast<cplx*>(sm) + (size_t)wave * (kFftWaveDoubles / 2);
-    float* ftile = reinterpret_cast<float*>(tile);                       // [6][100] log amplitudes (aliases the tile, behind a wave sync)
-    const int w = lane / 10, q = lane - 10 * w;                          // window of the wave, position (n2 in stage 1, k1 in stage 2)
-    const bool active = w < kFftPerWave;
-    // twiddles of this lane: stage 1 -> 2: W100^{q k1}, k1 = 0..9; real-input split: W200^{q + 10 k2}, k2 = 0..9
     cplx tw1[10], tw2[10];
-    {
-        // two sincos per lane; the other 18 twiddles by complex rotation (error ~10 eps; twenty library sincos calls were 3 000
-        // instructions = 5 us in front of every wave's first window)
-        double sn, cs;
-        sincos(6.283185307179586476925286766559 * (double)q / 100.0, &sn, &cs);
-        const cplx r1 = {cs, -sn};                                       // W100^q
-        sincos(6.283185307179586476925286766559 * (double)q / 200.0, &sn, &cs);
-        const cplx r2 = {cs, sn};                                        // (cos, sin) of 2 pi q / 200
-        const cplx s2 = {0.95105651629515357212, 0.30901699437494742410};   // (cos, sin) of 2 pi 10 / 200
-        tw1[0] = {1.0, 0.0};
-        tw2[0] = r2;
-#pragma unroll
-        for (int j = 1; j < 10; ++j) {
-            tw1[j] = cmul(tw1[j - 1], r1);
-            tw2[j] = cmul(tw2[j - 1], s2);                               // (cos, sin) of 2 pi (q + 10 j) / 200: the split uses both signs explicitly
-        }
-    }
+    fft200_twiddles(lane % 10, tw1, tw2);
     const double log_floor = log(1e-8);                                  // computeFFT: amp == 0 -> 1e-8
     const long long n_items = (n_windows + kFftPerWave - 1) / kFftPerWave;
-    for (long long item = (long long)blockIdx.x * 4 + wave; item < n_items; item += (long long)gridDim.x * 4) {
-        const long long w0 = item * kFftPerWave, wg = w0 + w;
-        const bool live = active && wg < n_windows;
-        cplx a[10], A[10];
-        if (live) {
-            const int nd = (int)(wg % N);
-            const long long bt = wg / N;
-            const int t = (int)(bt % T), b = (int)(bt / T);
-            const int src = perm_source(perm, b, N, nd);     // EEG_seq_reflect[:, pair] = EEG_seq[:, swapped pair]
-            const float* sig = raw + (((size_t)b * N + src) * T + t) * kFftWin;
+    for (long long item = (long long)blockIdx.x * 4 + wave; item < n_items; item += (long long)gridDim.x * 4)
+        fft200_item(raw, N, T, n_windows, perm, log_scale, mean, inv_std, feat_raw, feat_std, item, tile, lane, tw1, tw2, log_floor);
+}
+
+// The SSL sample is a PAIR (dataloader_ssl.py:317-341): 60 s of input and the first seconds of the following clip as target, ONE
+// coin and ONE scale factor per sample applied to both halves, then the scaler on both.  One grid walks the items of raw_x
+// (B, N, Tx*200) and behind them those of raw_y (B, N, Ty*200) with the clip's perm[b] / log_scale[b]: one twiddle set-up per wave
+// and one ramp for both halves; every item is fft200_item on its half, so each output equals the single-buffer kernel's bit for
+// bit.  The target has no un-augmented output: the correlation graph is built from the input clip alone (dataloader_ssl.py:349).
+// Only W = 200 has a paired kernel: for any other window the host runs fft_features_kernel once per half (nobody trains with one).
+struct FftHalf {
+    const float* raw;          // (B, N, T*200)
+    int T;
+    long long n_windows;       // B * N * T
+    float* feat_raw;           // (B, T, N, 100), nullable
+    float* feat_std;           // (B, T, N, 100), nullable
+};
+__global__ __launch_bounds__(256, EEG_FFT_MINW) void fft200_features_pair_kernel(FftHalf hx, FftHalf hy, int N, const int* __restrict__ perm,
+                                                                                 const float* __restrict__ log_scale, float mean, float inv_std) {
+    EEG_DYN_SMEM(sm);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cplx* tile = reinterpret_cast<cplx*>(sm) + (size_t)wave * (kFftWaveDoubles / 2);
+    cplx tw1[10], tw2[10];
+    fft200_twiddles(lane % 10, tw1, tw2);
+    const double log_floor = log(1e-8);
+    const long long nix = (hx.n_windows + kFftPerWave - 1) / kFftPerWave, niy = (hy.n_windows + kFftPerWave - 1) / kFftPerWave;
+    for (long long item = (long long)blockIdx.x * 4 + wave; item < nix + niy; item += (long long)gridDim.x * 4) {
+        const bool second = item >= nix;                                 // wave-uniform: each half ends with its own partial item
+        fft200_item(second ? hy.raw : hx.raw, N, second ? hy.T : hx.T, second ? hy.n_windows : hx.n_windows, perm, log_scale, mean, inv_std,
+                    second ? hy.feat_raw : hx.feat_raw, second ? hy.feat_std : hx.feat_std, second ? item - nix : item, tile, lane, tw1, tw2,
+                    log_floor);
+    }
+}
+
+// Augmentation of already standardised features, the pair in one launch: out[b, t, n, :] = in[b, t, perm[b][n], :] + shift[b] for
+// x (B, Tx, N, D) and y (B, Ty, N, D), shift[b] = log(scale_b) / std (adding log(scale) before the scaler = adding it over std
+// behind it).  blockIdx.x = clip, blockIdx.y = a stretch of kAugPerBlock 16-byte pieces of the clip's (Tx + Ty) * N rows (x rows
+// first): consecutive lanes hold consecutive pieces, so stores are whole lines and loads are whole 400-byte rows (D = 100: a row
+// covers 3 1/8 lines of 128 bytes, the partial lines are shared with the neighbouring row of the same step).  One read, one write.
+constexpr int kAugThreads = 256, kAugUnroll = 4, kAugPerBlock = kAugThreads * kAugUnroll;
+template <int D4C>              // 16-byte pieces per row when known at compile time (25: D = 100), 0 = read D4
+__global__ __launch_bounds__(kAugThreads) void augment_features_kernel(const float* __restrict__ x, const float* __restrict__ y, int N, int Tx,
+                                                                       int Ty, int D4, const int* __restrict__ perm,
+                                                                       const float* __restrict__ shift, float* __restrict__ x_out,
+                                                                       float* __restrict__ y_out) {
+    const int d4 = D4C > 0 ? D4C : D4, b = blockIdx.x;
+    const unsigned rows_x = (unsigned)Tx * N, total = (rows_x + (unsigned)Ty * N) * d4;
+    const float sh = shift[b];
+    const unsigned e0 = blockIdx.y * (unsigned)kAugPerBlock + threadIdx.x;
+    f32x4 v[kAugUnroll];
+    size_t dst[kAugUnroll];
+    bool in_y[kAugUnroll], on[kAugUnroll];
 #pragma unroll
-            for (int n1 = 0; n1 < 10; ++n1) {
-                const f32x2 v = *reinterpret_cast<const f32x2*>(sig + 20 * n1 + 2 * q);        // z[10 n1 + q]
-                a[n1] = {(double)v[0], (double)v[1]};
-            }
-            dft10(a, A);                                                 // over n1 -> k1
+    for (int u = 0; u < kAugUnroll; ++u) {
+        const unsigned e = e0 + u * kAugThreads;
+        on[u] = e < total;
+        if (!on[u]) continue;
+        unsigned row = e / d4;
+        const unsigned c = e - row * d4;
+        in_y[u] = row >= rows_x;
+        if (in_y[u]) row -= rows_x;
+        const unsigned t = row / N, nd = row - t * N;
+        const int src = perm_source(perm, b, N, (int)nd);
+        const size_t clip = (size_t)b * (in_y[u] ? Ty : Tx) * N;
+        dst[u] = ((clip + row) * d4 + c) * 4;
+        v[u] = *reinterpret_cast<const f32x4*>((in_y[u] ? y : x) + ((clip + (size_t)t * N + src) * d4 + c) * 4);
+    }
 #pragma unroll
-            for (int k1 = 0; k1 < 10; ++k1) tile[(w * 10 + q) * kFftRow + k1] = cmul(A[k1], tw1[k1]);
-        }
-        EEG_WAVE_SYNC();
-        if (live) {
+    for (int u = 0; u < kAugUnroll; ++u) {
+        if (!on[u]) continue;
+        f32x4 o;
 #pragma unroll
-            for (int n2 = 0; n2 < 10; ++n2) a[n2] = tile[(w * 10 + n2) * kFftRow + q];
-            dft10(a, A);                                                 // over n2 -> k2: A[k2] = Z[q + 10 k2]
-        }
-        EEG_WAVE_SYNC();
-        if (live) {
-#pragma unroll
-            for (int k2 = 0; k2 < 10; ++k2) tile[w * 110 + q + 10 * k2] = A[k2];              // Z[k] at [w][k]
-        }
-        EEG_WAVE_SYNC();
-        float v[10];
-        if (live) {
-#pragma unroll
-            for (int k2 = 0; k2 < 10; ++k2) {
-                const int k = q + 10 * k2;
-                const cplx zp = tile[w * 110 + (k == 0 ? 0 : 100 - k)];
-                const double ar = A[k2].re + zp.re, ai = A[k2].im - zp.im;                    // Z[k] + conj Z[100-k]
-                const double br = A[k2].re - zp.re, bi = A[k2].im + zp.im;                    // Z[k] - conj Z[100-k]
-                const double xr = ar + (tw2[k2].re * bi - tw2[k2].im * br);
-                const double xi = ai - (tw2[k2].re * br + tw2[k2].im * bi);
-                const double pw = 0.25 * (xr * xr + xi * xi);
-                // log|X| = ln2/2 * (e + log2 m), |X|^2 = m 2^e with m in [0.5, 1): the exponent split is exact in fp64, the mantissa's
-                // log2 is one v_log_f32 (absolute error ~1e-7 on a value in (-1, 0]) and the two parts are combined in fp64 -- the fp64
-                // library log (~70 fp64 instructions per bin) was 60 % of this kernel's instructions
-                int ex;
-                const double mant = frexp(pw, &ex);
-                const double lg = 0.34657359027997264 * ((double)ex + (double)fast_log2((float)mant));
-                v[k2] = (float)(pw == 0.0 ? log_floor : lg);
-            }
-        }
-        EEG_WAVE_SYNC();                                                 // every partner read is done: the tile becomes the output tile
-        if (live) {
-#pragma unroll
-            for (int k2 = 0; k2 < 10; ++k2) ftile[w * kFftBins + q + 10 * k2] = v[k2];
-        }
-        EEG_WAVE_SYNC();
-        // 6 windows x 100 floats leave as 16-byte pieces: feat_std at the window's own (b, t, node) slot (6 windows = one 2400-byte
-        // stretch), feat_raw at the SOURCE node's slot (perm is a permutation: every slot is written once)
-        for (int c = lane; c < kFftPerWave * kFftBins / 4; c += 64) {
-            const int j = c / 25, pos = 4 * (c - 25 * j);
-            const long long wj = w0 + j;
-            if (wj >= n_windows) continue;
-            const f32x4 val = *reinterpret_cast<const f32x4*>(ftile + 4 * c);
-            const int nd = (int)(wj % N);
-            const long long bt = wj / N;
-            const int b = (int)(bt / T);
-            if (feat_raw != nullptr) {
-                const int src = perm_source(perm, b, N, nd);
-                *reinterpret_cast<f32x4*>(feat_raw + ((size_t)bt * N + src) * kFftBins + pos) = val;
-            }
-            if (feat_std != nullptr) {
-                const double ls = log_scale != nullptr ? (double)log_scale[b] : 0.0;
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (float)((((double)val[e] + ls) - (double)mean) * (double)inv_std);
-                *reinterpret_cast<f32x4*>(feat_std + (size_t)wj * kFftBins + pos) = o;
-            }
-        }
-        EEG_WAVE_SYNC();                                                 // the output tile is free again
+        for (int k = 0; k < 4; ++k) o[k] = v[u][k] + sh;
+        *reinterpret_cast<f32x4*>((in_y[u] ? y_out : x_out) + dst[u]) = o;
     }
 }
 

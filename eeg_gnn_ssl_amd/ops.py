@@ -11,8 +11,8 @@ dispatcher's "no kernel for the CPU backend" error, and the C-ABI stub refuses n
 Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
-    fft_features, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_, clip_adam_dev_, teacher_flags_,
-    augment_draw_.
+    fft_features, fft_features_pair, augment_features, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
+    clip_adam_dev_, teacher_flags_, augment_draw_.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1105,6 +1105,81 @@ _define("fft_features", "(Tensor raw, int window, float mean, float std, bool st
         _fft_features_impl, _fft_features_fake)
 
 
+def _check_draws(what, perm, log_scale, b, n, ref, permutation=False):
+    """perm (B, N) / log_scale (B) operands of the paired operators: shapes checked, moved to the device of `ref`.
+    permutation: a HOST perm must be a permutation per row (an output written at the source slot would otherwise keep unwritten
+    slots; no device sync involved -- a device tensor is the output of eeg_dcrnn_augment_draw or the caller's responsibility)"""
+    if perm is not None:
+        if perm.numel() != b * n:
+            raise RuntimeError(f"{what}: perm has shape {tuple(perm.shape)}, expected ({b}, {n}) source channels")
+        if permutation and perm.device.type == "cpu" and ref.device.type != "cpu" and not bool(
+                (torch.sort(perm.reshape(b, n).to(torch.int64), dim=1).values == torch.arange(n, dtype=torch.int64)).all()):
+            raise RuntimeError(f"{what}: every row of perm must be a permutation of 0..N-1")
+        perm = perm.to(device=ref.device, dtype=torch.int32).contiguous()
+    if log_scale is not None:
+        if log_scale.numel() != b:
+            raise RuntimeError(f"{what}: log_scale has {log_scale.numel()} entries for {b} clips")
+        log_scale = log_scale.to(device=ref.device, dtype=torch.float32).contiguous()
+    return perm, log_scale
+
+
+def _fft_features_pair_impl(raw_x, raw_y, window: int, mean: float, std: float, perm, log_scale):
+    lib = _lib.get_lib()
+    raw_x, raw_y = raw_x.contiguous(), raw_y.contiguous()
+    _check(lib, raw_x, "raw input signals")
+    _check(lib, raw_y, "raw target signals")
+    if raw_x.dim() != 3 or raw_x.shape[2] % window != 0 or raw_x.shape[2] == 0:
+        raise RuntimeError(f"raw input signals must be (B, N, Tx*{window}), got {tuple(raw_x.shape)}")
+    b, n, total = raw_x.shape
+    if raw_y.dim() != 3 or tuple(raw_y.shape[:2]) != (b, n) or raw_y.shape[2] % window != 0 or raw_y.shape[2] == 0:
+        raise RuntimeError(f"raw target signals must be ({b}, {n}, Ty*{window}) like the input's clips and nodes, got {tuple(raw_y.shape)}")
+    tx, ty = total // window, raw_y.shape[2] // window
+    perm, log_scale = _check_draws("fft_features_pair", perm, log_scale, b, n, raw_x, permutation=True)
+    feat_raw = _new((b, tx, n, window // 2), raw_x)
+    x_std = torch.empty_like(feat_raw)
+    y_std = _new((b, ty, n, window // 2), raw_x)
+    lib.call("eeg_dcrnn_fft_features_pair", _p(raw_x), _p(raw_y), b, n, tx, ty, int(window), _p(perm), _p(log_scale), float(mean), float(std),
+             _p(feat_raw), _p(x_std), _p(y_std), _stream(raw_x))
+    return feat_raw, x_std, y_std
+
+
+def _fft_features_pair_fake(raw_x, raw_y, window, mean, std, perm, log_scale):
+    b, n, h2 = raw_x.shape[0], raw_x.shape[1], window // 2
+    sx = (b, raw_x.shape[2] // window, n, h2)
+    return raw_x.new_empty(sx), raw_x.new_empty(sx), raw_x.new_empty((b, raw_y.shape[2] // window, n, h2))
+
+
+_define("fft_features_pair", "(Tensor raw_x, Tensor raw_y, int window, float mean, float std, Tensor? perm, Tensor? log_scale) -> "
+        "(Tensor, Tensor, Tensor)", _fft_features_pair_impl, _fft_features_pair_fake)
+
+
+def _augment_features_impl(x, y, perm, log_scale, feature_std: float):
+    lib = _lib.get_lib()
+    x, y = x.contiguous(), y.contiguous()
+    _check(lib, x, "input features")
+    _check(lib, y, "target features")
+    if x.dim() != 4:
+        raise RuntimeError(f"input features must be (B, Tx, N, D), got {tuple(x.shape)}")
+    b, tx, n, d = x.shape
+    if y.dim() != 4 or y.shape[0] != b or tuple(y.shape[2:]) != (n, d):
+        raise RuntimeError(f"target features must be ({b}, Ty, {n}, {d}) like the input's clips, nodes and features, got {tuple(y.shape)}")
+    if perm is None or log_scale is None:
+        raise RuntimeError("augment_features: needs the draws (perm and log_scale)")
+    if not float(feature_std) != 0.0:
+        raise RuntimeError("augment_features: feature_std must be non-zero")
+    perm, log_scale = _check_draws("augment_features", perm, log_scale, b, n, x)
+    # the per-clip quotient (B floats) is left to the framework: it is then the very value the expression
+    # `x.gather(2, idx) + (log_scale / feature_std)[:, None, None, None]` adds, on whichever device
+    shift = (log_scale / float(feature_std)).contiguous()
+    x_out, y_out = torch.empty_like(x), torch.empty_like(y)
+    lib.call("eeg_dcrnn_augment_features", _p(x), _p(y), b, tx, int(y.shape[1]), n, d, _p(perm), _p(shift), _p(x_out), _p(y_out), _stream(x))
+    return x_out, y_out
+
+
+_define("augment_features", "(Tensor x, Tensor y, Tensor perm, Tensor log_scale, float feature_std) -> (Tensor, Tensor)",
+        _augment_features_impl, lambda x, y, perm, log_scale, feature_std: (torch.empty_like(x), torch.empty_like(y)))
+
+
 # =============================================================================================
 # losses that seed backward, optimiser tail
 # =============================================================================================
@@ -1344,6 +1419,29 @@ def fft_features(raw: torch.Tensor, window: int = 200, mean: Optional[float] = N
     fr, fs = torch.ops.eeg_dcrnn.fft_features(raw, int(window), float(mean) if std_on else 0.0,
                                               float(std) if std is not None else 1.0, std_on, perm, log_scale)
     return fr, (fs if std_on else None)
+
+
+def fft_features_pair(raw_x: torch.Tensor, raw_y: torch.Tensor, window: int = 200, mean: float = 0.0, std: float = 1.0,
+                      perm: Optional[torch.Tensor] = None, log_scale: Optional[torch.Tensor] = None):
+    """Featurisation of an SSL sample, which is a pair: raw_x (B,N,Tx*window) input and raw_y (B,N,Ty*window) target signals ->
+    (feat_raw_x (B,Tx,N,window/2): log|FFT| of the un-augmented input, the operand of the correlation graph;
+     x_std (B,Tx,N,window/2), y_std (B,Ty,N,window/2): both halves reflected by the clip's `perm[b]`, shifted by the clip's
+     `log_scale[b]` and standardised with (mean, std)).
+
+    Replaces dataloader_ssl.py:317-341 on top of `computeFFT` per step: one coin and one scale factor per sample, applied to the
+    input AND the target, then the scaler on both.  window = 200: one launch for the pair, every output bit-identical to
+    `fft_features` on that half; another window: the general kernel once per half.  Forward-only: the inputs of a training
+    step carry no gradient."""
+    return torch.ops.eeg_dcrnn.fft_features_pair(raw_x, raw_y, int(window), float(mean), float(std), perm, log_scale)
+
+
+def augment_features(x: torch.Tensor, y: torch.Tensor, perm: torch.Tensor, log_scale: torch.Tensor, feature_std: float):
+    """The reflection / amplitude-jitter augmentation of an SSL pair of already STANDARDISED features, one launch:
+    x_aug[b, t, n] = x[b, t, perm[b][n]] + log_scale[b] / feature_std, and the same for y (each with its own number of steps).
+    x (B,Tx,N,D), y (B,Ty,N,D), D a multiple of 4; perm (B,N) int32 source channel per node, log_scale (B) = log of the clip's
+    amplitude factor, feature_std = the StandardScaler's std (dataloader_ssl.py:159-182,317-341: the reference adds log(factor)
+    BEFORE it standardises).  Returns (x_aug, y_aug), new tensors.  Forward-only: the inputs of a training step carry no gradient."""
+    return torch.ops.eeg_dcrnn.augment_features(x, y, perm, log_scale, float(feature_std))
 
 
 def correlation_supports(x: torch.Tensor, top_k: int = 3, return_adj: bool = False):

@@ -76,6 +76,14 @@ class TrainStep:
         swapped name table); for the distance graph pass `reflected_supports` (`utils.reflected_supports`: the graph of
         `_get_combined_graph(swap_nodes)`) -- every clip then carries the plain or the reflected supports according to its coin
         (per-clip graphs: the general path, not the spectral form).  swap_perm: `utils.swap_permutation(num_nodes)` by default.
+        y, per task and mode: detection -> (B,) float labels; classification -> (B,) int64 classes; ssl -> the clip to predict, as
+        features (B, Ty, N, D) -- or, with raw_window, as RAW signals (B, N, Ty*raw_window) like x.  The SSL sample is a PAIR
+        (dataloader_ssl.py:317-341): the clip's coin and scale factor apply to input AND target, then the scaler to both -- with
+        raw_window one launch featurises both halves (`ops.fft_features_pair`), on feature inputs one launch augments both
+        (`ops.augment_features`); decoder (teacher forcing) and loss see the augmented, standardised target.  Graph side as for the
+        supervised tasks (dataloader_ssl.py:349,355): correlation graph of the un-augmented INPUT clip, or the plain / reflected
+        distance graph per coin.  Only the use_fft form of `_random_scale` (additive in the log domain) is built; its time-domain
+        variant (`use_fft` off: the signals are multiplied) is not.
         raw_window: the step takes RAW resampled signals (B, N, T*raw_window) instead of features and runs the reference's
         DataLoader-side chain on the device in front of the model (dataloader_detection.py:57-71,346-354,384-393): log|FFT| of every
         raw_window-sample step (`eeg_dcrnn_fft_features`) -> z-score with (raw_mean, raw_std) = the model input; with
@@ -168,13 +176,13 @@ class TrainStep:
         if hasattr(self, "lr_dev"):
             self.lr_dev.fill_(self._lr)   # (outside any captured graph: the graph reads the tensor)
 
-    def _use_device_curriculum(self, y) -> bool:
+    def _use_device_curriculum(self, t_out: int, batch: int) -> bool:
         m = self.model
         if self.task != "ssl" or not getattr(m, "use_curriculum_learning", False):
             return False
         if self.device_curriculum is None:
             dec = m.decoder
-            self.device_curriculum = ops.decoder_is_persistent(y.shape[1], y.shape[0], dec.num_nodes, dec.hid_dim, dec.output_dim,
+            self.device_curriculum = ops.decoder_is_persistent(t_out, batch, dec.num_nodes, dec.hid_dim, dec.output_dim,
                                                                dec.decoding_cells[0].num_matrices, dec.num_rnn_layers)
         return self.device_curriculum
 
@@ -213,7 +221,10 @@ class TrainStep:
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
             supports, perm, log_scale = self._draw_augmentation(x.shape[0], supports)
-        if self.raw_window is not None:              # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
+        if self.task == "ssl" and (self.raw_window is not None or perm is not None):
+            # the SSL sample is a pair: the target takes the clip's draws and the scaler like the input (dataloader_ssl.py:317-341)
+            x, y, supports = self._ssl_pair(x, y, supports, perm, log_scale)
+        elif self.raw_window is not None:            # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
             feat_raw, x = ops.fft_features(x, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm, log_scale=log_scale)
             if supports is None:
                 supports = ops.correlation_supports(feat_raw, top_k=3)       # (feat_raw: un-reflected, un-scaled, un-standardised)
@@ -228,7 +239,7 @@ class TrainStep:
         elif self.shared_graph:
             supports = ops.collapse_shared_supports(supports)
         if self.task == "ssl":
-            if self._use_device_curriculum(y):
+            if self._use_device_curriculum(y.shape[1], y.shape[0]):
                 self.model.batches_seen_increment = x.shape[0] * self.world
                 out = self.model(x, y, supports, batches_seen=self.samples_seen_dev)
             else:
@@ -252,6 +263,33 @@ class TrainStep:
         with self.fp.sink:                       # backward operators write into the flat gradient bucket
             out.backward(seed.view_as(out))
         return loss.detach()
+
+    def _ssl_target_steps(self, y) -> int:
+        """decoder steps of an SSL target: feature steps, or whole windows of a raw target (refused otherwise)"""
+        if self.raw_window is None:
+            return y.shape[1]
+        w = self.raw_window
+        if y.dim() != 3 or y.shape[2] == 0 or y.shape[2] % w != 0:
+            raise ValueError(f"TrainStep(task='ssl', raw_window={w}): y is the RAW target (B, num_nodes, Ty*{w}) -- the signals "
+                             f"of the seconds to predict, a whole number of {w}-sample windows -- got {tuple(y.shape)}")
+        return y.shape[2] // w
+
+    def _ssl_pair(self, x, y, supports, perm, log_scale):
+        """data side of the SSL step (dataloader_ssl.py:317-355): (model input, target, supports) with this step's draws (or none)
+        on BOTH halves; the correlation graph comes from the un-reflected, un-scaled INPUT clip, the target plays no part in it"""
+        if self.raw_window is not None:
+            self._ssl_target_steps(y)
+            if y.shape[:2] != x.shape[:2]:
+                raise ValueError(f"TrainStep(task='ssl', raw_window={self.raw_window}): the raw target must be (B, num_nodes, Ty*"
+                                 f"{self.raw_window}) with the input's {x.shape[0]} clips and {x.shape[1]} nodes, got {tuple(y.shape)}")
+            plain, x, y = ops.fft_features_pair(x, y, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm,
+                                                log_scale=log_scale)
+        else:
+            plain = x
+            x, y = ops.augment_features(x, y, perm, log_scale, self.feature_std)
+        if supports is None:
+            supports = ops.correlation_supports(plain, top_k=3)
+        return x, y, supports
 
     def _draw_augmentation(self, batch, supports):
         """this step's draws; with a distance graph and its reflected partner, the per-clip supports"""
@@ -284,12 +322,14 @@ class TrainStep:
         copying into the captured tensors (`x.copy_(batch)`) -- or, without any device-side copy, by capturing the step
         on TWO input sets (`slot` 0 and 1) and alternating `replay_step(slot)`: the host-to-device copy of batch k+1
         then lands directly in the tensors the next replay reads while batch k computes."""
-        if self.task == "ssl" and getattr(self.model, "use_curriculum_learning", False) and not self._use_device_curriculum(y):
+        # (the decoder's steps: feature steps of y, or the whole windows of a raw target)
+        on_device = self.task == "ssl" and self._use_device_curriculum(self._ssl_target_steps(y), y.shape[0])
+        if self.task == "ssl" and getattr(self.model, "use_curriculum_learning", False) and not on_device:
             # host-side teacher-forcing coin flips (model.py:194-200) select which launches are issued: a captured graph would
             # freeze one draw for ever.  (Where the persistent decoder kernels apply the flags are drawn on the device instead.)
             raise RuntimeError("TrainStep.capture: this decoder shape is outside the persistent decoder kernels, so curriculum "
                                "learning draws its teacher-forcing flags on the host every step; use step() (eager launches)")
-        keep = self.snapshot() if self.task == "ssl" and self._use_device_curriculum(y) and not include_update else None
+        keep = self.snapshot() if on_device and not include_update else None
 
         def body():
             loss = self.forward_backward(x, y, seq_lengths, supports)

@@ -105,6 +105,27 @@ int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const i
                            const float* log_scale, float mean, float std_, float* feat_raw,
                            float* feat_std, void* stream);
 
+/* The data side of the SSL sample, which is a PAIR (dataloader_ssl.py:317-341): 60 s of input and the first seconds of the
+ * following clip as target; ONE coin and ONE scale factor per sample (`_random_reflect(…, reflect)` / `_random_scale(…,
+ * scale_factor)`, dataloader_ssl.py:159-182) applied to both halves, then the StandardScaler on both.  raw_x (B,N,Tx*W),
+ * raw_y (B,N,Ty*W); perm (B,N) int32 / log_scale (B) as for eeg_dcrnn_fft_features, nullable (no augmentation).
+ *   feat_raw_x (B,Tx,N,W/2), nullable : log|FFT| of the un-reflected, un-scaled INPUT clip, the operand of the correlation
+ *                                       graph (dataloader_ssl.py:349; the target plays no part in the graph);
+ *   x_std (B,Tx,N,W/2), y_std (B,Ty,N,W/2) : ((log|FFT| of channel perm[b][n]) + log_scale[b] - mean) / std of each half.
+ * W = 200: both halves in ONE launch; every output is bit-identical to eeg_dcrnn_fft_features on that half (the same transform,
+ * re-scheduled).  Any other W: the general kernel of eeg_dcrnn_fft_features, once per half. */
+int eeg_dcrnn_fft_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
+                                const float* log_scale, float mean, float std_, float* feat_raw_x, float* x_std, float* y_std,
+                                void* stream);
+
+/* The same augmentation on an SSL pair of already STANDARDISED features (dataloader_ssl.py:159-182,317-341 followed by
+ * utils.py:393-428: reflecting commutes with the scaler, and adding log(scale) before it = adding log(scale) / std behind it):
+ *   x_out[b,t,n,:] = x[b,t,perm[b][n],:] + shift[b],   y_out likewise,   shift[b] = log_scale[b] / std.
+ * x, x_out (B,Tx,N,D); y, y_out (B,Ty,N,D); D % 4 == 0, 16-byte aligned, outputs distinct from inputs.  One launch, one read and
+ * one write of every value (HBM-bound: algorithmic bytes 8*B*(Tx+Ty)*N*D); a perm entry outside 0..N-1 selects the node itself. */
+int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, int Ty, int N, int D, const int32_t* perm,
+                               const float* shift, float* x_out, float* y_out, void* stream);
+
 /* Per-clip correlation graph and its dual random-walk supports, from the clips themselves
  * (replaces the DataLoader-side CPU code: dataloader_detection.py:258-307 `_get_indiv_graphs`
  * = |normalised lag-0 cross-correlation| of every electrode pair of the (N, T*D) clip, diag 1;
