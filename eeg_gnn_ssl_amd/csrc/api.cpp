@@ -58,14 +58,8 @@ long long* seq_probe_arg(hipStream_t st) {
 #endif
 }
 
-// the dev build's phase probe is armed (its instantiations exist for the register-resident kernels only)
-bool phase_probe_armed() {
-#if defined(EEG_DEV)
-    return g_seq_probe != nullptr;
-#else
-    return false;
-#endif
-}
+// a launch with this `probe` argument carries the dev build's armed phase probe (the product's clock-sample buffer is no such probe)
+bool carries_phase_probe(const long long* probe) { return eeg::kDevBuild && probe != nullptr; }
 
 int fail(const char* fmt, ...) {
     va_list ap;
@@ -83,17 +77,13 @@ inline hipStream_t S_(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 using namespace eeg;
 
-bool h_supported(int H) { return H == 16 || H == 32 || H == 64; }
-bool m_supported(int M) { return M == 1 || M == 2 || M == 3 || M == 4 || M == 5 || M == 7; }
-
 int check_dims(int N, int H, int Fin, int M) {
     if (N < 1 || N > kMaxNodes) return fail("num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
-    if (!h_supported(H)) return fail("rnn_units=%d unsupported (16, 32 or 64)", H);
+    if (!seq_h_supported(H)) return fail("rnn_units=%d unsupported (16, 32 or 64)", H);
     if (Fin < 4 || Fin % 4 != 0) return fail("per-node input dim=%d unsupported (must be a positive multiple of 4)", Fin);
-    if (!m_supported(M)) return fail("num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
-    // LDS of the BPTT kernel (SeqGeom::bwd_lds_floats): the widest case (H=64, M=7) only fits montages of <= 20 nodes
-    const int ka = M * H, rows = N <= 20 ? 20 : 32;
-    const size_t bwd = ((size_t)(M - 1) * kPFloats + (size_t)rows * (lds_stride_x(ka) + lds_stride_x(2 * ka))) * sizeof(float);
+    if (!seq_m_supported(M)) return fail("num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
+    // LDS of the one-wave BPTT kernel: the widest case (H=64, M=7) only fits montages of <= 20 nodes
+    const size_t bwd = seq_bwd_lds_floats(H, M, seq_bwd_rows(H, M, seq_nks(N))) * sizeof(float);
     if (bwd > kMaxLdsBytes)
         return fail("rnn_units=%d with %d hop matrices and %d nodes needs %zu KB of LDS for the backward pass (160 available)",
                     H, M, N, bwd / 1024);
@@ -353,37 +343,40 @@ int diffuse_adj(const float* Z, const float* P, int p_batched, int S, int B, int
     return 0;
 }
 
-// the two-wave recurrent kernels exist in a SPEC instantiation (spectral form: seq_launch.h) for exactly these calls -- mirrors the
-// selection inside seq_inst.cpp (64 units, at most 20 nodes, 2 or 3 hop matrices, two-wave variant on, 2 GB buffer descriptors)
-bool seq2_spec_ok(int H, int M, int N, int T, int B, int variant, int Sp, int SpE) {
-    if (H != 64 || N < 16 || N > 20 || M < 2 || M > 3 || variant != 1 || (phase_probe_armed() && M != 3)) return false;   // (probe instantiations: M = 3)
-    return (double)T * B * N * 3 * H * sizeof(float) < 2147483648.0 && (double)N * Sp * 3 * H * sizeof(float) < 2147483648.0 &&
-           (double)N * SpE * H * sizeof(float) < 2147483648.0;
+// The recurrent launches: the caller makes the plan (seq_launch.h) from one of these calls, lays its operands out by plan.kind,
+// and the plan is executed here.  The knobs are compile-time zeros in the product build.
+SeqCall seq_fwd_call(int H, int M, int N, int T, int B, size_t plane_stride, const long long* probe) {
+    SeqCall c{H, M, N, T, B};
+    c.plane_stride = plane_stride;
+    c.knob_one_wave = g_tune[EEG_TUNE_SEQ_FWD_ONE_WAVE];
+    c.knob_no_spec = g_tune[EEG_TUNE_SEQ_FWD_NO_SPEC];
+    c.probe = carries_phase_probe(probe);
+    return c;
 }
-
-int seq_fwd(int H, int M, const SeqFwdArgs& a, hipStream_t st) {
-    int rc = H == 16 ? launch_seq_fwd_h16(M, a, st) : H == 32 ? launch_seq_fwd_h32(M, a, st) : launch_seq_fwd_h64(M, a, st);
-    if (rc == 1) return fail("seq_fwd: no kernel for H=%d M=%d", H, M);
-    if (rc == 2) return fail("seq_fwd: kernel launch failed (H=%d M=%d)", H, M);
-    if (rc == 3) return fail("seq_fwd: H=%d M=%d N=%d exceeds the LDS of a CU", H, M, a.N);
+SeqCall seq_bwd_call(int H, int M, int N, int T, int B, const long long* probe) {
+    SeqCall c{H, M, N, T, B};
+    c.knob_one_wave = g_tune[EEG_TUNE_SEQ_BWD_ONE_WAVE];
+    c.knob_no_spec = g_tune[EEG_TUNE_SEQ_BWD_NO_SPEC];
+    c.knob_stream = g_tune[EEG_TUNE_SEQ_STREAM];
+    c.probe = carries_phase_probe(probe);
+    return c;
+}
+int seq_plan_error(const char* what, const SeqPlan& p, int H, int M, int N) {
+    if (p.error == kSeqNoKernel) return fail("%s: no kernel for H=%d M=%d", what, H, M);
+    if (p.error == kSeqNoFit) return fail("%s: H=%d M=%d N=%d exceeds the LDS of a CU", what, H, M, N);
     return 0;
 }
-// BPTT with more clips than 1.5 x the CUs at hop counts the two-wave kernel does not cover: two streamed-weight
-// workgroups per CU (kernels_seq_stream.h; dev knob 3: 1 = wherever the kernel exists, 2 = never)
-bool seq_stream_wanted(int H, int M, int B, int N) {
-    if (H != 64 || N > kDecRows || M > 5 || g_tune[3] == 2) return false;
-    return g_tune[3] == 1 || (M >= 4 && B >= 384);
+int seq_fwd(int H, int M, const SeqPlan& p, const SeqFwdArgs& a, hipStream_t st) {
+    if (seq_plan_error("seq_fwd", p, H, M, a.N)) return 1;
+    if (H == 16 ? launch_seq_fwd_h16(M, p, a, st) : H == 32 ? launch_seq_fwd_h32(M, p, a, st) : launch_seq_fwd_h64(M, p, a, st))
+        return fail("seq_fwd: kernel launch failed (H=%d M=%d)", H, M);
+    return 0;
 }
-int seq_bwd(int H, int M, const SeqBwdArgs& a, hipStream_t st) {
-    if (a.variant != 0 && !phase_probe_armed() && seq_stream_wanted(H, M, a.B, a.N)) {   // (the streamed kernel takes no clock samples either)
-        const int rs = launch_seq_bwd_stream(M, a, st);
-        if (rs == 0) return 0;
-        if (rs == 2) return fail("seq_bwd: streamed kernel launch failed (M=%d)", M);
-    }
-    int rc = H == 16 ? launch_seq_bwd_h16(M, a, st) : H == 32 ? launch_seq_bwd_h32(M, a, st) : launch_seq_bwd_h64(M, a, st);
-    if (rc == 1) return fail("seq_bwd: no kernel for H=%d M=%d", H, M);
-    if (rc == 2) return fail("seq_bwd: kernel launch failed (H=%d M=%d)", H, M);
-    if (rc == 3) return fail("seq_bwd: H=%d M=%d N=%d exceeds the LDS of a CU", H, M, a.N);
+int seq_bwd(int H, int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st) {
+    if (seq_plan_error("seq_bwd", p, H, M, a.N)) return 1;
+    if (p.kind == SeqKind::Stream) return launch_seq_bwd_stream(M, p, a, st) ? fail("seq_bwd: streamed kernel launch failed (M=%d)", M) : 0;
+    if (H == 16 ? launch_seq_bwd_h16(M, p, a, st) : H == 32 ? launch_seq_bwd_h32(M, p, a, st) : launch_seq_bwd_h64(M, p, a, st))
+        return fail("seq_bwd: kernel launch failed (H=%d M=%d)", H, M);
     return 0;
 }
 
@@ -732,9 +725,9 @@ size_t eeg_dcrnn_pack_floats(int Fin, int H, int M) { return make_cell_pack(Fin,
 
 int eeg_dcrnn_pack_cell(const float* Wg, const float* bg, const float* Wc, const float* bc, int Fin, int H, int M,
                         float* pack, void* stream) {
-    if (!h_supported(H)) return fail("pack_cell: rnn_units=%d unsupported", H);
+    if (!seq_h_supported(H)) return fail("pack_cell: rnn_units=%d unsupported", H);
     if (Fin < 4 || Fin % 4 != 0) return fail("pack_cell: input dim %d must be a positive multiple of 4", Fin);
-    if (!m_supported(M)) return fail("pack_cell: num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
+    if (!seq_m_supported(M)) return fail("pack_cell: num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
     CellPack p = make_cell_pack(Fin, H, M);
     EEG_LAUNCH_P("pack_cell", pack_cell_kernel, dim3(512), dim3(256), 0, S_(stream), Wg, bg, Wc, bc, pack, p);
     return check_launch("pack_cell");
@@ -794,8 +787,8 @@ int eeg_dcrnn_pack_cells(int n_cells, const float* const* Wg, const float* const
                          void* stream) {
     if (n_cells < 1 || n_cells > 4) return fail("pack_cells: %d cells (1..4 per launch)", n_cells);
     if (Wg == nullptr || bg == nullptr || Wc == nullptr || bc == nullptr || Fin == nullptr || packs == nullptr) return fail("pack_cells: null pointer table");
-    if (!h_supported(H)) return fail("pack_cells: rnn_units=%d unsupported", H);
-    if (!m_supported(M)) return fail("pack_cells: num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
+    if (!seq_h_supported(H)) return fail("pack_cells: rnn_units=%d unsupported", H);
+    if (!seq_m_supported(M)) return fail("pack_cells: num hop matrices M=%d unsupported (1,2,3,4,5,7)", M);
     if ((basis == nullptr) != (spacks == nullptr)) return fail("pack_cells: the per-frequency packs need the basis block and their output table");
     int fin[4];
     for (int c = 0; c < n_cells; ++c) {
@@ -869,26 +862,25 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
         if (nnf > 0) return fail("gemm_nnf: launch failed");
         if (nnf < 0 && launch_nng(planes, Fin, Sp, N, d->spack + sp.sxq, sp.sxq_stride, sp.nct_x, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
                                   d->spectral + spec_csum_offset(N), xgs)) return fail("gemm_nng: launch failed");
-        int done = 0;
         SeqFwdArgs a{XW, h0 != nullptr ? Hext : nullptr, P, d->p_batched, pack + p.bhg, pack + p.bhc, Hext + state, Rs, Us, Cs, RHs, nullptr, nullptr,
                      (size_t)0, d->T, d->B, N, d->act, seq_probe_arg(st)};
-        a.variant = g_tune[12] == 0 ? 1 : 0;
-        // the two-wave kernel in its SPEC instantiation where it applies (dev knob 22 = 1: the mixes as separate passes)
-        if (g_tune[22] == 0 && seq2_spec_ok(H, M, N, d->T, d->B, a.variant, Sp, SpE)) {
-            a.spec_U = d->spectral; a.Yh = Yh; a.Hh = Hplanes; a.RHh = RHplanes; a.spec_Sp = Sp; a.spec_SpE = SpE; a.spec_done = &done;
-            if (seq_fwd(H, M, a, st)) return 1;
-            if (!done) return fail("layer_fwd: the fused spectral recurrent kernel was not selected (internal)");
-        }
-        if (!done) {
+        SeqCall call = seq_fwd_call(H, M, N, d->T, d->B, 0, a.probe);
+        call.spectral = true; call.Sp = Sp; call.SpE = SpE;
+        const SeqPlan plan = seq_fwd_plan(call);
+        if (plan.kind == SeqKind::TwoWaveSpec) {   // the two-wave kernel in its SPEC instantiation: the mixes happen inside
+            a.XW = Yh; a.Hpl = Hplanes; a.RHpl = RHplanes; a.spec_U = d->spectral; a.spec_Sp = Sp; a.spec_SpE = SpE;
+            if (seq_fwd(H, M, plan, a, st)) return 1;
+            if (Hplanes != nullptr) {
+                if (launch_spec_zero_rows(Hplanes, N, (d->T + 1) * d->B, SpE, H, st)) return fail("spec_zero_rows: launch failed");
+                if (launch_spec_zero_pad(RHplanes, N, S, H, st)) return fail("spec_zero_pad: launch failed");
+            }
+        } else {                                   // the mixes as separate passes
             if (launch_spec_mix(0, Yh, d->spectral, nullptr, N, d->T, d->B, 3 * H, 0, XW, st, "spec_mix_y")) return fail("spec_mix: launch failed");
-            if (seq_fwd(H, M, a, st)) return 1;
+            if (seq_fwd(H, M, plan, a, st)) return 1;
             if (Hplanes != nullptr) {
                 if (launch_spec_mix(1, Hext, d->spectral, nullptr, N, d->T + 1, d->B, H, 0, Hplanes, st, "spec_mix_h", SpE)) return fail("spec_mix: launch failed");
                 if (launch_spec_mix(1, RHs, d->spectral, nullptr, N, d->T, d->B, H, 0, RHplanes, st, "spec_mix_h")) return fail("spec_mix: launch failed");
             }
-        } else if (Hplanes != nullptr) {
-            if (launch_spec_zero_rows(Hplanes, N, (d->T + 1) * d->B, SpE, H, st)) return fail("spec_zero_rows: launch failed");
-            if (launch_spec_zero_pad(RHplanes, N, S, H, st)) return fail("spec_zero_pad: launch failed");
         }
         return check_launch("layer_fwd (spectral)");
     } else if (d->x_planes_ready) {
@@ -910,8 +902,7 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
     if ((Hplanes != nullptr) != (RHplanes != nullptr)) return fail("layer_fwd: Hplanes/RHplanes must be both NULL or both non-NULL");
     SeqFwdArgs a{XW, h0 != nullptr ? Hext : nullptr, P, d->p_batched, pack + p.bhg, pack + p.bhc, Hext + state, Rs, Us, Cs, RHs, Hplanes, RHplanes,
                  (size_t)(d->T + 1) * state, d->T, d->B, d->N, d->act, seq_probe_arg(st)};
-    a.variant = g_tune[12] == 0 ? 1 : 0;          // two waves per SIMD where that kernel exists (knob 12 = 1: off)
-    return seq_fwd(H, M, a, st);
+    return seq_fwd(H, M, seq_fwd_plan(seq_fwd_call(H, M, d->N, d->T, d->B, a.plane_stride, a.probe)), a, st);
 }
 
 size_t eeg_dcrnn_layer_bwd_ws_floats(const eeg_layer_dims* d, int need_dx) { return layer_dims_positive(d) ? bwd_ws(d, need_dx).total : 0; }
@@ -935,12 +926,12 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
     SeqBwdArgs a{Hext + state, Hext, Rs, Us, Cs, dHseq, d_at_end, d_at_len,
                  reinterpret_cast<const long long*>(lengths), P, d->p_batched, pack + p.b1, pack + p.b2,
                  dXW, dh0, dbias, d->T, d->B, N, d->act, seq_probe_arg(st)};
-    a.variant = g_tune[13] == 0 ? 1 : 0;          // two waves per SIMD where that kernel exists (knob 13 = 1: off)
-    int dyh_done = 0;                             // spectral form: the two-wave BPTT kernel writes dYh = U^T dXW itself (dev knob 21 = 1: separate pass)
-    if (d->spectral != nullptr && g_tune[21] == 0 && seq2_spec_ok(H, M, N, d->T, d->B, a.variant, spec_rows(S), d->B + spec_rows(S))) {
-        a.spec_U = d->spectral; a.dYh = ws + w.dyh; a.spec_Sp = spec_rows(S); a.spec_done = &dyh_done;
-    }
-    if (seq_bwd(H, M, a, st)) return 1;
+    SeqCall call = seq_bwd_call(H, M, N, d->T, d->B, a.probe);
+    call.spectral = d->spectral != nullptr; call.Sp = spec_rows(S); call.SpE = d->B + spec_rows(S);
+    const SeqPlan plan = seq_bwd_plan(call);
+    const bool dyh_done = plan.kind == SeqKind::TwoWaveSpec;   // spectral form: the two-wave BPTT kernel writes dYh = U^T dXW itself
+    if (dyh_done) { a.spec_U = d->spectral; a.dYh = ws + w.dyh; a.spec_Sp = call.Sp; }
+    if (seq_bwd(H, M, plan, a, st)) return 1;
     // 2. weight gradients (hoisted, split-K with fixed-order reduction); the bias sums ride in their reduction launch
     const size_t xs = d->x_plane_stride > 0 ? (size_t)d->x_plane_stride : (size_t)R * Fin;
     BtMap bt;
@@ -1138,7 +1129,7 @@ size_t eeg_dcrnn_decoder_bwd_ws_floats(const eeg_decoder_dims* d) { return dec_d
 static bool dec_persistent_ok(const eeg_decoder_dims* d) {
     const int q4 = d->Dout / 4;
     return d->H == 64 && d->N <= kDecRows && d->L >= 1 && d->L <= 4 && d->T >= 1 && d->T <= 64 && d->Dout <= 128
-           && (q4 % 5 == 0 || q4 % 4 == 0) && m_supported(d->M)
+           && (q4 % 5 == 0 || q4 % 4 == 0) && seq_m_supported(d->M)
            && dec_fwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes
            && dec_bwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes;
 }
@@ -1223,8 +1214,7 @@ int eeg_dcrnn_decoder_fwd(const eeg_decoder_dims* d, const float* targets, const
                          saved + y.us[l] + (size_t)t * state, saved + y.cs[l] + (size_t)t * state,
                          saved + y.rhs[l] + (size_t)t * state, saved + y.hpl[l] + (size_t)t * state,
                          saved + y.rpl[l] + (size_t)t * state, hstride, 1, B, N, d->act, nullptr};
-            a.variant = g_tune[12] == 0 ? 1 : 0;
-            if (seq_fwd(H, M, a, st)) return 1;
+            if (seq_fwd(H, M, seq_fwd_plan(seq_fwd_call(H, M, N, 1, B, hstride, nullptr)), a, st)) return 1;
         }
         // projection (model.py:188-191): out_t = drop(h_top) W_p^T + b_p
         if (drop.on) {
@@ -1321,8 +1311,7 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
                          t == T - 1 ? nullptr : dhn_in, nullptr, nullptr, P, d->p_batched, pack + p.b1, pack + p.b2,
                          dXW, t == 0 ? dh0 + (size_t)l * state : dhn_out, ws + y.dbias[l] + (size_t)t * B * 3 * H,
                          1, B, N, d->act, nullptr};
-            a.variant = g_tune[13] == 0 ? 1 : 0;
-            if (seq_bwd(H, M, a, st)) return 1;
+            if (seq_bwd(H, M, seq_bwd_plan(seq_bwd_call(H, M, N, 1, B, nullptr)), a, st)) return 1;
             const bool need_dx = l > 0 || (t > 0 && feeds_back(t - 1));
             if (need_dx) {
                 SegPtrs sd;

@@ -20,8 +20,14 @@ namespace eeg {
 
 constexpr int kWave = 64;
 constexpr int kMaxNodes = 32;   // node rows are padded to two 16-row MFMA tiles
+constexpr int kDecRows = 20;    // node rows of the LDS tiles of the decoder / streamed-weight kernels (montages of at most 20 nodes)
 constexpr size_t kMaxLdsBytes = 160 * 1024;   // LDS of one gfx950 CU
 constexpr int kMaxM = 8;        // hop matrices incl. identity (K<=3 with two supports -> 7)
+#if defined(EEG_DEV)            // make dev / the test emulator: tuning knobs + the recurrent kernels' cycle probe
+constexpr bool kDevBuild = true;
+#else
+constexpr bool kDevBuild = false;
+#endif
 
 __host__ __device__ constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ constexpr int round_up(int a, int b) { return ceil_div(a, b) * b; }

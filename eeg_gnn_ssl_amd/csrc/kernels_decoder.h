@@ -395,8 +395,6 @@ __device__ __forceinline__ void gemm_stream_nnq(const float* __restrict__ tile, 
     }
 }
 
-constexpr int kDecRows = 20;     // node rows of the LDS tiles (montages of at most 20 nodes)
-
 // LDS floats of dec_fwd_persist_kernel<64, M>
 __host__ __device__ constexpr size_t dec_fwd_lds_floats(int M, int L, int Dout) {
     const int H = 64, KAP = M * H, XS = lds_stride_q(M * round_up(Dout, 16));

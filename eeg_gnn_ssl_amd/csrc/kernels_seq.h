@@ -32,19 +32,47 @@
 
 namespace eeg {
 
+// Which instantiations of the family exist, as functions of integers: the instantiation units ask with template arguments
+// (`if constexpr`), the launch plan (seq_launch.h) with run-time ones, so a plan cannot name a kernel that was not compiled.
+// NKS = k-steps of the node mix: 5 covers N <= 20 (the 19-electrode graph), 8 covers N <= 32.
+constexpr int seq_nks(int N) { return N <= 20 ? 5 : 8; }
+// two waves per SIMD (seq_fwd2_kernel, seq_bwd2_kernel).  M >= 4: the r + c weights of a forward wave / w1 + half of w2 of a
+// backward role-A wave no longer fit in 256 registers
+constexpr bool seq_has_two_wave(int H, int M, int nks) { return H == 64 && nks == 5 && M <= 3; }
+constexpr bool seq_has_spec(int H, int M, int nks) { return seq_has_two_wave(H, M, nks) && M >= 2; }   // their SPEC form (M = 1: no mix)
+// cycle-probe instantiations (one-wave, two-wave, SPEC): dev build only; the streamed kernel takes no clock samples
+constexpr bool seq_has_probe(int H, int M, int nks) { return kDevBuild && H == 64 && M == 3 && nks == 5; }
+constexpr bool seq_has_stream(int H, int M) { return H == 64 && M <= 5; }   // seq_bwd_stream_kernel (kernels_seq_stream.h), N <= kDecRows
+
 template <int H, int M>
 struct SeqGeom {
     static constexpr int KA = M * H, KAP = lds_stride_x(KA), KS = KA / 4;        // h-wide hop tile (swizzled, common.h)
     static constexpr int KG = M * 2 * H, KGP = lds_stride_x(KG), KSG = KG / 4;   // 2H-wide hop tile (bwd)
     static constexpr int NGT = 2 * H / 16, NCT = H / 16;                         // gate / cand col tiles
     static constexpr int GT = ceil_div(NGT, 4), CT = ceil_div(NCT, 4);           // per wave (4 waves)
-    static constexpr size_t fwd_lds_floats() { return (size_t)(M - 1) * kPFloats + 2 * 32 * KAP; }
-    // Node rows of the backward kernel's LDS tiles: 32 (two MFMA node tiles), or -- where 32 rows exceed the
-    // 160 KB of a CU (H=64, M=7) and the montage has at most 20 nodes, so that the second tile runs on the
-    // 4x4x1 MFMA and only rows 16..19 are ever read -- 20.
-    static constexpr size_t bwd_lds_floats(int rows) { return (size_t)(M - 1) * kPFloats + (size_t)rows * (KAP + KGP); }
-    static constexpr int bwd_rows(int nks) { return (nks == 5 && bwd_lds_floats(32) * sizeof(float) > kMaxLdsBytes) ? 20 : 32; }
 };
+// Dynamic LDS of the kernels in floats, for run-time (H, M) too (the kernels carve their `sm` in this order):
+// seq_fwd_kernel: hop polynomials + A, A2 [32][KAP]
+constexpr size_t seq_fwd_lds_floats(int H, int M) { return (size_t)(M - 1) * kPFloats + 2 * 32 * lds_stride_x(M * H); }
+// seq_fwd2_kernel: + the update-gate tile U [16][64]; SPEC: + XR, 2 x XC [16][64], XRr [4][64], W1L [4][KS/4][64][4]
+constexpr size_t seq_fwd2_lds_floats(int H, int M, bool spec) {
+    return seq_fwd_lds_floats(H, M) + 16 * 64 + (spec ? 3 * 16 * 64 + 4 * 64 + 4 * (M * H / 4 / 4) * 256 : 0);
+}
+// seq_bwd_kernel: hop polynomials + EC [rows][KAP] + EG [rows][KGP].  Node rows of the tiles: 32 (two MFMA node tiles), or --
+// where 32 rows exceed the 160 KB of a CU (H=64, M=7) and the montage has at most 20 nodes, so that the second tile runs on the
+// 4x4x1 MFMA and only rows 16..19 are ever read -- 20.
+constexpr size_t seq_bwd_lds_floats(int H, int M, int rows) {
+    return (size_t)(M - 1) * kPFloats + (size_t)rows * (lds_stride_x(M * H) + lds_stride_x(M * 2 * H));
+}
+constexpr int seq_bwd_rows(int H, int M, int nks) { return (nks == 5 && seq_bwd_lds_floats(H, M, 32) * sizeof(float) > kMaxLdsBytes) ? 20 : 32; }
+// seq_bwd2_kernel: 32-row tiles + DP [4][20][20] + two coefficient buffers of 4 x (5*256 + 256 + 64) floats
+constexpr size_t seq_bwd2_lds_floats(int H, int M) { return seq_bwd_lds_floats(H, M, 32) + 4 * 20 * 20 + 2 * 4 * (5 * 256 + 256 + 64); }
+// seq_bwd_stream_kernel<64, M>: [kDecRows]-row tiles.  (the hop polynomials are only staged through the tile area: after
+// load_poly_frags they live in registers -- at M = 5 the tiles of two workgroups take 150 of the 160 KB of a CU)
+constexpr size_t seq_stream_bwd_lds_floats(int M) {
+    const size_t tiles = (size_t)kDecRows * (M * 64 + M * 128), polys = (size_t)(M - 1) * kPFloats;
+    return tiles > polys ? tiles : polys;
+}
 
 
 // acc[i][nt] += W-frag[i][.] x X(32 nodes x 4*NKS, LDS, stride)^T for NT column tiles; the node
@@ -635,6 +663,7 @@ __global__ __launch_bounds__(512, 1) void seq_fwd2_kernel(
     //  of them keeps in registers for the whole launch stays allocated while the other runs)
     const int tid = threadIdx.x, lane = tid & 63, wave8 = SPEC ? wave_uniform(tid >> 6) : (tid >> 6), role = wave8 >> 2, wave = wave8 & 3;
     const int lr = lane & 15, lg = lane >> 4;
+    // (the launch plan sizes what follows by seq_fwd2_lds_floats: keep the two in step)
     float* U = A2 + 32 * KAP;                      // [16][UST] update gate of nodes 0..15 of the current step
     float* XR = U + 16 * UST;                      // SPEC: [16][UST] r pre-activations of nodes 0..15 of the next step (from role B)
     float* XC = XR + 16 * UST;                     //       ... of c, two buffers (step parity: written one phase after the other is read)
@@ -970,7 +999,7 @@ __global__ __launch_bounds__(256, 1) void seq_bwd_kernel(
     pp.start();
     EEG_DYN_SMEM(sm);
     float* Pl = sm;
-    constexpr int ROWS = G::bwd_rows(NKS);
+    constexpr int ROWS = seq_bwd_rows(H, M, NKS);
     float* EC = Pl + (M - 1) * kPFloats;    // [ROWS][KAP]  slot 0 = dC, slots m = P_m^T dC
     float* EG = EC + ROWS * KAP;            // [ROWS][KGP]  slot 0 = [dR|dU], slots m = P_m^T [dR|dU]
     constexpr bool REM4 = NKS == 5;
@@ -1293,6 +1322,7 @@ __global__ __launch_bounds__(512, 1) void seq_bwd2_kernel(
     float* DP = EG + ROWS * KGP + ct * (20 * DPS);                     // [20][DPS] GEMM2 result + external gradient, tile ct
     float* CF0 = EG + ROWS * KGP + 4 * 20 * DPS + ct * kCoefTile;      // this column tile's coefficient block, buffer 0 (buffer 1: + 4 * kCoefTile)
     constexpr int kZero = ROWS * (KAP + KGP) + 4 * 20 * DPS + 2 * 4 * kCoefTile;   // floats cleared per clip
+    static_assert((size_t)(M - 1) * kPFloats + kZero == seq_bwd2_lds_floats(H, M), "the launch plan sizes the dynamic LDS by seq_bwd2_lds_floats");
     const int node[2] = {lr, 16 + lr};
     const bool valid[2] = {lr < N, 16 + lr < N};
     const int nodec[2] = {valid[0] ? lr : N - 1, valid[1] ? 16 + lr : N - 1};

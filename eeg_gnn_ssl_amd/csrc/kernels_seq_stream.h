@@ -14,13 +14,6 @@
 
 namespace eeg {
 
-// (the hop polynomials are only staged through the tile area: after load_poly_frags they live in registers -- at M = 5
-//  the tiles of two workgroups take 150 of the 160 KB of a CU)
-__host__ __device__ constexpr size_t seq_stream_bwd_lds_floats(int M) {
-    const size_t tiles = (size_t)kDecRows * (M * 64 + M * 128), polys = (size_t)(M - 1) * kPFloats;
-    return tiles > polys ? tiles : polys;
-}
-
 // BPTT, same contract as seq_bwd_kernel (operands one step ahead, d_at_end / d_at_len / lengths, dXW, dh0 and the
 // per-clip bias-gradient sums), weights b1 / b2 streamed.
 template <int H, int M>

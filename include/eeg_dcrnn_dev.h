@@ -35,6 +35,14 @@ int eeg_dcrnn_set_seq_probe(int64_t* probe);
  * keys 5 / 6 / 7: target workgroup counts of the streaming diffusion (forward / adjoint) and the correlation-Gram launches.
  * Defaults (all 0) = the product configuration. */
 int eeg_dcrnn_set_tuning(int key, int value);
+/* the keys that select among the recurrent kernels (the inputs of the launch plans, csrc/seq_launch.h) */
+enum {
+    EEG_TUNE_SEQ_STREAM = 3,
+    EEG_TUNE_SEQ_FWD_ONE_WAVE = 12,
+    EEG_TUNE_SEQ_BWD_ONE_WAVE = 13,
+    EEG_TUNE_SEQ_BWD_NO_SPEC = 21,
+    EEG_TUNE_SEQ_FWD_NO_SPEC = 22
+};
 
 #ifdef __cplusplus
 }
