@@ -37,9 +37,9 @@ thread_local char g_err[512] = "";
 // include/eeg_dcrnn_dev.h).  In the product build the knobs are compile-time zeros and there is no probe.
 #if defined(EEG_DEV)
 long long* g_seq_probe = nullptr;  // see eeg_dcrnn_set_seq_probe
-int g_tune[24] = {0};               // see eeg_dcrnn_set_tuning
+int g_tune[EEG_TUNE_COUNT] = {0};               // see eeg_dcrnn_set_tuning
 #else
-constexpr int g_tune[24] = {0};
+constexpr int g_tune[EEG_TUNE_COUNT] = {0};
 #endif
 
 std::atomic<long long*> g_clock_samples{nullptr};   // eeg_dcrnn_prof_clock_samples (measurement hook, like the event recorder)
@@ -93,166 +93,112 @@ int check_dims(int N, int H, int Fin, int M) {
 // CUs of the current device (the persistent GEMMs size their grids by it); queried once per process
 int num_cus() { return platform_num_cus(); }
 
-// fewest rows the persistent round-3 GEMMs are used for (below it the ramp of their 2-per-CU grid costs more than the
-// round-2 kernels' many small workgroups); dev knob 2, bits 2..: rows per CU instead of the default
-int q_min_rows() { return ((g_tune[2] >> 2) > 0 ? (g_tune[2] >> 2) : 256) * num_cus(); }
+// ---- hoisted GEMMs -----------------------------------------------------------------------------
+// The caller makes a plan (gemm_launch.h) from one of these calls, sizes its buffers and picks its operands by the plan, and the
+// plan is executed here: the template switch and one launch per kernel signature.  The knobs are compile-time zeros in the
+// product build.
+GemmKnobs gemm_knobs() {
+    return GemmKnobs{g_tune[EEG_TUNE_NN_STAGED], g_tune[EEG_TUNE_TN_STAGED], g_tune[EEG_TUNE_QUAD], g_tune[EEG_TUNE_TN_XCD],
+                     g_tune[EEG_TUNE_TN_WIDE_FROM], g_tune[EEG_TUNE_TN_TARGET], g_tune[EEG_TUNE_TNQ_TARGET], g_tune[EEG_TUNE_TN_NO_PAIR]};
+}
+// the A segments of a GEMM are batch-major (B clips x T steps x N nodes): the kernels with a row map read them through it
+struct BtMap { int T = 0, B = 0, N = 0; };
+NnCall nn_call(int nseg, int F, int R, int nct_total, int ldc, int O, BtMap bt = BtMap(), bool quad_pack = false, int bf3_nct = 0) {
+    return NnCall{nseg, F, R, nct_total, ldc, O, bt.T > 0, quad_pack, bf3_nct, num_cus(), gemm_knobs()};
+}
+TnCall tn_call(int nseg, int F, int R, int O, bool batch_major = false, bool offer_quad = false) {
+    return TnCall{nseg, F, R, O, batch_major, offer_quad, num_cus(), gemm_knobs()};
+}
 
-// ---- GEMM dispatch ---------------------------------------------------------------------------
+// the right-hand side of an NN GEMM in the forms the caller holds: the fp32 pack, its quad order (kernels_pack.h: bxq / bxtq;
+// NnCall::quad_pack) and the bf16 term pack (NnCall::bf3_nct)
+struct NnRhs { const float* Bp; const float* Bq = nullptr; const unsigned short* W3 = nullptr; };
 template <int NCTW, int KC>
-int run_nn(const SegPtrs& segs, int nseg, int F, int R, const float* Bp, int nct_total, const float* bias,
-           float* C, int ldc, int O, hipStream_t st, const char* tag) {
-    constexpr int KCS = lds_stride(KC), NB = 2 * NCTW;
-    const size_t lds = 2 * (size_t)(128 * KCS + (KC / 4) * NB * 64) * sizeof(float);
-    EEG_SET_MAX_LDS((gemm_nn_kernel<NCTW, KC>), lds);
-    dim3 grid(ceil_div(R, 128), ceil_div(nct_total, NB));
-    EEG_LAUNCH_P(tag, (gemm_nn_kernel<NCTW, KC>), grid, dim3(256), lds, st, segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O);
+int run_nn(const NnPlan& p, const NnCall& c, const SegPtrs& segs, const NnRhs& B, const float* bias, float* C, hipStream_t st, const char* tag) {
+    EEG_SET_MAX_LDS((gemm_nn_kernel<NCTW, KC>), p.lds);
+    EEG_LAUNCH_P(tag, (gemm_nn_kernel<NCTW, KC>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, segs, c.nseg, c.F, c.R, B.Bp, c.nct_total, bias, C, c.ldc, c.O);
     return check_launch("gemm_nn");
 }
-// the A segments of a GEMM are batch-major (B clips x T steps x N nodes): the DMA kernels read them through a row map
-struct BtMap { int T = 0, B = 0, N = 0; };
 template <int NCTW, int KC, int MINB = 2>
-int run_nn_dma(const SegPtrs& segs, int nseg, int F, int R, const float* Bp, int nct_total, const float* bias,
-               float* C, int ldc, int O, hipStream_t st, const char* tag, BtMap bt) {
-    constexpr int NB = 2 * NCTW;
-    const size_t lds = 2 * (size_t)(128 * KC + (KC / 4) * NB * 64) * sizeof(float);
-    EEG_SET_MAX_LDS((gemm_nn_dma_kernel<NCTW, KC, MINB>), lds);
-    dim3 grid(ceil_div(R, 128), ceil_div(nct_total, NB));
-    EEG_LAUNCH_P(tag, (gemm_nn_dma_kernel<NCTW, KC, MINB>), grid, dim3(256), lds, st, segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, bt.T, bt.B, bt.N);
+int run_nn_dma(const NnPlan& p, const NnCall& c, const SegPtrs& segs, const NnRhs& B, const float* bias, float* C, hipStream_t st, const char* tag, BtMap bt) {
+    EEG_SET_MAX_LDS((gemm_nn_dma_kernel<NCTW, KC, MINB>), p.lds);
+    EEG_LAUNCH_P(tag, (gemm_nn_dma_kernel<NCTW, KC, MINB>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, segs, c.nseg, c.F, c.R, B.Bp, c.nct_total, bias, C, c.ldc, c.O, bt.T, bt.B, bt.N);
     return check_launch("gemm_nn_dma");
 }
-bool nn_dma_ok(int F, int R, int ldc) { return g_tune[0] == 0 && ldc % 4 == 0 && (double)R * F < 4.0e9 && (F % 16 == 0 || F % 20 == 0); }
 template <int NCTW>
-int run_nn_kc(const SegPtrs& segs, int nseg, int F, int R, const float* Bp, int nct_total, const float* bias,
-              float* C, int ldc, int O, hipStream_t st, const char* tag, BtMap bt) {
-    if (nn_dma_ok(F, R, ldc)) {                                      // LDS-DMA staging (default)
-        if (F % 16 == 0) return run_nn_dma<NCTW, 16>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
-        if (F % 20 == 0) return run_nn_dma<NCTW, 20>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
+int run_nn_chunk(const NnPlan& p, const NnCall& c, const SegPtrs& segs, const NnRhs& B, const float* bias, float* C, hipStream_t st, const char* tag, BtMap bt) {
+    if (p.kind == NnKind::Dma) {
+        if (p.kc == 16) return run_nn_dma<NCTW, 16>(p, c, segs, B, bias, C, st, tag, bt);
+        return run_nn_dma<NCTW, 20>(p, c, segs, B, bias, C, st, tag, bt);
     }
-    if (bt.T > 0) return fail("gemm_nn: a batch-major segment needs the LDS-DMA kernel (F=%d)", F);
-    if (F % 32 == 0) return run_nn<NCTW, 32>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag);
-    if (F % 20 == 0) return run_nn<NCTW, 20>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag);
-    if (F % 16 == 0) return run_nn<NCTW, 16>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag);
-    return run_nn<NCTW, 4>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag);
+    if (p.kc == 32) return run_nn<NCTW, 32>(p, c, segs, B, bias, C, st, tag);
+    if (p.kc == 20) return run_nn<NCTW, 20>(p, c, segs, B, bias, C, st, tag);
+    if (p.kc == 16) return run_nn<NCTW, 16>(p, c, segs, B, bias, C, st, tag);
+    return run_nn<NCTW, 4>(p, c, segs, B, bias, C, st, tag);
 }
-// C[R x O] = [segments] @ packed B (nct_total col tiles) + bias
-// Bq: the same right-hand side in the quad order of gemm_nnr_kernel (kernels_pack.h: bxq / bxtq), or NULL.  The round-3
-// kernel takes the launch when it covers the shape and every one of its 2-per-CU workgroups gets at least two 128-row
-// tiles (dev knob 2 bit 0 = 1: never)
-int gemm_nn(const SegPtrs& segs, int nseg, int F, int R, const float* Bp, int nct_total, const float* bias,
-            float* C, int ldc, int O, hipStream_t st, const char* tag = "gemm_nn", BtMap bt = BtMap(), const float* Bq = nullptr) {
-    if (Bq != nullptr && (g_tune[2] & 1) == 0 && g_tune[0] == 0 && R >= q_min_rows() && nnq_supported(nseg, F, R, nct_total, ldc, O)) {
-        if (launch_nnq(segs, nseg, F, R, Bq, nct_total, bias, C, ldc, O, bt.T, bt.B, bt.N, num_cus(), st, tag)) return fail("gemm_nnq: launch failed");
-        return check_launch("gemm_nnq");
-    }
-    // few row blocks (per-step decoder GEMMs): narrower column blocks fill more CUs
-    if (nct_total <= 4 || ceil_div(R, 128) * ceil_div(nct_total, 12) < 160)
-        return run_nn_kc<2>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
-    // column block of 12, 10 or 8 tiles, whichever leaves the fewest padding tiles (20 tiles = dX at M = 5: 2 x 10
-    // instead of 2 x 12 with a sixth of the MFMAs on padding)
-    const int pad6 = round_up(nct_total, 12) - nct_total, pad5 = round_up(nct_total, 10) - nct_total, pad4 = round_up(nct_total, 8) - nct_total;
-    if (pad5 < pad6 && pad5 <= pad4 && F % 16 == 0 && nn_dma_ok(F, R, ldc))
-        return run_nn_dma<5, 16>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
-    if (pad4 < pad6 && nn_dma_ok(F, R, ldc)) return run_nn_kc<4>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
-    return run_nn_kc<6>(segs, nseg, F, R, Bp, nct_total, bias, C, ldc, O, st, tag, bt);
-}
-
-// opt-in three-term bf16 split of an NN GEMM (kernels_gemm_bf.h).  Returns -1 when the shape has no instantiation (the caller
-// then takes the fp32 kernel), 0 ok, 1 error.
 template <int NTB>
-int run_nn_bf3(const SegPtrs& segs, int nseg, int F, int R, const unsigned short* Wp, int nct_total, const float* bias, float* C,
-               int ldc, int O, hipStream_t st, const char* tag, BtMap bt) {
-    const size_t lds = 2 * 3 * (size_t)NTB * 1024;
-    EEG_SET_MAX_LDS((gemm_nn_bf3_kernel<NTB>), lds);
-    EEG_LAUNCH_P(tag, (gemm_nn_bf3_kernel<NTB>), dim3(ceil_div(R, 128), nct_total / NTB), dim3(256), lds, st, segs, nseg, F, R, Wp, nct_total,
-                 bias, C, ldc, O, bt.T, bt.B, bt.N);
+int run_nn_bf3(const NnPlan& p, const NnCall& c, const SegPtrs& segs, const NnRhs& B, const float* bias, float* C, hipStream_t st, const char* tag, BtMap bt) {
+    EEG_SET_MAX_LDS((gemm_nn_bf3_kernel<NTB>), p.lds);
+    EEG_LAUNCH_P(tag, (gemm_nn_bf3_kernel<NTB>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, segs, c.nseg, c.F, c.R, B.W3, c.bf3_nct, bias, C, c.ldc, c.O, bt.T, bt.B, bt.N);
     return check_launch("gemm_nn_bf3");
 }
-int gemm_nn_bf3(const SegPtrs& segs, int nseg, int F, int R, const unsigned short* Wp, int nct_total, const float* bias, float* C,
-                int ldc, int O, hipStream_t st, const char* tag, BtMap bt) {
-    if (F % 4 != 0 || ldc % 4 != 0 || O % 4 != 0 || (double)R * F >= 4.0e9) return -1;
-    if (nct_total % 12 == 0) return run_nn_bf3<12>(segs, nseg, F, R, Wp, nct_total, bias, C, ldc, O, st, tag, bt);
-    if (nct_total % 10 == 0) return run_nn_bf3<10>(segs, nseg, F, R, Wp, nct_total, bias, C, ldc, O, st, tag, bt);
-    if (nct_total % 8 == 0) return run_nn_bf3<8>(segs, nseg, F, R, Wp, nct_total, bias, C, ldc, O, st, tag, bt);
-    return -1;
+// C[R x O] = [segments] @ B (nct_total col tiles) + bias
+int gemm_nn(const NnPlan& p, const NnCall& c, const SegPtrs& segs, const NnRhs& B, const float* bias, float* C, hipStream_t st,
+            const char* tag = "gemm_nn", BtMap bt = BtMap()) {
+    if (p.error == kGemmNeedsRowMap) return fail("gemm_nn: a batch-major segment needs the LDS-DMA kernel (F=%d)", c.F);
+    if (p.kind == NnKind::Quad) {
+        if (launch_nnq(p, segs, c.nseg, c.F, c.R, B.Bq, c.nct_total, bias, C, c.ldc, c.O, bt.T, bt.B, bt.N, st, tag)) return fail("gemm_nnq: launch failed");
+        return check_launch("gemm_nnq");
+    }
+    if (p.kind != NnKind::Bf3) {
+        if (p.nctw == 2) return run_nn_chunk<2>(p, c, segs, B, bias, C, st, tag, bt);
+        if (p.nctw == 5) return run_nn_dma<5, 16>(p, c, segs, B, bias, C, st, tag, bt);   // (planned for the DMA kernel with 16-deep chunks only)
+        if (p.nctw == 4) return run_nn_chunk<4>(p, c, segs, B, bias, C, st, tag, bt);
+        return run_nn_chunk<6>(p, c, segs, B, bias, C, st, tag, bt);
+    }
+    if (p.nctw == 12) return run_nn_bf3<12>(p, c, segs, B, bias, C, st, tag, bt);
+    if (p.nctw == 10) return run_nn_bf3<10>(p, c, segs, B, bias, C, st, tag, bt);
+    return run_nn_bf3<8>(p, c, segs, B, bias, C, st, tag, bt);
+}
+// the same for a caller that holds the fp32 pack only and time-major rows
+int gemm_nn(const SegPtrs& segs, int nseg, int F, int R, const float* Bp, int nct_total, const float* bias, float* C, int ldc, int O, hipStream_t st) {
+    const NnCall c = nn_call(nseg, F, R, nct_total, ldc, O);
+    return gemm_nn(gemm_nn_plan(c), c, segs, NnRhs{Bp}, bias, C, st);
 }
 
+struct TnArgs { const float* dY; int ldy, ycol0; float* partial; };
 template <int NCTW>
-int run_tn(const SegPtrs& segs, int nseg, int F, int R, const float* dY, int ldy, int ycol0, int O,
-           float* partial, int nsplit, int rows_per_split, hipStream_t st, const char* tag) {
-    constexpr int OT = 2 * NCTW * 16;
-    constexpr int YS = OT + ((16 - (OT % 32)) + 32) % 32;
-    const size_t lds = 2 * (size_t)(32 * 80 + 32 * YS) * sizeof(float);
-    EEG_SET_MAX_LDS((gemm_tn_kernel<NCTW>), lds);
-    dim3 grid(nseg * ceil_div(F, 64), nsplit);
-    // same XCD-aware placement as the DMA kernel (run_tn_dma); in this register-staged kernel it measured slower in round 1
-    // (1.19 vs 1.04 ms per step), so here it stays a dev knob (4 = 2)
-    const int remap = (g_tune[4] == 2 && nsplit % 8 == 0 && grid.x > 1) ? 1 : 0;
-    EEG_LAUNCH_P(tag, (gemm_tn_kernel<NCTW>), grid, dim3(256), lds, st, segs, nseg, F, R, dY, ldy, ycol0, O, partial, rows_per_split, remap);
+int run_tn(const TnPlan& p, const TnCall& c, const SegPtrs& segs, const TnArgs& a, hipStream_t st, const char* tag) {
+    EEG_SET_MAX_LDS((gemm_tn_kernel<NCTW>), p.lds);
+    EEG_LAUNCH_P(tag, (gemm_tn_kernel<NCTW>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, segs, c.nseg, c.F, c.R, a.dY, a.ldy, a.ycol0, c.O, a.partial, p.rps, p.remap);
     return check_launch("gemm_tn");
 }
-// k-block width of the DMA TN kernel.  128-wide blocks halve the re-reads of dY (PMC: 862 -> ~600 MB per
-// launch) but measured SLOWER (gemm_tn 1.08-1.15 vs 0.92 ms/step, cfg2): the re-reads are served by the
-// Infinity Cache, and the wider tile costs occupancy.
-constexpr int kTnKbw = 64;
 template <int KTW, int NCTW, int RC, int WK = 2>
-int run_tn_dma(const SegPtrs& segs, int nseg, int F, int R, const float* dY, int ldy, int ycol0, int O,
-               float* partial, int nsplit, int rows_per_split, hipStream_t st, const char* tag, BtMap bt) {
-    constexpr int OT = 2 * NCTW * 16, KBW = 16 * KTW * WK;
-    const size_t lds = 2 * (size_t)(RC * KBW + RC * OT) * sizeof(float);
-    EEG_SET_MAX_LDS((gemm_tn_dma_kernel<KTW, NCTW, RC, WK>), lds);
-    dim3 grid(ceil_div(nseg * F, KBW), nsplit);
-    // all k-blocks of a row split on ONE XCD (they read the same dY rows): PMC traffic of the class 831 -> 432 MB per launch
-    // (1.93x -> 1.00x algorithmic) at unchanged time (dev knob 4 = 1 switches the placement off)
-    const int remap = (g_tune[4] == 0 && nsplit % 8 == 0 && grid.x > 1) ? 1 : 0;
-    EEG_LAUNCH_P(tag, (gemm_tn_dma_kernel<KTW, NCTW, RC, WK>), grid, dim3(128 * WK), lds, st, segs, nseg, F, R, dY, ldy, ycol0, O, partial, rows_per_split, bt.T, bt.B, bt.N, remap);
+int run_tn_dma(const TnPlan& p, const TnCall& c, const SegPtrs& segs, const TnArgs& a, hipStream_t st, const char* tag, BtMap bt) {
+    EEG_SET_MAX_LDS((gemm_tn_dma_kernel<KTW, NCTW, RC, WK>), p.lds);
+    EEG_LAUNCH_P(tag, (gemm_tn_dma_kernel<KTW, NCTW, RC, WK>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, segs, c.nseg, c.F, c.R, a.dY, a.ldy, a.ycol0, c.O, a.partial, p.rps, bt.T, bt.B, bt.N, p.remap);
     return check_launch("gemm_tn_dma");
 }
-
-// dev knob 14: 8-wave / 128-column k-blocks for dY tiles of this width and up (0 = never); knob 15: their workgroup target
-int tn_wide_from() { return g_tune[14]; }
-bool tn_dma_ok(int F, int O) { return g_tune[1] == 0 && O > 32 && O % 4 == 0 && F % 4 == 0; }
-int tn_split(int nseg, int F, int R, int O, int* rows_per_split) {
-    const bool dma = tn_dma_ok(F, O);
-    const bool wide = dma && tn_wide_from() > 0 && O >= tn_wide_from();
-    const int blocks = dma ? ceil_div(nseg * F, wide ? 2 * kTnKbw : kTnKbw) : nseg * ceil_div(F, 64);
-    // ~3 workgroups per CU (wide: 2) per 400 k rows: measured, R = 291 840 rows (cfg2/3/4): 768 workgroups best (1152: +12 %,
-    // 1536: +1..10 %); R = 583 680 (cfg5): 1536 best (768: +4 %, and +20 % on the h-gate shape with the XCD placement)
-    const int target = (wide ? 512 : 768) * ceil_div(R, 400000);
-    int nsplit = ceil_div(g_tune[15] > 0 ? g_tune[15] : target, blocks);
-    int rps = round_up(ceil_div(R, nsplit), 32);
-    if (rps < 128) rps = 128;
-    nsplit = ceil_div(R, rps);
-    if (nsplit >= 8) nsplit = round_up(nsplit, 8);   // multiple of 8: XCD-aware k-block placement (trailing splits may be empty)
-    *rows_per_split = rps;
-    return nsplit;
-}
 // partial[nsplit][nseg*F][O] = per-split A^T dY[:, ycol0:ycol0+O]
-int gemm_tn(const SegPtrs& segs, int nseg, int F, int R, const float* dY, int ldy, int ycol0, int O,
-            float* partial, int nsplit, int rows_per_split, hipStream_t st, const char* tag = "gemm_tn", BtMap bt = BtMap(),
-            const TnqPlan* q = nullptr) {
-    if (q != nullptr && q->ok) {                         // round-3 kernel (nsplit / rows_per_split are the plan's)
-        if (launch_tnq(*q, segs, nseg, F, R, dY, ldy, ycol0, O, partial, bt.T, bt.B, bt.N, st, tag)) return fail("gemm_tnq: launch failed");
+int gemm_tn(const TnPlan& p, const TnCall& c, const SegPtrs& segs, const float* dY, int ldy, int ycol0, float* partial, hipStream_t st,
+            const char* tag = "gemm_tn", BtMap bt = BtMap()) {
+    if (p.error == kGemmNeedsRowMap) return fail("gemm_tn: a batch-major segment needs the LDS-DMA kernel (O=%d)", c.O);
+    if (p.error == kGemmBadO) return fail("gemm_tn: O=%d unsupported", c.O);
+    const TnArgs a{dY, ldy, ycol0, partial};
+    if (p.kind == TnKind::Quad) {
+        if (launch_tnq(p, segs, c.nseg, c.F, c.R, dY, ldy, ycol0, c.O, partial, bt.T, bt.B, bt.N, st, tag)) return fail("gemm_tnq: launch failed");
         return check_launch("gemm_tnq");
     }
-    if (tn_dma_ok(F, O) && rows_per_split % 32 == 0 && R >= 1) {   // LDS-DMA staging (default)
-#define EEG_TN(NCTW, RC) run_tn_dma<2, NCTW, RC>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag, bt)
-        // row-chunk depth: the 192-column tile stages 16 rows at a time (32 KB of LDS per workgroup -> 4 workgroups
-        // per CU instead of 2 with 32-row stages: -3.5 % on that shape); the narrower tiles are better off with 32
-        // rows (measured both ways); 8-row stages are 15 % slower
-#define EEG_TNW(NCTW, RC) run_tn_dma<2, NCTW, RC, 4>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag, bt)
-        const bool wide = tn_wide_from() > 0 && O >= tn_wide_from();
-        if (O > 128 && O <= 192) return wide ? EEG_TNW(6, 16) : EEG_TN(6, 16);
-        if (O > 64 && O <= 128) return wide ? EEG_TNW(4, 32) : EEG_TN(4, 32);
-        return wide ? EEG_TNW(2, 32) : EEG_TN(2, 32);
-#undef EEG_TNW
-#undef EEG_TN
+    if (p.kind != TnKind::Staged) {
+        const bool wide = p.kind == TnKind::DmaWide;
+        if (p.nctw == 6) return wide ? run_tn_dma<2, 6, 16, 4>(p, c, segs, a, st, tag, bt) : run_tn_dma<2, 6, 16>(p, c, segs, a, st, tag, bt);
+        if (p.nctw == 4) return wide ? run_tn_dma<2, 4, 32, 4>(p, c, segs, a, st, tag, bt) : run_tn_dma<2, 4, 32>(p, c, segs, a, st, tag, bt);
+        return wide ? run_tn_dma<2, 2, 32, 4>(p, c, segs, a, st, tag, bt) : run_tn_dma<2, 2, 32>(p, c, segs, a, st, tag, bt);
     }
-    if (bt.T > 0) return fail("gemm_tn: a batch-major segment needs the LDS-DMA kernel (O=%d)", O);
-    if (O <= 32) return run_tn<1>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag);
-    if (O <= 64) return run_tn<2>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag);
-    if (O <= 128) return run_tn<4>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag);
-    if (O <= 192) return run_tn<6>(segs, nseg, F, R, dY, ldy, ycol0, O, partial, nsplit, rows_per_split, st, tag);
-    return fail("gemm_tn: O=%d unsupported", O);
+    if (p.nctw == 1) return run_tn<1>(p, c, segs, a, st, tag);
+    if (p.nctw == 2) return run_tn<2>(p, c, segs, a, st, tag);
+    if (p.nctw == 4) return run_tn<4>(p, c, segs, a, st, tag);
+    return run_tn<6>(p, c, segs, a, st, tag);
 }
 
 // the streaming kernel applies (and with it the batch-major input option of eeg_dcrnn_layer_fwd)
@@ -276,7 +222,7 @@ int diffuse_fwd(const float* X, const float* P, int p_batched, int S, int B, int
         // profiles/r02_b_diffuse_sweep.txt) 64 us against 75 us with 6 single-pass workgroups per CU and 68 / 85 us with 2 / 1
         // (fewer, longer sequential streams suit the DRAM pages better than more parallelism); prefetching the next
         // sample's rows ahead of the stores was slower (71 us).  dev knob 5 overrides the target.
-        const int want = ceil_div(g_tune[5] > 0 ? g_tune[5] : 1024, sB);
+        const int want = ceil_div(g_tune[EEG_TUNE_DIFFUSE_FWD_WGS] > 0 ? g_tune[EEG_TUNE_DIFFUSE_FWD_WGS] : 1024, sB);
         if (ny > want) ny = want;
         if (ny < 1) ny = 1;
         EEG_LAUNCH_P("diffuse_fwd", diffuse_fwd_stream_kernel<19>, dim3(sB, ny), dim3(threads), 0, st, X, P, p_batched, S, B, F, M, planes, plane_stride, x_bt, xcopy);
@@ -308,19 +254,19 @@ int diffuse_fwd(const float* X, const float* P, int p_batched, int S, int B, int
 }
 int diffuse_adj(const float* Z, const float* P, int p_batched, int S, int B, int N, int F, int M, float* dX,
                 hipStream_t st, const float* add = nullptr) {
-    if (N == 19 && F / 4 <= 128 && g_tune[9] == 0 && (double)S * N * M * F < 1.7e10 && S / (p_batched ? B : 1) >= 4) {   // the EEG montage: streaming kernel (no LDS); 32-bit float4 offsets
+    if (N == 19 && F / 4 <= 128 && g_tune[EEG_TUNE_DIFFUSE_ADJ_LDS] == 0 && (double)S * N * M * F < 1.7e10 && S / (p_batched ? B : 1) >= 4) {   // the EEG montage: streaming kernel (no LDS); 32-bit float4 offsets
         const int F4 = F / 4, sB = p_batched ? B : 1, T = S / sB;
         int threads = 256;
         while (threads > 64 && (threads / 2) / F4 >= T && (threads / 2) >= F4) threads /= 2;
         const int SPW = threads / F4;
         int ny = ceil_div(T, SPW);
-        const int want = ceil_div(g_tune[6] > 0 ? g_tune[6] : 4096, sB);   // dev knob 6 (512 .. 4096 measured alike)
+        const int want = ceil_div(g_tune[EEG_TUNE_DIFFUSE_ADJ_WGS] > 0 ? g_tune[EEG_TUNE_DIFFUSE_ADJ_WGS] : 4096, sB);   // dev knob 6 (512 .. 4096 measured alike)
         if (ny > want) ny = want;
         if (ny < 1) ny = 1;
         // round 5: Z walked in storage order (all hop slots of a node row together) where the hop count has an instantiation
-        if (g_tune[18] == 0 && M == 3) {
+        if (g_tune[EEG_TUNE_DIFFUSE_ADJ_PLANES] == 0 && M == 3) {
             EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 3>), dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, add, dX);
-        } else if (g_tune[18] == 0 && M == 5) {
+        } else if (g_tune[EEG_TUNE_DIFFUSE_ADJ_PLANES] == 0 && M == 5) {
             EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 5>), dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, add, dX);
         } else {
             EEG_LAUNCH_P("diffuse_adj", diffuse_adj_stream_kernel<19>, dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, M, add, dX);
@@ -382,19 +328,15 @@ int seq_bwd(int H, int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st)
 
 struct BwdWs {
     size_t dxw, dbias, hplanes, rhplanes, partial, part_g, part_c, z, total;   // partial = x-part region; part_g / part_c follow it
-    int nsplit_x, rps_x, nsplit_hg, rps_hg, nsplit_hc, rps_hc;
-    TnqPlan qx, qg, qc;        // round-3 TN kernel where it covers the shape (ok = 1): its split plan replaces tn_split's
+    TnCall cx, chg, chc;       // the three weight-gradient TNs of the cell (x-part, h-part of the gate, of the candidate) ...
+    TnPlan tx, thg, thc;       // ... and their plans: kernel, row split (-> the partial regions), grid
+    bool pair;                 // the two h-part problems as one launch (tn_pair_applies)
     // spectral form (d->spectral): dyh = U^T dXW (N, Sp, 3H); hplanes / rhplanes = U^T h_{t-1}, U^T (r*h_{t-1}) (N, Sp, H); partial /
     // part_g / part_c = the grouped TNs' [N*spg][K][O]; z = dXh (N, Sp, Fin)
     size_t dyh;
     TngPlan gx, gh;
     TnfPlan gf;                // the three problems in one pass (kernels_gemm_f.h); ok: gx.spg = gh.spg = gf.spg
 };
-// dev knob 2 bit 1 = 2: the round-2 TN kernels everywhere
-TnqPlan tn_plan_q(int nseg, int F, int R, int O, bool bt) {
-    if ((g_tune[2] & 2) != 0 || g_tune[1] != 0 || R < q_min_rows()) return TnqPlan{};
-    return tnq_plan(nseg, F, R, O, bt, g_tune[16] > 0 ? g_tune[16] / 2 : num_cus());    // dev knob 16: target workgroups of the whole-block TN GEMM
-}
 BwdWs bwd_ws(const eeg_layer_dims* d, int need_dx) {
     BwdWs w;
     const size_t R = (size_t)d->T * d->B * d->N;
@@ -409,20 +351,18 @@ BwdWs bwd_ws(const eeg_layer_dims* d, int need_dx) {
     w.gx = spec ? tng_plan(d->Fin, spec_rows(d->T * d->B), d->N, num_cus()) : TngPlan{};
     w.gh = spec ? tng_plan(d->H, spec_rows(d->T * d->B), d->N, num_cus()) : TngPlan{};
     // dev knob 23 = 1: the three separate grouped launches
-    w.gf = spec && g_tune[23] == 0 ? tnf_plan(d->Fin, d->H, spec_rows(d->T * d->B), d->N, num_cus()) : TnfPlan{};
+    w.gf = spec && g_tune[EEG_TUNE_SPEC_TN_SEPARATE] == 0 ? tnf_plan(d->Fin, d->H, spec_rows(d->T * d->B), d->N, num_cus()) : TnfPlan{};
     if (w.gf.ok) { w.gx.spg = w.gh.spg = w.gf.spg; w.gx.rps = w.gh.rps = w.gf.rps; }
-    w.nsplit_x = tn_split(d->M, d->Fin, (int)R, 3 * d->H, &w.rps_x);
-    w.nsplit_hg = tn_split(d->M, d->H, (int)R, 2 * d->H, &w.rps_hg);
-    w.nsplit_hc = tn_split(d->M, d->H, (int)R, d->H, &w.rps_hc);
-    w.qx = tn_plan_q(d->M, d->Fin, (int)R, 3 * d->H, d->x_batch_major != 0);
-    w.qg = tn_plan_q(d->M, d->H, (int)R, 2 * d->H, false);
-    w.qc = tn_plan_q(d->M, d->H, (int)R, d->H, false);
-    if (w.qx.ok) { w.nsplit_x = w.qx.nsplit; w.rps_x = w.qx.rps; }
-    if (w.qg.ok) { w.nsplit_hg = w.qg.nsplit; w.rps_hg = w.qg.rps; }
-    if (w.qc.ok) { w.nsplit_hc = w.qc.nsplit; w.rps_hc = w.qc.rps; }
-    size_t px = (size_t)w.nsplit_x * d->M * d->Fin * 3 * d->H;
-    size_t pg = (size_t)w.nsplit_hg * d->M * d->H * 2 * d->H;
-    size_t pc = (size_t)w.nsplit_hc * d->M * d->H * d->H;
+    w.cx = tn_call(d->M, d->Fin, (int)R, 3 * d->H, d->x_batch_major != 0, true);
+    w.chg = tn_call(d->M, d->H, (int)R, 2 * d->H, false, true);
+    w.chc = tn_call(d->M, d->H, (int)R, d->H, false, true);
+    w.tx = gemm_tn_plan(w.cx);
+    w.thg = gemm_tn_plan(w.chg);
+    w.thc = gemm_tn_plan(w.chc);
+    w.pair = tn_pair_applies(w.thg, w.thc, w.chg.knobs);
+    size_t px = (size_t)w.tx.nsplit * d->M * d->Fin * 3 * d->H;
+    size_t pg = (size_t)w.thg.nsplit * d->M * d->H * 2 * d->H;
+    size_t pc = (size_t)w.thc.nsplit * d->M * d->H * d->H;
     if (spec) {
         px = (size_t)d->N * w.gx.spg * d->Fin * 3 * d->H;
         pg = (size_t)d->N * w.gh.spg * d->H * 2 * d->H;
@@ -453,7 +393,7 @@ int cell_weight_grads(const eeg_layer_dims* d, const float* X, const float* plan
     for (int m = 0; m < kMaxM; ++m) sx.p[m] = m == 0 ? X : (m < M ? planes + (size_t)(m - 1) * x_stride : nullptr);
     float* part_g = part + (w.part_g - w.partial);
     float* part_c = part + (w.part_c - w.partial);
-    if (gemm_tn(sx, M, Fin, R, dXW, 3 * H, 0, 3 * H, part, w.nsplit_x, w.rps_x, st, "gemm_tn_x", bt, &w.qx)) return 1;
+    if (gemm_tn(w.tx, w.cx, sx, dXW, 3 * H, 0, part, st, "gemm_tn_x", bt)) return 1;
     //   h-part of the gate: hops(h_{t-1})^T [dR|dU]
     const float* hpl = hpl_in;
     size_t hs = h_stride;
@@ -474,22 +414,20 @@ int cell_weight_grads(const eeg_layer_dims* d, const float* X, const float* plan
     }
     SegPtrs sr;
     for (int m = 0; m < kMaxM; ++m) sr.p[m] = m == 0 ? RHs : (m < M ? rpl + (size_t)(m - 1) * rs : nullptr);
-    // Round 5: where the whole-block TN kernel covers both h-part problems with the same plan (same K, row splits and dY rows; only
-    // the column count differs: 2H vs H) they go out as ONE launch whose workgroups alternate between the two -- the 64-column
-    // problem waits for its operands (0.61 of the MFMA peak alone), the 128-column one for the matrix pipe (0.77): side by side on
-    // the two workgroup slots of a CU they take 0.366 instead of 0.390 ms per cfg2 step (role `gemm_tn_h`; dev knob 19 = 1: one by one)
-    int pair = -1;
-    if (g_tune[19] == 0) {
-        pair = launch_tnq_pair(w.qg, w.qc, sh, sr, M, H, R, dXW, 3 * H, 0, 2 * H, part_g, 2 * H, H, part_c, st, "gemm_tn_h");
-        if (pair > 0) return fail("gemm_tnq_pair: launch failed");
-    }
-    if (pair < 0) {
-        if (gemm_tn(sh, M, H, R, dXW, 3 * H, 0, 2 * H, part_g, w.nsplit_hg, w.rps_hg, st, "gemm_tn_hg", BtMap(), &w.qg)) return 1;
-        if (gemm_tn(sr, M, H, R, dXW, 3 * H, 2 * H, H, part_c, w.nsplit_hc, w.rps_hc, st, "gemm_tn_hc", BtMap(), &w.qc)) return 1;
+    // Round 5: where the pair applies (gemm_launch.h) the two h-part problems go out as ONE launch whose workgroups alternate
+    // between the two -- the 64-column problem waits for its operands (0.61 of the MFMA peak alone), the 128-column one for the
+    // matrix pipe (0.77): side by side on the two workgroup slots of a CU they take 0.366 instead of 0.390 ms per cfg2 step (role
+    // `gemm_tn_h`)
+    if (w.pair) {
+        if (launch_tnq_pair(w.thg.q, w.thc.q, sh, sr, M, H, R, dXW, 3 * H, 0, 2 * H, part_g, 2 * H, H, part_c, st, "gemm_tn_h"))
+            return fail("gemm_tnq_pair: launch failed");
+    } else {
+        if (gemm_tn(w.thg, w.chg, sh, dXW, 3 * H, 0, part_g, st, "gemm_tn_hg")) return 1;
+        if (gemm_tn(w.thc, w.chc, sr, dXW, 3 * H, 2 * H, part_c, st, "gemm_tn_hc")) return 1;
     }
     //   one fixed-order reduction of the three sets of split-K partials into the reference's gradient layout
     ReduceJobs jobs;
-    const int Ks[3] = {M * Fin, M * H, M * H}, Os[3] = {3 * H, 2 * H, H}, ns[3] = {w.nsplit_x, w.nsplit_hg, w.nsplit_hc};
+    const int Ks[3] = {M * Fin, M * H, M * H}, Os[3] = {3 * H, 2 * H, H}, ns[3] = {w.tx.nsplit, w.thg.nsplit, w.thc.nsplit};
     const float* parts[3] = {part, part_g, part_c};
     int nblocks = 0;
     for (int j = 0; j < 3; ++j) {
@@ -560,7 +498,8 @@ struct DecLayout {
     size_t planes[8], hext[8], rs[8], us[8], cs[8], rhs[8], hpl[8], rpl[8];
     // backward workspace
     size_t dxw[8], dbias[8], dotot, da, dhn, z, partial, projt_pack, colsum, bwd_total;
-    int nsplit_p, rps_p;
+    TnCall cp;                 // the projection's weight gradient
+    TnPlan tp;
     BwdWs lw[8];
     eeg_layer_dims ld[8];
 };
@@ -606,8 +545,9 @@ DecLayout dec_layout(const eeg_decoder_dims* d) {
     y.da = o;     o += align64(state);
     y.dhn = o;    o += align64(2 * (size_t)d->L * state);
     y.z = o;      o += align64((size_t)d->B * d->N * d->M * (d->Dout > d->H ? d->Dout : d->H));
-    y.nsplit_p = tn_split(1, d->Dout, (int)R, d->H, &y.rps_p);
-    const size_t pp = (size_t)y.nsplit_p * d->Dout * d->H;
+    y.cp = tn_call(1, d->Dout, (int)R, d->H);
+    y.tp = gemm_tn_plan(y.cp);
+    const size_t pp = (size_t)y.tp.nsplit * d->Dout * d->H;
     part = pp > part ? pp : part;
     y.partial = o; o += align64(part);
     y.projt_pack = o; o += align64((size_t)(d->Dout / 4) * nct_h * 64);
@@ -641,7 +581,7 @@ int eeg_dcrnn_abi_version(void) { return 5; }
 int eeg_dcrnn_is_device_build(void) { return kPlatformIsDevice; }
 #if defined(EEG_DEV)
 int eeg_dcrnn_set_tuning(int key, int value) {
-    if (key < 0 || key >= 24) return fail("set_tuning: key %d out of range", key);
+    if (key < 0 || key >= EEG_TUNE_COUNT) return fail("set_tuning: key %d out of range", key);
     g_tune[key] = value;
     return 0;
 }
@@ -812,9 +752,12 @@ int eeg_dcrnn_spectral_ok(const eeg_layer_dims* d, int need_dx) {
 int eeg_dcrnn_batch_major_ok(const eeg_layer_dims* d) {
     if (!diffuse_streams(d->p_batched, d->T * d->B, d->B, d->N, d->Fin)) return 0;
     // 2: the GEMMs read the batch-major input through a row map (d->x_batch_major = 1, no copy); 1: only with the
-    // time-major copy Xtm
+    // time-major copy Xtm.  The rule is "the LDS-DMA kernel applies to both x-part GEMMs", NOT "both x-part plans succeed with a
+    // row map": the quad kernels read a row map too, also where the DMA kernels do not apply, and Python keeps other tensors for
+    // the backward by this answer.
     const int R = d->T * d->B * d->N;
-    return (nn_dma_ok(d->Fin, R, 3 * d->H) && tn_dma_ok(d->Fin, 3 * d->H)) ? 2 : 1;
+    const GemmKnobs k = gemm_knobs();
+    return (nn_dma_applies(d->Fin, R, 3 * d->H, k) && tn_dma_applies(d->Fin, 3 * d->H, k)) ? 2 : 1;
 }
 
 int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, const float* h0, const float* P,
@@ -842,7 +785,6 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
         bt.T = d->T; bt.B = d->B; bt.N = d->N;
     }
     float* XW = ws;
-    int rc3 = -1;
     if (d->spectral != nullptr) {
         // spectral form (shared symmetric support; spec_common.h): Xh = U^T X (node-major, time-major rows; kept in `planes` for the
         // backward, or handed over by the layer below: x_planes_ready), Yh_i = Xh_i Wt_i + csum_i * bias (grouped GEMM, K = Fin), and
@@ -857,7 +799,7 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
         float* Yh = ws + (size_t)R * 3 * H;
         if (!d->x_planes_ready && launch_spec_mix(1, X, d->spectral, nullptr, N, d->T, d->B, Fin, d->x_batch_major ? 1 : 0, planes, st, "spec_mix_x"))
             return fail("spec_mix: launch failed");
-        int nnf = g_tune[20] == 0 ? launch_nnf(planes, xgs, Fin, Sp, N, d->spack + sp.sxr, sp.sxr_stride, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
+        int nnf = g_tune[EEG_TUNE_SPEC_NN_GROUPED] == 0 ? launch_nnf(planes, xgs, Fin, Sp, N, d->spack + sp.sxr, sp.sxr_stride, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
                                                d->spectral + spec_csum_offset(N)) : -1;
         if (nnf > 0) return fail("gemm_nnf: launch failed");
         if (nnf < 0 && launch_nng(planes, Fin, Sp, N, d->spack + sp.sxq, sp.sxq_stride, sp.nct_x, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
@@ -892,12 +834,10 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
     // 2. hoisted x-part GEMM: XW = [X | planes] @ Bx + [bg|bc]
     SegPtrs segs;
     for (int m = 0; m < kMaxM; ++m) segs.p[m] = m == 0 ? X : (m < M ? planes + (size_t)(m - 1) * xs : nullptr);
-    if (rc3 < 0 && d->pack3 != nullptr && pack3_supported(Fin, H, M)) {          // opt-in: three-term bf16 split (include/eeg_dcrnn.h, eeg_layer_dims.pack3)
-        const Pack3 q = make_pack3(Fin, H, M);
-        rc3 = gemm_nn_bf3(segs, M, Fin, R, d->pack3 + q.xw, q.xw_nct, pack + p.bias, XW, 3 * H, 3 * H, st, "gemm_nn_xw", bt);
-        if (rc3 > 0) return 1;
-    }
-    if (rc3 < 0 && gemm_nn(segs, M, Fin, R, pack + p.bx, 3 * H / 16, pack + p.bias, XW, 3 * H, 3 * H, st, "gemm_nn_xw", bt, p.has_bxq ? pack + p.bxq : nullptr)) return 1;
+    const bool bf3 = d->pack3 != nullptr && pack3_supported(Fin, H, M);   // opt-in: three-term bf16 split (include/eeg_dcrnn.h, eeg_layer_dims.pack3)
+    const Pack3 q = make_pack3(Fin, H, M);
+    const NnCall cxw = nn_call(M, Fin, R, 3 * H / 16, 3 * H, 3 * H, bt, p.has_bxq, bf3 ? q.xw_nct : 0);
+    if (gemm_nn(gemm_nn_plan(cxw), cxw, segs, NnRhs{pack + p.bx, pack + p.bxq, bf3 ? d->pack3 + q.xw : nullptr}, pack + p.bias, XW, st, "gemm_nn_xw", bt)) return 1;
     // 3. the recurrence
     if ((Hplanes != nullptr) != (RHplanes != nullptr)) return fail("layer_fwd: Hplanes/RHplanes must be both NULL or both non-NULL");
     SeqFwdArgs a{XW, h0 != nullptr ? Hext : nullptr, P, d->p_batched, pack + p.bhg, pack + p.bhc, Hext + state, Rs, Us, Cs, RHs, Hplanes, RHplanes,
@@ -961,7 +901,7 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
         if (cell_weight_grads_spectral(d, planes, xs_spec(d), hh, hh_gs, rhh, dYh, ws + w.partial, w, dWg, dWc, st, dbias, dbg, dbc)) return 1;
         if (dX != nullptr) {
             // one kernel (GEMM over K = 3H + the node mix back) where it applies; dev knob 17 = 1: the grouped GEMM and the mix as passes
-            const int dxf = g_tune[17] == 0 ? launch_dxf(dYh, Sp, S, N, Fin, d->spack + sp.sxtq, sp.sxtq_stride, d->spectral, dX, st, "gemm_dx_f") : -1;
+            const int dxf = g_tune[EEG_TUNE_SPEC_DX_PASSES] == 0 ? launch_dxf(dYh, Sp, S, N, Fin, d->spack + sp.sxtq, sp.sxtq_stride, d->spectral, dX, st, "gemm_dx_f") : -1;
             if (dxf > 0) return fail("gemm_dxf: launch failed");
             if (dxf < 0) {
                 float* dXh = ws + w.z;
@@ -978,13 +918,10 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
         float* Z = ws + w.z;
         SegPtrs sd;
         for (int m = 0; m < kMaxM; ++m) sd.p[m] = m == 0 ? dXW : nullptr;
-        int rc3 = -1;
-        if (d->pack3 != nullptr && pack3_supported(Fin, H, M)) {      // opt-in: three-term bf16 split
-            const Pack3 q = make_pack3(Fin, H, M);
-            rc3 = gemm_nn_bf3(sd, 1, 3 * H, R, d->pack3 + q.dx, q.dx_nct, nullptr, Z, M * Fin, M * Fin, st, "gemm_nn_dx", BtMap());
-            if (rc3 > 0) return 1;
-        }
-        if (rc3 < 0 && gemm_nn(sd, 1, 3 * H, R, pack + p.bxt, round_up(M * Fin, 16) / 16, nullptr, Z, M * Fin, M * Fin, st, "gemm_nn_dx", BtMap(), p.has_bxtq ? pack + p.bxtq : nullptr)) return 1;
+        const bool bf3 = d->pack3 != nullptr && pack3_supported(Fin, H, M);      // opt-in: three-term bf16 split
+        const Pack3 q = make_pack3(Fin, H, M);
+        const NnCall cdx = nn_call(1, 3 * H, R, round_up(M * Fin, 16) / 16, M * Fin, M * Fin, BtMap(), p.has_bxtq, bf3 ? q.dx_nct : 0);
+        if (gemm_nn(gemm_nn_plan(cdx), cdx, sd, NnRhs{pack + p.bxt, pack + p.bxtq, bf3 ? d->pack3 + q.dx : nullptr}, nullptr, Z, st, "gemm_nn_dx")) return 1;
         if (diffuse_adj(Z, P, d->p_batched, S, d->B, N, Fin, M, dX, st)) return 1;
     }
     return 0;
@@ -1065,7 +1002,7 @@ int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, in
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
 static int corr_nsplit(int B, int T) {
-    int ns = ceil_div(g_tune[7] > 0 ? g_tune[7] : 1024, B);         // dev knob 7: target number of workgroups
+    int ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);         // dev knob 7: target number of workgroups
     const int cap = ceil_div(T, 4);
     if (ns > cap) ns = cap;
     return ns < 1 ? 1 : ns;
@@ -1167,7 +1104,7 @@ int eeg_dcrnn_decoder_fwd(const eeg_decoder_dims* d, const float* targets, const
     //      apply (hidden size, montage > 20 nodes, LDS) the per-step launches below run
     {
         const size_t lds = dec_fwd_lds_floats(M, L, Dout) * sizeof(float);
-        if (g_tune[11] == 0 && dec_persistent_ok(d)) {
+        if (g_tune[EEG_TUNE_DEC_FWD_PER_STEP] == 0 && dec_persistent_ok(d)) {
             DecFwdArgs a;
             for (int l = 0; l < L; ++l) {
                 const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
@@ -1263,7 +1200,7 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
         const int q4 = Dout / 4;
         const int dt = q4 % 5 == 0 ? 5 : (q4 % 4 == 0 ? 4 : 0);
         const size_t lds = dec_bwd_lds_floats(M, L, Dout) * sizeof(float);
-        if (g_tune[10] == 0 && dec_persistent_ok(d)) {
+        if (g_tune[EEG_TUNE_DEC_BWD_PER_STEP] == 0 && dec_persistent_ok(d)) {
             DecBwdArgs a;
             for (int l = 0; l < L; ++l) {
                 const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
@@ -1346,8 +1283,8 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
     // projection: dW_p (Dout x H) = sum_rows dOtot^T h_top ;  db_p = column sums of dOtot
     SegPtrs so;
     for (int m = 0; m < kMaxM; ++m) so.p[m] = m == 0 ? dOtot : nullptr;
-    if (gemm_tn(so, 1, Dout, (int)Rall, saved + y.hd, H, 0, H, ws + y.partial, y.nsplit_p, y.rps_p, st)) return 1;   // (hd = h_top without dropout)
-    EEG_LAUNCH_P("reduce_unpack", reduce_unpack_kernel, dim3(ceil_div(Dout * H, 64)), dim3(256), 256 * sizeof(float4), st, ws + y.partial, y.nsplit_p, Dout, H, 3, Dout, H, 1, dWp, dWp);
+    if (gemm_tn(y.tp, y.cp, so, saved + y.hd, H, 0, ws + y.partial, st)) return 1;   // (hd = h_top without dropout)
+    EEG_LAUNCH_P("reduce_unpack", reduce_unpack_kernel, dim3(ceil_div(Dout * H, 64)), dim3(256), 256 * sizeof(float4), st, ws + y.partial, y.tp.nsplit, Dout, H, 3, Dout, H, 1, dWp, dWp);
     if (check_launch("reduce_unpack(proj)")) return 1;
     return colsum(dOtot, (int)Rall, Dout, Dout, ws + y.colsum, dbp, nullptr, st);
 }
@@ -1458,8 +1395,7 @@ int eeg_dcrnn_dconv_fwd(const float* X, const float* P, int p_batched, int B, in
 size_t eeg_dcrnn_dconv_bwd_ws_floats(int B, int N, int F, int M, int O) {
     if (B < 1 || N < 1 || F < 1 || M < 1 || O < 1) return 0;
     const int R = B * N;
-    int rps;
-    const int nsplit = tn_split(M, F, R, O, &rps);
+    const int nsplit = gemm_tn_plan(tn_call(M, F, R, O)).nsplit;
     return (size_t)(M - 1) * R * F + align64((size_t)nsplit * M * F * O) + align64((size_t)(O / 4) * (round_up(M * F, 16) / 16) * 64)
            + (size_t)R * M * F + align64(colsum_ws(R, O));
 }
@@ -1470,8 +1406,9 @@ int eeg_dcrnn_dconv_bwd(const float* X, const float* P, int p_batched, int B, in
     if (O % 16 != 0 || O > 192) return fail("dconv_bwd: output_dim=%d must be a multiple of 16 (<= 192)", O);
     hipStream_t st = S_(stream);
     const int R = B * N;
-    int rps;
-    const int nsplit = tn_split(M, F, R, O, &rps);
+    const TnCall cw = tn_call(M, F, R, O);
+    const TnPlan tw = gemm_tn_plan(cw);
+    const int nsplit = tw.nsplit;
     float* planes = ws;
     float* part = planes + (size_t)(M - 1) * R * F;
     float* tpack = part + align64((size_t)nsplit * M * F * O);
@@ -1482,7 +1419,7 @@ int eeg_dcrnn_dconv_bwd(const float* X, const float* P, int p_batched, int B, in
         if (diffuse_fwd(X, P, p_batched, B, B, N, F, M, planes, st)) return 1;
         SegPtrs sx;
         for (int m = 0; m < kMaxM; ++m) sx.p[m] = m == 0 ? X : (m < M ? planes + (size_t)(m - 1) * R * F : nullptr);
-        if (gemm_tn(sx, M, F, R, dOut, O, 0, O, part, nsplit, rps, st)) return 1;
+        if (gemm_tn(tw, cw, sx, dOut, O, 0, part, st)) return 1;
         EEG_LAUNCH_P("reduce_unpack", reduce_unpack_kernel, dim3(ceil_div(M * F * O, 64)), dim3(256), 256 * sizeof(float4), st, part, nsplit, M * F, O, 4, F, 0, M, dW, dW);
         if (check_launch("reduce_unpack(dconv)")) return 1;
     }

@@ -17,31 +17,37 @@ extern "C" {
  * wave spent per phase (slots 0-7 forward, 8-15 backward); NULL disables.  Only the H=64, M=3
  * instantiations carry the probe. */
 int eeg_dcrnn_set_seq_probe(int64_t* probe);
-/* Integer knobs selecting kernel variants for A/B timing.  key 0 = 1: register-staged NN GEMM;
- * key 1 = 1: register-staged TN GEMM; key 4 = 1: NO XCD-aware placement of the TN k-blocks in the LDS-DMA kernel (2: placement in the register-staged one);
- * key 9 = 1: LDS/MFMA adjoint diffusion; key 12 = 1: single-wave-per-SIMD forward recurrent kernel also
- * where the two-wave one exists (64 units, M <= 3); key 13 = 1: the same for the BPTT kernel; key 11 = 1: per-step
- * launches in the decoder forward instead of the persistent kernel, key 10 = 1: the same for the decoder backward;
- * key 8: unused (round 1-3: k-steps per weight group of the layer-0 input part in the persistent decoder forward); key 3: the
- * streamed-weight BPTT kernel with two workgroups per CU (1 = wherever it exists, 2 = never; default: batches beyond
- * 1.5 clips per CU at M >= 4); keys 14 / 15: 8-wave TN GEMM from this dY width up / its workgroup target;
- * key 18 = 1: the round-4
- * adjoint diffusion (hop planes consumed one at a time) instead of the row-streaming one;
- * key 19 = 1: the two h-part weight-gradient GEMMs of a cell as two launches instead of the paired one;
- * key 17 = 1: the input gradient of a spectral layer as grouped GEMM + node-mix pass instead of gemm_dxf_kernel;
- * key 20 = 1: the round-5 grouped NN GEMM for the spectral x-part instead of gemm_nnf_kernel (kernels_gemm_f.h);
- * key 21 = 1 / 22 = 1: the general-path BPTT / forward recurrent kernels under the spectral form; key 23 = 1: the three grouped
- * weight-gradient launches instead of the fused one (kernels_gemm_f.h);
- * keys 5 / 6 / 7: target workgroup counts of the streaming diffusion (forward / adjoint) and the correlation-Gram launches.
- * Defaults (all 0) = the product configuration. */
+/* Integer knobs selecting kernel variants for A/B timing; the keys are named below.  Defaults (all 0) = the product configuration. */
 int eeg_dcrnn_set_tuning(int key, int value);
-/* the keys that select among the recurrent kernels (the inputs of the launch plans, csrc/seq_launch.h) */
 enum {
-    EEG_TUNE_SEQ_STREAM = 3,
-    EEG_TUNE_SEQ_FWD_ONE_WAVE = 12,
-    EEG_TUNE_SEQ_BWD_ONE_WAVE = 13,
-    EEG_TUNE_SEQ_BWD_NO_SPEC = 21,
-    EEG_TUNE_SEQ_FWD_NO_SPEC = 22
+    /* the hoisted GEMMs (the inputs of the launch plans, csrc/gemm_launch.h) */
+    EEG_TUNE_NN_STAGED = 0,          /* 1: register-staged NN GEMM */
+    EEG_TUNE_TN_STAGED = 1,          /* 1: register-staged TN GEMM */
+    EEG_TUNE_QUAD = 2,               /* bit 0: no persistent quad NN GEMM; bit 1: no quad TN GEMM; bits 2..: rows per CU from which they run */
+    EEG_TUNE_TN_XCD = 4,             /* 1: NO XCD-aware placement of the TN k-blocks in the LDS-DMA kernel; 2: placement in the register-staged one */
+    EEG_TUNE_TN_WIDE_FROM = 14,      /* 8-wave TN GEMM from this dY width up */
+    EEG_TUNE_TN_TARGET = 15,         /* workgroup target of the split TN GEMMs */
+    EEG_TUNE_TNQ_TARGET = 16,        /* workgroup target of the quad TN GEMM */
+    EEG_TUNE_TN_NO_PAIR = 19,        /* 1: the two h-part weight-gradient GEMMs of a cell as two launches instead of the paired one */
+    /* the recurrent kernels (the inputs of the launch plans, csrc/seq_launch.h) */
+    EEG_TUNE_SEQ_STREAM = 3,         /* streamed-weight BPTT kernel, two workgroups per CU: 1 = wherever it exists, 2 = never */
+    EEG_TUNE_SEQ_FWD_ONE_WAVE = 12,  /* 1: single-wave-per-SIMD forward kernel also where the two-wave one exists */
+    EEG_TUNE_SEQ_BWD_ONE_WAVE = 13,  /* 1: the same for the BPTT kernel */
+    EEG_TUNE_SEQ_BWD_NO_SPEC = 21,   /* 1: the general-path BPTT kernel under the spectral form */
+    EEG_TUNE_SEQ_FWD_NO_SPEC = 22,   /* 1: the general-path forward kernel under the spectral form */
+    /* diffusion, decoder, spectral form */
+    EEG_TUNE_DIFFUSE_FWD_WGS = 5,    /* target workgroup count of the streaming diffusion, forward */
+    EEG_TUNE_DIFFUSE_ADJ_WGS = 6,    /* the same, adjoint */
+    EEG_TUNE_GRAM_WGS = 7,           /* the same, correlation-Gram launches */
+    /* 8: unused (rounds 1-3: k-steps per weight group of the layer-0 input part in the persistent decoder forward) */
+    EEG_TUNE_DIFFUSE_ADJ_LDS = 9,    /* 1: LDS/MFMA adjoint diffusion */
+    EEG_TUNE_DEC_BWD_PER_STEP = 10,  /* 1: per-step launches in the decoder backward instead of the persistent kernel */
+    EEG_TUNE_DEC_FWD_PER_STEP = 11,  /* 1: the same for the decoder forward */
+    EEG_TUNE_SPEC_DX_PASSES = 17,    /* 1: input gradient of a spectral layer as grouped GEMM + node-mix pass instead of gemm_dxf_kernel */
+    EEG_TUNE_DIFFUSE_ADJ_PLANES = 18, /* 1: the round-4 adjoint diffusion (hop planes one at a time) instead of the row-streaming one */
+    EEG_TUNE_SPEC_NN_GROUPED = 20,   /* 1: the round-5 grouped NN GEMM for the spectral x-part instead of gemm_nnf_kernel */
+    EEG_TUNE_SPEC_TN_SEPARATE = 23,  /* 1: the three grouped weight-gradient launches instead of the fused one */
+    EEG_TUNE_COUNT = 24
 };
 
 #ifdef __cplusplus
