@@ -83,6 +83,11 @@ _SIGNATURES = {
     "eeg_dcrnn_teacher_flags": (c_int, [_FP, _FP, c_int64, ctypes.c_double, c_int, _FP, c_void_p]),
     "eeg_dcrnn_fft_features_pair": (c_int, [_FP, _FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, c_float, c_float, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_augment_features": (c_int, [_FP, _FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_window_features": (c_int, [_FP, c_int, c_int, c_int, c_int, _FP, _FP, c_float, c_float, _FP, c_void_p]),
+    "eeg_dcrnn_window_features_pair": (c_int, [_FP, _FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, c_float, c_float, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_augment_windows": (c_int, [_FP, _FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_corr_graph_rows_ws_floats": (c_size_t, [c_int, c_int, c_int]),
+    "eeg_dcrnn_corr_graph_rows": (c_int, [_FP, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_augment_draw": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, _FP, c_void_p]),
     "eeg_dcrnn_pack_cells": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32),
                              c_int, c_int, POINTER(c_void_p), _FP, c_int, POINTER(c_void_p), c_void_p]),

@@ -1000,6 +1000,54 @@ int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, in
     return check_launch("augment_features");
 }
 
+/* ---- time-domain inputs: windows of the raw signals, multiplicative augmentation -------------------- */
+// one launch of window_stream_kernel over x (and y when Ty > 0); `what` names the entry point in refusals
+static int window_stream(const char* what, bool raw, const float* x, const float* y, int B, int Tx, int Ty, int N, int W, const int32_t* perm,
+                         const float* a, const float* c, float mean, float std_, float* x_out, float* y_out, void* stream) {
+    if (B < 1 || N < 1 || Tx < 1 || Ty < 0) return fail("%s: empty input (B=%d, N=%d, Tx=%d, Ty=%d)", what, B, N, Tx, Ty);
+    if (W < 4 || W % 4 != 0) return fail("%s: window=%d unsupported (positive multiple of 4)", what, W);
+    if (x_out == x || (Ty > 0 && y_out == y)) return fail("%s: in-place call (rows move between nodes: outputs must not alias inputs)", what);
+    if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)x_out | (uintptr_t)y_out) & 15) != 0) return fail("%s: tensors must be 16-byte aligned", what);
+    const long long pieces = (long long)(Tx + Ty) * N * (W / 4);            // 16-byte pieces per clip
+    const long long chunks = (pieces + kAugPerBlock - 1) / kAugPerBlock;
+    if (chunks > 65535) return fail("%s: %lld values per clip exceed one launch (limit %lld)", what, 4 * pieces, 4LL * 65535 * kAugPerBlock);
+    const dim3 grid((unsigned)B, (unsigned)chunks);
+    const int* pm = reinterpret_cast<const int*>(perm);
+#define EEG_WSTREAM(RAW, D4C) \
+    EEG_LAUNCH_P(what, (window_stream_kernel<RAW, D4C>), grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, W / 4, pm, a, c, mean, std_, x_out, y_out)
+    if (raw) { if (W == 200) EEG_WSTREAM(true, 50); else EEG_WSTREAM(true, 0); }
+    else { if (W == 200) EEG_WSTREAM(false, 50); else EEG_WSTREAM(false, 0); }
+#undef EEG_WSTREAM
+    return check_launch(what);
+}
+
+int eeg_dcrnn_window_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* scale, float mean, float std_,
+                              float* x_std, void* stream) {
+    if (raw == nullptr) return fail("window_features: null input");
+    if (x_std == nullptr) return fail("window_features: null output");
+    if (!(std_ != 0.f)) return fail("window_features: std must be non-zero");
+    return window_stream("window_features", true, raw, nullptr, B, T, 0, N, W, perm, scale, nullptr, mean, std_, x_std, nullptr, stream);
+}
+
+int eeg_dcrnn_window_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
+                                   const float* scale, float mean, float std_, float* x_std, float* y_std, void* stream) {
+    if (raw_x == nullptr || raw_y == nullptr)
+        return fail("window_features_pair: null input (raw_x=%p, raw_y=%p)", (const void*)raw_x, (const void*)raw_y);
+    if (x_std == nullptr || y_std == nullptr)
+        return fail("window_features_pair: null output (x_std=%p, y_std=%p): the pair is the standardised input and target", (void*)x_std, (void*)y_std);
+    if (Ty < 1) return fail("window_features_pair: empty input (B=%d, N=%d, Tx=%d, Ty=%d)", B, N, Tx, Ty);
+    if (!(std_ != 0.f)) return fail("window_features_pair: std must be non-zero");
+    return window_stream("window_features_pair", true, raw_x, raw_y, B, Tx, Ty, N, W, perm, scale, nullptr, mean, std_, x_std, y_std, stream);
+}
+
+int eeg_dcrnn_augment_windows(const float* x, const float* y, int B, int Tx, int Ty, int N, int D, const int32_t* perm, const float* a,
+                              const float* c, float* x_out, float* y_out, void* stream) {
+    if (x == nullptr || perm == nullptr || a == nullptr || c == nullptr) return fail("augment_windows: null input / perm / factors");
+    if ((y == nullptr) != (Ty == 0)) return fail("augment_windows: target and Ty=%d disagree (no target: y = NULL and Ty = 0)", Ty);
+    if (x_out == nullptr || (y != nullptr && y_out == nullptr)) return fail("augment_windows: null output (x_out=%p, y_out=%p)", (void*)x_out, (void*)y_out);
+    return window_stream("augment_windows", false, x, y, B, Tx, Ty, N, D, perm, a, c, 0.f, 1.f, x_out, y_out, stream);
+}
+
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
 static int corr_nsplit(int B, int T) {
     int ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);         // dev knob 7: target number of workgroups
@@ -1048,6 +1096,48 @@ int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, 
         default: return fail("corr_graph: feature dim=%d unsupported (<= 128)", D);
     }
     if (check_launch("corr_gram")) return 1;
+    EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
+    return check_launch("corr_finish");
+}
+
+// chunks of a clip's channel rows (P pieces of Q floats), and the workgroups per clip that share them
+static int corr_rows_nsplit(int B, int P, int Q) {
+    const long long chunks = (long long)P * ceil_div(Q, kRowChunk);
+    long long ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);   // dev knob 7, as corr_nsplit
+    const long long cap = (chunks + 3) / 4;
+    if (ns > cap) ns = cap;
+    return ns < 1 ? 1 : (int)(ns > 65535 ? 65535 : ns);
+}
+size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q) {
+    return (B >= 1 && P >= 1 && Q >= 1) ? (size_t)B * corr_rows_nsplit(B, P, Q) * kGramFloats : 0;
+}
+int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1, float* S2,
+                              float* ws, void* stream) {
+    if (X == nullptr || ws == nullptr) return fail("corr_graph_rows: null input / workspace");
+    if (S1 == nullptr || S2 == nullptr) return fail("corr_graph_rows: null output (S1=%p, S2=%p)", (void*)S1, (void*)S2);
+    if (N < 1 || N > kMaxNodes) return fail("corr_graph_rows: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
+    if (B < 1 || P < 1) return fail("corr_graph_rows: empty batch/clip (B=%d, pieces=%d)", B, P);
+    if (Q < 4 || Q % 4 != 0) return fail("corr_graph_rows: row piece of %d floats unsupported (positive multiple of 4)", Q);
+    if (top_k < 0 || top_k >= N) return fail("corr_graph_rows: top_k=%d unsupported (0..%d)", top_k, N - 1);
+    if (((uintptr_t)X & 15) != 0) return fail("corr_graph_rows: clips must be 16-byte aligned");
+    // pieces of a row lie piece_stride floats apart and hold all N nodes: one piece (raw rows) or >= N*Q apart (window tensors)
+    if (P > 1 && (piece_stride < (long long)N * Q || piece_stride % 4 != 0))
+        return fail("corr_graph_rows: piece stride %lld unsupported (multiple of 4, >= N*Q = %d)", piece_stride, N * Q);
+    const long long clip_floats = (P > 1 ? (long long)(P - 1) * piece_stride : 0) + (long long)N * Q;
+    if (clip_floats * 4 >= (1LL << 31)) return fail("corr_graph_rows: a clip of %lld bytes exceeds the 2 GB one descriptor covers", clip_floats * 4);
+    hipStream_t st = S_(stream);
+    const int ns = corr_rows_nsplit(B, P, Q);
+    const int tile_floats = N * kRowChunk > kGramFloats ? N * kRowChunk : kGramFloats;
+    const size_t lds = 4 * (size_t)tile_floats * sizeof(float);            // <= 128 KB (N = 32)
+    const unsigned ps = P > 1 ? (unsigned)piece_stride : 0u;
+    if (N <= 20) {
+        EEG_SET_MAX_LDS((corr_gram_rows_kernel<true>), lds);
+        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats);
+    } else {
+        EEG_SET_MAX_LDS((corr_gram_rows_kernel<false>), lds);
+        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<false>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats);
+    }
+    if (check_launch("corr_gram_rows")) return 1;
     EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
     return check_launch("corr_finish");
 }

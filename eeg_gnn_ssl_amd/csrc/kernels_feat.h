@@ -314,6 +314,61 @@ __global__ __launch_bounds__(kAugThreads) void augment_features_kernel(const flo
     }
 }
 
+// ---- time-domain inputs (the reference without --use_fft) -----------------------------------------------------------------------
+// computeSliceMatrix(is_fft=False) (dataloader_detection.py:25-85) cuts the clip's channel rows into 1-s windows and nothing else:
+// clip[t, n, :] = raw[n, t*W : (t+1)*W]; `_random_reflect` permutes the channels (:233-245), `_random_scale` MULTIPLIES the signals
+// (`EEG_seq *= scale_factor`, :247-256), then the scaler (utils.py:393-428); the SSL loader does the same to both halves of its pair
+// with one coin and one factor (dataloader_ssl.py:159-182,317-341).  Two routes to the model input, one kernel:
+//   RAW  = true : in = raw signals (B, N, T*W) -> out[b, t, n, :] = (in[b, perm[b][n], t*W ..] * a[b] - mean) / std, the product and
+//                 the difference as ONE fused multiply-add (one rounding, on the GPU and in any other build of this source)
+//                 (a = the clip's scale factor, null = 1): windowing, augmentation and scaler in one read and one write; no
+//                 un-augmented copy is written -- the correlation graph of a time-domain clip is that of the raw rows themselves;
+//   RAW  = false: in = standardised windows (B, T, N, W) -> out[b, t, n, :] = in[b, t, perm[b][n], :] * a[b] + c[b], the product
+//                 rounded before the sum like the framework's two kernels (a = s, c = (s - 1) * mean / std: the same augmentation
+//                 applied behind the scaler).
+// Launch shape of augment_features_kernel above: blockIdx.x = clip, blockIdx.y = a stretch of kAugPerBlock 16-byte pieces of the
+// clip's (Tx + Ty) * N output rows (x rows first, Ty = 0: no second half), kAugUnroll pieces in flight per thread; consecutive
+// lanes hold consecutive pieces, so stores are whole lines and loads whole rows of 4*W bytes.  Every element takes the same
+// instructions whether its half travels alone or in a pair: the paired launch is a re-scheduling, bit for bit.
+template <bool RAW, int D4C>    // D4C: 16-byte pieces per row when known at compile time (50: W = 200), 0 = read D4
+__global__ __launch_bounds__(kAugThreads) void window_stream_kernel(const float* __restrict__ x, const float* __restrict__ y, int N, int Tx,
+                                                                    int Ty, int D4, const int* __restrict__ perm, const float* __restrict__ a,
+                                                                    const float* __restrict__ c, float mean, float std_,
+                                                                    float* __restrict__ x_out, float* __restrict__ y_out) {
+    const int d4 = D4C > 0 ? D4C : D4, b = blockIdx.x;
+    const unsigned rows_x = (unsigned)Tx * N, total = (rows_x + (unsigned)Ty * N) * d4;
+    const float ab = a != nullptr ? a[b] : 1.0f, cb = (!RAW && c != nullptr) ? c[b] : 0.0f;
+    const unsigned e0 = blockIdx.y * (unsigned)kAugPerBlock + threadIdx.x;
+    f32x4 v[kAugUnroll];
+    size_t dst[kAugUnroll];
+    bool in_y[kAugUnroll], on[kAugUnroll];
+#pragma unroll
+    for (int u = 0; u < kAugUnroll; ++u) {
+        const unsigned e = e0 + u * kAugThreads;
+        on[u] = e < total;
+        if (!on[u]) continue;
+        unsigned row = e / d4;
+        const unsigned p = e - row * d4;
+        in_y[u] = row >= rows_x;
+        if (in_y[u]) row -= rows_x;
+        const unsigned t = row / N, nd = row - t * N;
+        const unsigned T = in_y[u] ? Ty : Tx;
+        const int src = perm_source(perm, b, N, (int)nd);
+        const size_t clip = (size_t)b * T * N;
+        dst[u] = ((clip + row) * d4 + p) * 4;
+        const size_t from = RAW ? (((size_t)b * N + src) * T + t) : (clip + (size_t)t * N + src);
+        v[u] = *reinterpret_cast<const f32x4*>((in_y[u] ? y : x) + (from * d4 + p) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < kAugUnroll; ++u) {
+        if (!on[u]) continue;
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = RAW ? __builtin_fmaf(v[u][k], ab, -mean) / std_ : unfused_mul_add(v[u][k], ab, cb);
+        *reinterpret_cast<f32x4*>((in_y[u] ? y_out : x_out) + dst[u]) = o;
+    }
+}
+
 // Data augmentation drawn on the device (dataloader_detection.py:384-389: `_random_reflect` then `_random_scale` per sample, in the
 // DataLoader workers): clip b takes Philox counter used[1] + b of the {seed, offset} pair `used` (eeg_dcrnn_rng_take): word 0 is the
 // fair coin of `np.random.choice([True, False])` (top bit), word 1 the uniform of `np.random.uniform(0.8, 1.2)`.  Outputs, all

@@ -11,6 +11,8 @@
 //    contiguous stream, lane (i, g) reads the 16 bytes X[t][node i][16q+4g .. +3] from LDS and feeds
 //    them as BOTH operands (G = X X^T), one float per MFMA; the K order inside a 16-feature chunk is
 //    permuted, which a sum over all k does not care about.  Algorithmic bytes: 4*T*N*D per clip.
+//  * corr_gram_rows_kernel: the same Gram for wide channel rows (time-domain clips: raw rows of any length, windows of any
+//    width), staged in 256-float chunks per node through a descriptor over the clip; same partial-Gram layout.
 //  * corr_finish_kernel: one workgroup per clip: fixed-order sum of the NS partial Grams,
 //    normalisation, |.|, diag = 1, top-k per row, S1/S2.
 #pragma once
@@ -20,6 +22,69 @@ namespace eeg {
 
 constexpr int kGramTile = 256;                 // one 16x16 MFMA accumulator tile, C layout (r*64 + lane)
 constexpr int kGramFloats = 3 * kGramTile;     // tiles (0,0), (0,1), (1,1) of the padded 32x32 Gram
+
+// The six accumulators of a wave's Gram (REM4: c00b / c01b / c11b are the second chains, the odd k of every pair) and the two steps
+// both Gram kernels share: the MFMAs of one 16-byte fragment pair, and the hand-over of the four waves' sums as ONE partial Gram.
+struct GramAcc {
+    f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = {0.f, 0.f, 0.f, 0.f}, c11 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 c00b = {0.f, 0.f, 0.f, 0.f}, c01b = {0.f, 0.f, 0.f, 0.f}, c11b = {0.f, 0.f, 0.f, 0.f};
+};
+template <bool REM4>
+__device__ __forceinline__ void gram_mma(GramAcc& a, const float4 x0, const float4 x1) {
+    if constexpr (REM4) {       // c01 / c11 registers hold [lane][r] = partial of G[16 + r][node of the lane] (see corr_gram_kernel)
+        // the quad's 16x16x4 MFMAs on two alternating chains (a lone chain issues every 52 cycles, not 32), then its
+        // 4x4x1 MFMAs as one run (a change of shape costs ~11 cycles per 4x4x1, up to ~43 per run; chain_lab.hip)
+        a.c00 = mfma16(x0.x, x0.x, a.c00); a.c00b = mfma16(x0.y, x0.y, a.c00b);
+        a.c00 = mfma16(x0.z, x0.z, a.c00); a.c00b = mfma16(x0.w, x0.w, a.c00b);
+        a.c01 = mfma4(x1.x, x0.x, a.c01); a.c11 = mfma4(x1.x, x1.x, a.c11); a.c01b = mfma4(x1.y, x0.y, a.c01b); a.c11b = mfma4(x1.y, x1.y, a.c11b);
+        a.c01 = mfma4(x1.z, x0.z, a.c01); a.c11 = mfma4(x1.z, x1.z, a.c11); a.c01b = mfma4(x1.w, x0.w, a.c01b); a.c11b = mfma4(x1.w, x1.w, a.c11b);
+    } else {
+        a.c00 = mfma16(x0.x, x0.x, a.c00); a.c01 = mfma16(x0.x, x1.x, a.c01); a.c11 = mfma16(x1.x, x1.x, a.c11);
+        a.c00 = mfma16(x0.y, x0.y, a.c00); a.c01 = mfma16(x0.y, x1.y, a.c01); a.c11 = mfma16(x1.y, x1.y, a.c11);
+        a.c00 = mfma16(x0.z, x0.z, a.c00); a.c01 = mfma16(x0.z, x1.z, a.c01); a.c11 = mfma16(x1.z, x1.z, a.c11);
+        a.c00 = mfma16(x0.w, x0.w, a.c00); a.c01 = mfma16(x0.w, x1.w, a.c01); a.c11 = mfma16(x1.w, x1.w, a.c11);
+    }
+}
+// called by all 256 threads once their loops are done: sm (the staging buffers, free behind the first barrier) takes the four
+// waves' tiles in C layout, `out` their sum in a fixed order
+template <bool REM4>
+__device__ __forceinline__ void gram_write_partial(GramAcc& a, float* sm, int wave, int lane, float* __restrict__ out) {
+    const int i = lane & 15, g = lane >> 4;
+    if constexpr (REM4) { a.c00 += a.c00b; a.c01 += a.c01b; a.c11 += a.c11b; }
+    __syncthreads();                                        // staging buffers are free: reuse for the partial Grams
+    float* mine = sm + wave * kGramFloats;
+    if constexpr (REM4) {
+        // tiles (0,1) and (1,1) in C layout (row = 4*(l>>4) + r, col = l & 15 at [r*64 + l]) from the per-lane-group partials:
+        //   G[n][16 + r]     = sum_g c01[lane (n, g)][r]      -> tile (0,1), row n, col r
+        //   G[16 + r][16 + j] = sum_g c11[lane (j, g)][r]      -> tile (1,1), row r, col j   (lanes with i < 4)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            mine[0 * kGramTile + r * 64 + lane] = a.c00[r];
+            mine[1 * kGramTile + r * 64 + lane] = 0.f;
+            mine[2 * kGramTile + r * 64 + lane] = 0.f;
+        }
+        for (int gg = 0; gg < 4; ++gg) {                    // fixed order: lane group 0, 1, 2, 3
+            EEG_WAVE_SYNC();
+            if (g == gg) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    mine[1 * kGramTile + (i & 3) * 64 + 16 * (i >> 2) + r] += a.c01[r];
+                    if (i < 4) mine[2 * kGramTile + r * 64 + i] += a.c11[r];
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            mine[0 * kGramTile + r * 64 + lane] = a.c00[r];
+            mine[1 * kGramTile + r * 64 + lane] = a.c01[r];
+            mine[2 * kGramTile + r * 64 + lane] = a.c11[r];
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kGramFloats; e += 256)
+        out[e] = (sm[e] + sm[kGramFloats + e]) + (sm[2 * kGramFloats + e] + sm[3 * kGramFloats + e]);
+}
 
 // NQ = number of 16-feature chunks.  Every wave owns the time steps t0, t0 + 4*NS, ... of its clip and a private LDS
 // buffer of one time step (N*D floats rounded up to whole 1-KB wave-DMAs): the step travels global -> LDS as ONE
@@ -39,8 +104,7 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
     EEG_DYN_SMEM(sm);                          // [4 waves][step_floats] staging | reused as [4 waves][kGramFloats] at the end
     const int lane = threadIdx.x & 63, wave = wave_uniform(threadIdx.x >> 6), i = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, sp = blockIdx.y, NS = gridDim.y;
-    f32x4 c00 = {0.f, 0.f, 0.f, 0.f}, c01 = {0.f, 0.f, 0.f, 0.f}, c11 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 c00b = c00, c01b = c00, c11b = c00;          // REM4: second chains (odd k of every pair), added at the end
+    GramAcc acc;
     const int i1 = REM4 ? 16 + (i & 3) : 16 + i;          // second-tile row this lane feeds
     const bool has0 = i < N, has1 = i1 < N;
     float* buf = sm + wave * step_floats;
@@ -77,58 +141,73 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
         EEG_WAVE_SYNC();
         if (t + dt < T) stage(t + dt);                      // next step of this wave: flies during the MFMAs below
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const float4 x0 = a0[q], x1 = a1[q];
-            if constexpr (REM4) {       // c01 / c11 registers hold [lane][r] = partial of G[16 + r][node of the lane] (see above)
-                // the quad's 16x16x4 MFMAs on two alternating chains (a lone chain issues every 52 cycles, not 32), then its
-                // 4x4x1 MFMAs as one run (a change of shape costs ~11 cycles per 4x4x1, up to ~43 per run; chain_lab.hip)
-                c00 = mfma16(x0.x, x0.x, c00); c00b = mfma16(x0.y, x0.y, c00b);
-                c00 = mfma16(x0.z, x0.z, c00); c00b = mfma16(x0.w, x0.w, c00b);
-                c01 = mfma4(x1.x, x0.x, c01); c11 = mfma4(x1.x, x1.x, c11); c01b = mfma4(x1.y, x0.y, c01b); c11b = mfma4(x1.y, x1.y, c11b);
-                c01 = mfma4(x1.z, x0.z, c01); c11 = mfma4(x1.z, x1.z, c11); c01b = mfma4(x1.w, x0.w, c01b); c11b = mfma4(x1.w, x1.w, c11b);
-            } else {
-                c00 = mfma16(x0.x, x0.x, c00); c01 = mfma16(x0.x, x1.x, c01); c11 = mfma16(x1.x, x1.x, c11);
-                c00 = mfma16(x0.y, x0.y, c00); c01 = mfma16(x0.y, x1.y, c01); c11 = mfma16(x1.y, x1.y, c11);
-                c00 = mfma16(x0.z, x0.z, c00); c01 = mfma16(x0.z, x1.z, c01); c11 = mfma16(x1.z, x1.z, c11);
-                c00 = mfma16(x0.w, x0.w, c00); c01 = mfma16(x0.w, x1.w, c01); c11 = mfma16(x1.w, x1.w, c11);
-            }
-        }
+        for (int q = 0; q < NQ; ++q) gram_mma<REM4>(acc, a0[q], a1[q]);
     }
-    if constexpr (REM4) { c00 += c00b; c01 += c01b; c11 += c11b; }
-    __syncthreads();                                        // staging buffers are free: reuse for the partial Grams
-    float* mine = sm + wave * kGramFloats;
-    if constexpr (REM4) {
-        // tiles (0,1) and (1,1) in C layout (row = 4*(l>>4) + r, col = l & 15 at [r*64 + l]) from the per-lane-group partials:
-        //   G[n][16 + r]     = sum_g c01[lane (n, g)][r]      -> tile (0,1), row n, col r
-        //   G[16 + r][16 + j] = sum_g c11[lane (j, g)][r]      -> tile (1,1), row r, col j   (lanes with i < 4)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            mine[0 * kGramTile + r * 64 + lane] = c00[r];
-            mine[1 * kGramTile + r * 64 + lane] = 0.f;
-            mine[2 * kGramTile + r * 64 + lane] = 0.f;
+    gram_write_partial<REM4>(acc, sm, wave, lane, part + ((size_t)b * NS + sp) * kGramFloats);
+}
+
+// The Gram of WIDE channel rows: time-domain clips, whose rows are the raw signals themselves (dataloader_detection.py:258-307 on a
+// clip of computeSliceMatrix(is_fft=False), :25-85: `eeg_clip.reshape((num_sensors, -1))` is the (N, T*200) channel rows again).  A
+// channel row is P pieces of Q floats, piece p of node n at X[b][p * pstride + n * Q ..]: raw rows (B, N, L) are P = 1, Q = L; a
+// window tensor (B, T, N, D) is P = T, Q = D, pstride = N * D.  grid (B, NS): every wave owns the chunks k0, k0 + 4 * NS, ... of its
+// clip, a chunk = kRowChunk = 256 consecutive floats of one piece for every node ([N][256] in a wave-private LDS buffer): per node ONE
+// 1-KB wave-DMA through a descriptor over exactly the clip, so nothing outside the clip is ever addressed; lanes behind the end of a
+// piece (ragged last chunk, Q < 256) ask for an offset outside the descriptor, and whatever their LDS slot then holds is masked
+// to zero where the fragments are read: a zero adds nothing to a Gram.  The LDS rows are 1 KB apart, so the 16 rows a fragment read
+// touches would share their banks: lane l of node n's DMA fetches the 16-byte unit l ^ (n & 15) (the LDS side of a DMA is
+// lane-linear, so the swizzle goes on the SOURCE address), and the read of unit u of node n goes to slot u ^ (n & 15).
+// Same pipeline as corr_gram_kernel: fragments to registers, then the next chunk's DMA flies during the MFMAs; same partial-Gram
+// layout, so corr_finish_kernel serves both.  Fixed chunk -> wave assignment, fixed order: bit-reproducible.
+constexpr int kRowChunk = 256, kRowQuads = kRowChunk / 16;
+template <bool REM4>
+__global__ __launch_bounds__(256) void corr_gram_rows_kernel(const float* __restrict__ X, int N, int P, int Q, unsigned pstride,
+                                                             unsigned clip_floats, float* __restrict__ part, int tile_floats) {
+    EEG_DYN_SMEM(sm);                          // [4 waves][tile_floats] staging | reused as [4 waves][kGramFloats] at the end
+    const int lane = threadIdx.x & 63, wave = wave_uniform(threadIdx.x >> 6), i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x, sp = blockIdx.y, NS = gridDim.y;
+    GramAcc acc;
+    const int i1 = REM4 ? 16 + (i & 3) : 16 + i;          // second-tile row this lane feeds
+    const bool has0 = i < N, has1 = i1 < N;
+    float* buf = sm + wave * tile_floats;
+    const wbuf_t clip = make_wbuf_n(X + (size_t)b * clip_floats, clip_floats * 4u);
+    const int cpp = ceil_div(Q, kRowChunk), nchunks = P * cpp;          // chunks per piece, per clip
+    auto stage = [&](int k) {
+        const int p = k / cpp, q0 = (k - p * cpp) * kRowChunk;
+        const unsigned base = (unsigned)p * pstride;
+        for (int n = 0; n < N; ++n) {
+            const int q = q0 + 4 * (lane ^ (n & 15));
+            // (host: clip bytes < 2^31, so 0x80000000 lies outside every descriptor)
+            wbuf_dma16(clip, buf + n * kRowChunk, q < Q ? (base + (unsigned)(n * Q + q)) * 4u : 0x80000000u, 0u);
         }
-        for (int gg = 0; gg < 4; ++gg) {                    // fixed order: lane group 0, 1, 2, 3
-            EEG_WAVE_SYNC();
-            if (g == gg) {
+    };
+    const int n0 = has0 ? i : 0, n1 = has1 ? i1 : 0;
+    const float* r0 = buf + n0 * kRowChunk;
+    const float* r1 = buf + n1 * kRowChunk;
+    const int k0 = sp * 4 + wave, dk = 4 * NS;
+    if (k0 < nchunks) stage(k0);
+    for (int k = k0; k < nchunks; k += dk) {
+        const int q0 = (k % cpp) * kRowChunk, valid = Q - q0 < kRowChunk ? Q - q0 : kRowChunk;          // wave-uniform
+        float4 a0[kRowQuads], a1[kRowQuads];
+        EEG_WAVE_SYNC();                                    // every lane's pieces of the chunk have been requested
+        EEG_VM_WAIT(0);                                     // ... and have landed (this wave's only vector-memory traffic)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    mine[1 * kGramTile + (i & 3) * 64 + 16 * (i >> 2) + r] += c01[r];
-                    if (i < 4) mine[2 * kGramTile + r * 64 + i] += c11[r];
-                }
-            }
+        for (int q = 0; q < kRowQuads; ++q) {
+            if (16 * q >= valid) continue;                  // whole quads behind the end of the piece: no read, no MFMA
+            const int u = 4 * q + g;                        // 16-byte unit of the chunk
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 v0 = *reinterpret_cast<const float4*>(r0 + 4 * (u ^ (n0 & 15)));
+            const float4 v1 = *reinterpret_cast<const float4*>(r1 + 4 * (u ^ (n1 & 15)));
+            a0[q] = (has0 && 4 * u < valid) ? v0 : z;
+            a1[q] = (has1 && 4 * u < valid) ? v1 : z;
         }
-    } else {
+        EEG_LDS_WAIT();                                     // the reads have RETURNED before the next DMA may overwrite the buffer
+        EEG_WAVE_SYNC();                                    // (see corr_gram_kernel)
+        if (k + dk < nchunks) stage(k + dk);                // next chunk of this wave: flies during the MFMAs below
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            mine[0 * kGramTile + r * 64 + lane] = c00[r];
-            mine[1 * kGramTile + r * 64 + lane] = c01[r];
-            mine[2 * kGramTile + r * 64 + lane] = c11[r];
-        }
+        for (int q = 0; q < kRowQuads; ++q)
+            if (16 * q < valid) gram_mma<REM4>(acc, a0[q], a1[q]);
     }
-    __syncthreads();
-    float* out = part + ((size_t)b * NS + sp) * kGramFloats;
-    for (int e = threadIdx.x; e < kGramFloats; e += 256)
-        out[e] = (sm[e] + sm[kGramFloats + e]) + (sm[2 * kGramFloats + e] + sm[3 * kGramFloats + e]);
+    gram_write_partial<REM4>(acc, sm, wave, lane, part + ((size_t)b * NS + sp) * kGramFloats);
 }
 
 // grid B, block 256.  LDS: G[32][33] | A[32][33] | rowsum[32] | colsum[32]

@@ -11,7 +11,7 @@ dispatcher's "no kernel for the CPU backend" error, and the C-ABI stub refuses n
 Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
-    fft_features, fft_features_pair, augment_features, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
+    fft_features, fft_features_pair, augment_features, window_features, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
@@ -1180,6 +1180,130 @@ _define("augment_features", "(Tensor x, Tensor y, Tensor perm, Tensor log_scale,
         _augment_features_impl, lambda x, y, perm, log_scale, feature_std: (torch.empty_like(x), torch.empty_like(y)))
 
 
+# ---- time-domain inputs (the reference without --use_fft) ----------------------------------------------------------------
+def _check_scale(what, scale, b, ref):
+    if scale is not None:
+        if scale.numel() != b:
+            raise RuntimeError(f"{what}: scale has {scale.numel()} entries for {b} clips")
+        scale = scale.to(device=ref.device, dtype=torch.float32).contiguous()
+    return scale
+
+
+def _raw_windows(what, raw, window, name, like=None):
+    """(B, N, T) of raw signals (B, N, T*window); `like`: the (B, N) the target of a pair must share with its input"""
+    if window < 4 or window % 4 != 0:
+        raise RuntimeError(f"{what}: window={window} unsupported (positive multiple of 4)")
+    if raw.dim() != 3 or raw.shape[2] % window != 0 or raw.shape[2] == 0 or (like is not None and tuple(raw.shape[:2]) != like):
+        want = f"(B, N, T*{window})" if like is None else f"({like[0]}, {like[1]}, Ty*{window}) like the input's clips and nodes"
+        raise RuntimeError(f"raw {name} signals must be {want}, got {tuple(raw.shape)}")
+    return raw.shape[0], raw.shape[1], raw.shape[2] // window
+
+
+def _window_features_impl(raw, window: int, mean: float, std: float, perm, scale):
+    lib = _lib.get_lib()
+    raw = raw.contiguous()
+    _check(lib, raw, "raw signals")
+    b, n, t_len = _raw_windows("window_features", raw, window, "input")
+    if not float(std) != 0.0:
+        raise RuntimeError("window_features: std must be non-zero")
+    perm, _ = _check_draws("window_features", perm, None, b, n, raw)
+    scale = _check_scale("window_features", scale, b, raw)
+    out = _new((b, t_len, n, window), raw)
+    lib.call("eeg_dcrnn_window_features", _p(raw), b, n, t_len, int(window), _p(perm), _p(scale), float(mean), float(std), _p(out), _stream(raw))
+    return out
+
+
+_define("window_features", "(Tensor raw, int window, float mean, float std, Tensor? perm, Tensor? scale) -> Tensor", _window_features_impl,
+        lambda raw, window, mean, std, perm, scale: raw.new_empty((raw.shape[0], raw.shape[2] // window, raw.shape[1], window)))
+
+
+def _window_features_pair_impl(raw_x, raw_y, window: int, mean: float, std: float, perm, scale):
+    lib = _lib.get_lib()
+    raw_x, raw_y = raw_x.contiguous(), raw_y.contiguous()
+    _check(lib, raw_x, "raw input signals")
+    _check(lib, raw_y, "raw target signals")
+    b, n, tx = _raw_windows("window_features_pair", raw_x, window, "input")
+    _, _, ty = _raw_windows("window_features_pair", raw_y, window, "target", like=(b, n))
+    if not float(std) != 0.0:
+        raise RuntimeError("window_features_pair: std must be non-zero")
+    perm, _ = _check_draws("window_features_pair", perm, None, b, n, raw_x)
+    scale = _check_scale("window_features_pair", scale, b, raw_x)
+    x_std, y_std = _new((b, tx, n, window), raw_x), _new((b, ty, n, window), raw_x)
+    lib.call("eeg_dcrnn_window_features_pair", _p(raw_x), _p(raw_y), b, n, tx, ty, int(window), _p(perm), _p(scale), float(mean), float(std),
+             _p(x_std), _p(y_std), _stream(raw_x))
+    return x_std, y_std
+
+
+_define("window_features_pair", "(Tensor raw_x, Tensor raw_y, int window, float mean, float std, Tensor? perm, Tensor? scale) -> (Tensor, Tensor)",
+        _window_features_pair_impl,
+        lambda raw_x, raw_y, window, mean, std, perm, scale: (raw_x.new_empty((raw_x.shape[0], raw_x.shape[2] // window, raw_x.shape[1], window)),
+                                                              raw_x.new_empty((raw_x.shape[0], raw_y.shape[2] // window, raw_x.shape[1], window))))
+
+
+def _augment_windows_impl(x, y, perm, scale, mean: float, std: float):
+    lib = _lib.get_lib()
+    x = x.contiguous()
+    _check(lib, x, "input windows")
+    if x.dim() != 4:
+        raise RuntimeError(f"input windows must be (B, Tx, N, D), got {tuple(x.shape)}")
+    b, tx, n, d = x.shape
+    ty = 0
+    if y is not None:
+        y = y.contiguous()
+        _check(lib, y, "target windows")
+        if y.dim() != 4 or y.shape[0] != b or tuple(y.shape[2:]) != (n, d) or y.shape[1] == 0:
+            raise RuntimeError(f"target windows must be ({b}, Ty, {n}, {d}) like the input's clips, nodes and samples, got {tuple(y.shape)}")
+        ty = int(y.shape[1])
+    if perm is None or scale is None:
+        raise RuntimeError("augment_windows: needs the draws (perm and scale)")
+    if not float(std) != 0.0:
+        raise RuntimeError("augment_windows: std must be non-zero")
+    perm, _ = _check_draws("augment_windows", perm, None, b, n, x)
+    a = _check_scale("augment_windows", scale, b, x)
+    # the two per-clip factors (B floats each) are left to the framework, like `shift` of augment_features: they are then the very
+    # values the expression `x.gather(2, idx) * a[:, None, None, None] + c[:, None, None, None]` uses, on whichever device
+    c = ((a - 1.0) * (float(mean) / float(std))).contiguous()
+    x_out = torch.empty_like(x)
+    y_out = torch.empty_like(y) if y is not None else _new((0,), x)
+    lib.call("eeg_dcrnn_augment_windows", _p(x), _p(y), b, tx, ty, n, d, _p(perm), _p(a), _p(c), _p(x_out), _p(y_out) if y is not None else None,
+             _stream(x))
+    return x_out, y_out
+
+
+_define("augment_windows", "(Tensor x, Tensor? y, Tensor perm, Tensor scale, float mean, float std) -> (Tensor, Tensor)", _augment_windows_impl,
+        lambda x, y, perm, scale, mean, std: (torch.empty_like(x), torch.empty_like(y) if y is not None else x.new_empty((0,))))
+
+
+def _corr_graph_rows_impl(x, top_k: int):
+    """x (B, N, L) raw channel rows, or (B, T, N, D) windows whose channel rows are the T pieces of D samples"""
+    lib = _lib.get_lib()
+    x = x.contiguous()
+    _check(lib, x, "clips")
+    if x.dim() == 3:
+        (b, n, q), p, stride = x.shape, 1, 0
+    elif x.dim() == 4:
+        b, p, n, q = x.shape
+        stride = n * q
+    else:
+        raise RuntimeError(f"clips must be raw rows (B,N,L) or windows (B,T,N,D), got {tuple(x.shape)}")
+    if q < 4 or q % 4 != 0:
+        raise RuntimeError(f"corr_graph_rows: rows of {q} samples unsupported (positive multiple of 4)")
+    if b < 1 or p < 1:
+        raise RuntimeError(f"corr_graph_rows: empty batch/clip {tuple(x.shape)}")
+    adj, s1, s2 = (_new((b, n, n), x) for _ in range(3))
+    ws = _new((lib.query("eeg_dcrnn_corr_graph_rows_ws_floats", b, p, q),), x)
+    lib.call("eeg_dcrnn_corr_graph_rows", _p(x), b, n, p, q, stride, int(top_k), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
+    return adj, s1, s2
+
+
+def _corr_graph_rows_fake(x, top_k):
+    n = x.shape[1] if x.dim() == 3 else x.shape[2]
+    return tuple(x.new_empty((x.shape[0], n, n)) for _ in range(3))
+
+
+_define("corr_graph_rows", "(Tensor x, int top_k) -> (Tensor adj, Tensor s1, Tensor s2)", _corr_graph_rows_impl, _corr_graph_rows_fake)
+
+
 # =============================================================================================
 # losses that seed backward, optimiser tail
 # =============================================================================================
@@ -1435,6 +1559,33 @@ def fft_features_pair(raw_x: torch.Tensor, raw_y: torch.Tensor, window: int = 20
     return torch.ops.eeg_dcrnn.fft_features_pair(raw_x, raw_y, int(window), float(mean), float(std), perm, log_scale)
 
 
+def window_features(raw: torch.Tensor, window: int, mean: float, std: float, perm: Optional[torch.Tensor] = None,
+                    scale: Optional[torch.Tensor] = None):
+    """Time-domain input of the model on the device (the reference without --use_fft): raw (B,N,T*window) resampled signals ->
+    (B,T,N,window) = (raw[b, perm[b][n], t*window ..] * scale[b] - mean) / std: the windowing of `computeSliceMatrix(is_fft=False)`
+    (dataloader_detection.py:25-85), `_random_reflect` / `_random_scale` (`EEG_seq *= scale_factor`, :233-256) and
+    `StandardScaler.transform` (utils.py:393-428) in one pass.  perm (B,N) int32 source channel per node, scale (B) the clip's
+    amplitude factor; None = no reflection / factor 1.  Forward-only."""
+    return torch.ops.eeg_dcrnn.window_features(raw, int(window), float(mean), float(std), perm, scale)
+
+
+def window_features_pair(raw_x: torch.Tensor, raw_y: torch.Tensor, window: int, mean: float, std: float,
+                         perm: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None):
+    """`window_features` of an SSL pair in one launch (dataloader_ssl.py:159-182,317-341: one coin and one factor per sample on
+    input AND target, the scaler on both): raw_x (B,N,Tx*window), raw_y (B,N,Ty*window) -> (x_std (B,Tx,N,window), y_std
+    (B,Ty,N,window)), each bit-identical to `window_features` on that half."""
+    return torch.ops.eeg_dcrnn.window_features_pair(raw_x, raw_y, int(window), float(mean), float(std), perm, scale)
+
+
+def augment_windows(x: torch.Tensor, y: Optional[torch.Tensor], perm: torch.Tensor, scale: torch.Tensor, mean: float, std: float):
+    """The time-domain augmentation on already STANDARDISED windows, one launch for x (B,Tx,N,D) and an optional y (B,Ty,N,D):
+    out[b, t, n] = in[b, t, perm[b][n]] * scale[b] + (scale[b] - 1) * mean / std -- multiplying the signals by s in front of the
+    scaler (mean, std) = this behind it.  D a multiple of 4; perm (B,N) int32, scale (B).  Returns (x_aug, y_aug or None), new
+    tensors.  Forward-only."""
+    xa, ya = torch.ops.eeg_dcrnn.augment_windows(x, y, perm, scale, float(mean), float(std))
+    return xa, (ya if y is not None else None)
+
+
 def augment_features(x: torch.Tensor, y: torch.Tensor, perm: torch.Tensor, log_scale: torch.Tensor, feature_std: float):
     """The reflection / amplitude-jitter augmentation of an SSL pair of already STANDARDISED features, one launch:
     x_aug[b, t, n] = x[b, t, perm[b][n]] + log_scale[b] / feature_std, and the same for y (each with its own number of steps).
@@ -1447,10 +1598,21 @@ def augment_features(x: torch.Tensor, y: torch.Tensor, perm: torch.Tensor, log_s
 def correlation_supports(x: torch.Tensor, top_k: int = 3, return_adj: bool = False):
     """Per-clip correlation graph -> [S1, S2] dual random-walk supports, on the device.
 
-    x (B,T,N,D) clips (the model input).  Replaces the DataLoader-side `_get_indiv_graphs` +
+    x (B,T,N,D) clips (the model input); D <= 128 (features) runs the kernel that stages whole time steps, a wider D (time-domain
+    windows, D = 200) the kernel for wide channel rows.  Replaces the DataLoader-side `_get_indiv_graphs` +
     `keep_topk` + `_compute_supports('dual_random_walk')` (dataloader_detection.py:258-307,335-354).
     Returns [S1 (B,N,N), S2 (B,N,N)] (and the sparsified adjacency (B,N,N) if return_adj)."""
-    adj, s1, s2 = torch.ops.eeg_dcrnn.corr_graph(x, int(top_k))
+    adj, s1, s2 = (torch.ops.eeg_dcrnn.corr_graph_rows if x.dim() == 4 and x.shape[3] > 128 else torch.ops.eeg_dcrnn.corr_graph)(x, int(top_k))
+    return ([s1, s2], adj) if return_adj else [s1, s2]
+
+
+def correlation_supports_raw(raw: torch.Tensor, top_k: int = 3, return_adj: bool = False):
+    """The same graph for a time-domain clip, from its raw signals: raw (B,N,L) channel rows, L a multiple of 4 (the clip of
+    `computeSliceMatrix(is_fft=False)` reshaped by `_get_indiv_graphs` to (N, T*200) is these rows again; dataloader_detection.py:
+    25-85,258-307).  Returns [S1 (B,N,N), S2 (B,N,N)] (and the sparsified adjacency if return_adj)."""
+    if raw.dim() != 3:
+        raise RuntimeError(f"raw signals must be (B, N, L) channel rows, got {tuple(raw.shape)}")
+    adj, s1, s2 = torch.ops.eeg_dcrnn.corr_graph_rows(raw, int(top_k))
     return ([s1, s2], adj) if return_adj else [s1, s2]
 
 

@@ -58,7 +58,7 @@ class TrainStep:
                  scaler_mean: Optional[float] = None, scaler_std: Optional[float] = None,
                  always_reduce: bool = False, raw_window: Optional[int] = None, raw_mean: float = 0.0, raw_std: float = 1.0,
                  shared_graph: bool = True, data_augment: bool = False, swap_perm=None, reflected_supports=None,
-                 feature_std: Optional[float] = None):
+                 feature_std: Optional[float] = None, use_fft: bool = True, feature_mean: Optional[float] = None):
         """shared_graph: batched supports whose clips all carry one and the same graph (the reference's trainers pass the distance
         graph that way) are handed to the model in their 2-D form, which lets the encoder run its hoisted GEMMs in the
         eigenbasis of that graph (`ops.collapse_shared_supports`: one comparison + one flag read per supports TENSOR, cached; a
@@ -82,8 +82,15 @@ class TrainStep:
         raw_window one launch featurises both halves (`ops.fft_features_pair`), on feature inputs one launch augments both
         (`ops.augment_features`); decoder (teacher forcing) and loss see the augmented, standardised target.  Graph side as for the
         supervised tasks (dataloader_ssl.py:349,355): correlation graph of the un-augmented INPUT clip, or the plain / reflected
-        distance graph per coin.  Only the use_fft form of `_random_scale` (additive in the log domain) is built; its time-domain
-        variant (`use_fft` off: the signals are multiplied) is not.
+        distance graph per coin.
+        use_fft=False: the reference's time-domain input mode (no `--use_fft`): a step of the clip is the 200 samples themselves
+        (`computeSliceMatrix(is_fft=False)`, dataloader_detection.py:25-85; the model has input_dim = output_dim = raw_window) and
+        `_random_scale` MULTIPLIES the signals (`EEG_seq *= scale_factor`, :247-256); the factor is exp(log_scale) of the same device
+        draws (`self.last_scale`).  With raw_window, x (and for ssl y) are the raw signals as above and one launch windows, reflects,
+        scales and standardises them (`ops.window_features` / `ops.window_features_pair`); supports=None is the correlation graph
+        of the raw rows of the un-augmented INPUT (`ops.correlation_supports_raw`).  On ready windows (B, T, N, raw-window samples,
+        already standardised) the step applies x[b, :, perm[b]] * s_b + (s_b - 1) * feature_mean / feature_std to x -- and for ssl
+        to y -- in one launch (`ops.augment_windows`), which is the same value; feature_mean and feature_std are required then.
         raw_window: the step takes RAW resampled signals (B, N, T*raw_window) instead of features and runs the reference's
         DataLoader-side chain on the device in front of the model (dataloader_detection.py:57-71,346-354,384-393): log|FFT| of every
         raw_window-sample step (`eeg_dcrnn_fft_features`) -> z-score with (raw_mean, raw_std) = the model input; with
@@ -113,6 +120,9 @@ class TrainStep:
         self.scaler_mean, self.scaler_std = scaler_mean, scaler_std
         self.raw_window, self.raw_mean, self.raw_std = raw_window, float(raw_mean), float(raw_std)
         self.shared_graph = bool(shared_graph)
+        self.use_fft = bool(use_fft)
+        self.feature_mean = None if feature_mean is None else float(feature_mean)
+        self.last_scale = None            # time-domain steps: the clips' amplitude factors of the latest step (tests / logging)
         # detection / classification: head + criterion + head backward as ONE operator behind the encoder (ops.cls_head_loss) instead
         # of model.forward -> loss kernel -> autograd through the head (same values; False: that public path, launch by launch)
         self.fused_head = True
@@ -122,6 +132,9 @@ class TrainStep:
         self.swap_perm, self.reflected_supports, self._augment_rng = None, None, None
         if self.data_augment:
             from . import utils
+            if not use_fft and raw_window is None and (feature_std is None or feature_mean is None):
+                raise ValueError("TrainStep: data_augment on time-domain windows (use_fft=False) needs feature_mean and feature_std (the "
+                                 "StandardScaler's: the reference multiplies the signals BEFORE it standardises)")
             if raw_window is None and feature_std is None:
                 raise ValueError("TrainStep: data_augment on feature inputs needs feature_std (the StandardScaler's std: the reference "
                                  "adds log(scale) BEFORE it standardises)")
@@ -221,7 +234,9 @@ class TrainStep:
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
             supports, perm, log_scale = self._draw_augmentation(x.shape[0], supports)
-        if self.task == "ssl" and (self.raw_window is not None or perm is not None):
+        if not self.use_fft:
+            x, y, supports = self._time_domain_inputs(x, y, supports, perm, log_scale)
+        elif self.task == "ssl" and (self.raw_window is not None or perm is not None):
             # the SSL sample is a pair: the target takes the clip's draws and the scaler like the input (dataloader_ssl.py:317-341)
             x, y, supports = self._ssl_pair(x, y, supports, perm, log_scale)
         elif self.raw_window is not None:            # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
@@ -289,6 +304,35 @@ class TrainStep:
             x, y = ops.augment_features(x, y, perm, log_scale, self.feature_std)
         if supports is None:
             supports = ops.correlation_supports(plain, top_k=3)
+        return x, y, supports
+
+    def _time_domain_inputs(self, x, y, supports, perm, log_scale):
+        """data side of a use_fft=False step (dataloader_detection.py:25-85,233-256,384-393; dataloader_ssl.py:317-355): (model
+        input, target, supports) with this step's draws (or none) -- on BOTH halves of an SSL pair; the correlation graph comes
+        from the un-reflected, un-scaled INPUT clip"""
+        scale = None
+        if log_scale is not None:
+            scale = torch.exp(log_scale)             # B floats, a framework op (capturable): `EEG_seq *= scale_factor`
+            self.last_scale = scale
+        pair = self.task == "ssl"
+        if self.raw_window is not None:
+            raw = x
+            if pair:
+                self._ssl_target_steps(y)
+                if y.shape[:2] != x.shape[:2]:
+                    raise ValueError(f"TrainStep(task='ssl', raw_window={self.raw_window}): the raw target must be (B, num_nodes, Ty*"
+                                     f"{self.raw_window}) with the input's {x.shape[0]} clips and {x.shape[1]} nodes, got {tuple(y.shape)}")
+                x, y = ops.window_features_pair(x, y, self.raw_window, self.raw_mean, self.raw_std, perm=perm, scale=scale)
+            else:
+                x = ops.window_features(x, self.raw_window, self.raw_mean, self.raw_std, perm=perm, scale=scale)
+            if supports is None:
+                supports = ops.correlation_supports_raw(raw, top_k=3)
+        elif perm is not None:
+            plain = x
+            x, ya = ops.augment_windows(x, y if pair else None, perm, scale, self.feature_mean, self.feature_std)
+            y = ya if pair else y
+            if supports is None:
+                supports = ops.correlation_supports(plain, top_k=3)
         return x, y, supports
 
     def _draw_augmentation(self, batch, supports):

@@ -126,6 +126,30 @@ int eeg_dcrnn_fft_features_pair(const float* raw_x, const float* raw_y, int B, i
 int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, int Ty, int N, int D, const int32_t* perm,
                                const float* shift, float* x_out, float* y_out, void* stream);
 
+/* Time-domain inputs (the reference without --use_fft), replacing the DataLoader-side CPU code: dataloader_detection.py:25-85
+ * `computeSliceMatrix(is_fft=False)` (clip[t,n,:] = raw[n, t*W:(t+1)*W]), :233-245 `_random_reflect`, :247-256 `_random_scale`
+ * (`EEG_seq *= scale_factor`), utils.py:393-428 StandardScaler.transform.  raw (B,N,T*W) resampled signals, W % 4 == 0;
+ *   x_std (B,T,N,W) : (raw[b, perm[b][n], t*W ..] * scale[b] - mean) / std in fp32, the model input.
+ * perm (B,N) int32 / scale (B) may be NULL (no reflection / factor 1); a perm entry outside 0..N-1 selects the node itself.
+ * No un-augmented copy is written: the correlation graph of a time-domain clip is that of the raw rows (eeg_dcrnn_corr_graph_rows).
+ * One read and one write of every value (HBM-bound: algorithmic bytes 8*B*N*T*W); tensors 16-byte aligned. */
+int eeg_dcrnn_window_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* scale, float mean,
+                              float std_, float* x_std, void* stream);
+
+/* The same for the SSL pair (dataloader_ssl.py:159-182,317-341: one coin and one scale factor per sample on input AND target, the
+ * scaler on both): raw_x (B,N,Tx*W), raw_y (B,N,Ty*W) -> x_std (B,Tx,N,W), y_std (B,Ty,N,W) in ONE launch; every output is
+ * bit-identical to eeg_dcrnn_window_features on that half. */
+int eeg_dcrnn_window_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
+                                   const float* scale, float mean, float std_, float* x_std, float* y_std, void* stream);
+
+/* The time-domain augmentation on already STANDARDISED windows (dataloader_detection.py:233-256 / dataloader_ssl.py:159-182 in
+ * front of utils.py:393-428: (v*s - mean)/std = ((v - mean)/std)*s + (s - 1)*mean/std):
+ *   x_out[b,t,n,:] = x[b,t,perm[b][n],:] * a[b] + c[b],   a[b] = s_b,   c[b] = (s_b - 1) * mean / std   (product rounded first),
+ * and y_out likewise.  x, x_out (B,Tx,N,D); y, y_out (B,Ty,N,D), or y = y_out = NULL with Ty = 0 (the supervised tasks);
+ * D % 4 == 0, 16-byte aligned, outputs distinct from inputs.  One launch, algorithmic bytes 8*B*(Tx+Ty)*N*D. */
+int eeg_dcrnn_augment_windows(const float* x, const float* y, int B, int Tx, int Ty, int N, int D, const int32_t* perm, const float* a,
+                              const float* c, float* x_out, float* y_out, void* stream);
+
 /* Per-clip correlation graph and its dual random-walk supports, from the clips themselves
  * (replaces the DataLoader-side CPU code: dataloader_detection.py:258-307 `_get_indiv_graphs`
  * = |normalised lag-0 cross-correlation| of every electrode pair of the (N, T*D) clip, diag 1;
@@ -135,6 +159,16 @@ int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, in
 size_t eeg_dcrnn_corr_graph_ws_floats(int B, int T);
 int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, float* adj, float* S1,
                          float* S2, float* ws, void* stream);
+
+/* The same graph from WIDE channel rows (time-domain clips: dataloader_detection.py:258-307 on a clip of :25-85, whose
+ * `eeg_clip.reshape((num_sensors, -1))` is the raw (N, T*200) rows again).  The row of node n of clip b is P pieces of Q floats,
+ * piece p at X[b*clip + p*piece_stride + n*Q ..]: raw rows (B,N,L) are P = 1, Q = L (piece_stride ignored); a window tensor
+ * (B,T,N,D) is P = T, Q = D, piece_stride = N*D.  Q % 4 == 0 (no upper limit), N <= 32, a clip < 2 GB.  Normalisation, top-k and
+ * supports are the code of eeg_dcrnn_corr_graph; fixed-order sums (bit-reproducible).  HBM-bound: algorithmic bytes 4*B*N*P*Q.
+ * ws: eeg_dcrnn_corr_graph_rows_ws_floats(B, P, Q) floats. */
+size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q);
+int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1,
+                              float* S2, float* ws, void* stream);
 
 /* Number of floats of the packed weight block of one DCGRU cell. */
 size_t eeg_dcrnn_pack_floats(int Fin, int H, int M);
