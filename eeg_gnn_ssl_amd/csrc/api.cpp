@@ -1151,11 +1151,12 @@ size_t eeg_dcrnn_decoder_fwd_ws_floats(const eeg_decoder_dims* d) { return dec_d
 size_t eeg_dcrnn_decoder_bwd_ws_floats(const eeg_decoder_dims* d) { return dec_dims_positive(d) ? dec_layout(d).bwd_total : 0; }
 
 // the persistent decoder kernels (kernels_decoder.h) cover this shape: forward and backward always pair up over the shared `saved`
-// layout (64 units, <= 20 nodes, <= 4 layers, horizon <= 64, Dout <= 128 with Dout/4 divisible by 4 or 5 = the weight-group
-// sizes of the backward's projection transpose, both LDS budgets)
+// layout (64 units, <= 20 nodes, <= 4 layers, horizon <= 64, Dout <= 256 with Dout/4 divisible by 4 or 5 = the weight-group
+// sizes of the backward's projection transpose, both LDS budgets: past 128 outputs those decide -- M = 5 with two layers fits up
+// to 200 outputs, M = 5 with three layers and M = 7 do not: table in DESIGN.md 4.4)
 static bool dec_persistent_ok(const eeg_decoder_dims* d) {
     const int q4 = d->Dout / 4;
-    return d->H == 64 && d->N <= kDecRows && d->L >= 1 && d->L <= 4 && d->T >= 1 && d->T <= 64 && d->Dout <= 128
+    return d->H == 64 && d->N <= kDecRows && d->L >= 1 && d->L <= 4 && d->T >= 1 && d->T <= 64 && d->Dout <= 256
            && (q4 % 5 == 0 || q4 % 4 == 0) && seq_m_supported(d->M)
            && dec_fwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes
            && dec_bwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes;

@@ -76,7 +76,8 @@ __device__ __forceinline__ float rem4_reduce(f32x4 t) {
 }
 
 // columns of the packs c1 / c2 (kernels_pack.h): hidden units, then input features padded so that the decoder's
-// layers (Fin <= 128, 64 units) all have the SAME column-tile count, a literal in kernels_decoder.h
+// layers (Fin <= 128, 64 units) all have the SAME column-tile count, a literal in kernels_decoder.h; a wider first layer
+// (Fin = Dout up to 256) has 16 (Fin <= 192) or 20 column tiles, the template argument CX0 of the wide backward kernels
 __host__ __device__ constexpr int cell_pack_cx_cols(int Fin, int H) { return H + (Fin <= 128 ? 128 : round_up(Fin, 64)); }
 
 // Quad-permuted K order of the recurrent-kernel weight packs: MFMA number `ks` consumes, on lane

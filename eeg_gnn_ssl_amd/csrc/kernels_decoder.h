@@ -647,7 +647,12 @@ namespace eeg {
 // previous step's output gradient.  On chip per clip: the dC / [dR|dU] tiles with their adjoint hop rows, the
 // output-gradient tiles, the recurrent gradients dh^l (lane-linear LDS slots).  It emits dXW of every (layer, step) --
 // the hoisted parameter-gradient GEMMs, the bias column sums and the projection gradients stay as they are -- the total
-// output gradients dOtot and dh0.  At most 20 nodes, 64 units, Dout <= 128 (packs of 8 or 12 column tiles).
+// output gradients dOtot and dh0.  At most 20 nodes, 64 units, Dout <= 256 where the LDS tiles fit (dec_bwd_lds_floats).
+// Layer 0's c1 / c2 packs have CX0 column tiles: 12 up to 128 outputs, 16 up to 192, 20 up to 256 (cell_pack_cx_cols); the
+// layers above always 12.  Up to 128 outputs a wave owns at most two input-gradient tiles (w, w + 4) and GEMM1 / GEMM2 carry
+// them beside its hidden tile; the wide instantiations (CX0 > 12: 9..16 input-gradient tiles) add a SECOND pass over the same
+// adjoint hop rows for tiles w + 8, w + 12 (the wide tail) instead of a fourth and fifth tile in the first: five tiles of
+// weight ring and accumulators do not fit beside the rest at one wave per SIMD.
 struct DecBwdLayerPtrs {
     const float *c1, *c2;                            // weight packs [hidden | input] (kernels_pack.h)
     const float *hext, *rs, *us, *cs;                // saved by the forward
@@ -675,7 +680,7 @@ __host__ __device__ constexpr size_t dec_bwd_lds_floats(int M, int L, int Dout) 
            + (size_t)L * 4 * 2 * 256;
 }
 
-template <int H, int M, int DT>
+template <int H, int M, int DT, int CX0 = cell_pack_cx_cols(64, 64) / 16>
 __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
     unsigned long long feeds_mask = a.feeds_mask;
     if (a.teacher_dev != nullptr) {                 // flags drawn on the device: out_t feeds step t+1 unless teacher-forced
@@ -686,7 +691,9 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
     static_assert(H == 64, "one column tile per wave");
     constexpr int NKS = 5, ROWS = kDecRows, KAP = M * H, KGP = M * 2 * H, NCT = H / 16, NQ = M * H / 16;
     constexpr int PD = NQ < 3 ? NQ : 3;              // quads of weights in flight ahead of the MFMAs
-    constexpr int kCx = cell_pack_cx_cols(H, H) / 16;     // column tiles of the c1 / c2 packs (12)
+    constexpr int kCx = cell_pack_cx_cols(H, H) / 16;     // column tiles of the c1 / c2 packs (12); layer 0: CX0
+    constexpr bool WIDE = CX0 > kCx;                      // more than 128 outputs: 9..16 input-gradient tiles, layer 0's packs are wider
+    static_assert(CX0 == kCx || CX0 == cell_pack_cx_cols(192, H) / 16 || CX0 == cell_pack_cx_cols(256, H) / 16, "layer-0 pack width");
     EEG_DYN_SMEM(sm);
     const int T = a.T, B = a.B, N = a.N, Dout = a.Dout, L = a.L, act = a.act;
     const int FP = round_up(Dout, 16), FS = lds_stride_q(FP);      // row stride of the output-gradient tiles: 4 mod 64 dwords (conflict-free fragment reads)
@@ -702,9 +709,12 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
     const size_t state = (size_t)B * N * H;
     const int nct_h = H / 16, nct_o = FP / 16;
     // column tiles of c1 / c2 this wave accumulates: its hidden tile, then the input-feature tiles wave, wave + 4
-    const int nx0 = (nct_o + 3) / 4;                                // input tiles per wave, layer 0 (1 or 2)
+    const int nx0 = WIDE ? 2 : (nct_o + 3) / 4;                     // input tiles per wave in GEMM1 / GEMM2, layer 0 (1 or 2)
     const int wt0[3] = {ct, NCT + (wave < nct_o ? wave : 0), NCT + (wave + 4 < nct_o ? wave + 4 : 0)};
     const int wtu[3] = {ct, NCT + ct, NCT + ct};                    // layers above: input = 64 hidden units of the layer below
+    // wide tail: the input tiles wave + 8, wave + 12 that exist (nt2 of them; wave-uniform)
+    const int nt2 = WIDE ? (wave + 8 < nct_o ? 1 : 0) + (wave + 12 < nct_o ? 1 : 0) : 0;
+    const int wtt[2] = {NCT + (wave + 8 < nct_o ? wave + 8 : 0), NCT + (wave + 12 < nct_o ? wave + 12 : 0)};
 
     DecProbe<kDecProbe> pp;        // 0 output-gradient tile, 1 projection transpose, 2 blend backward + node mix + barrier, 3 GEMM1, 4 its epilogue
     pp.start();                    // + node mixes + barrier, 5 GEMM2, 6 hand-over of dX + barrier, 7 clip set-up / bias sums
@@ -742,7 +752,7 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
             nu[1] = (f32x4){lp.us[so + oh1], 0.f, 0.f, 0.f};
             nc[1] = (f32x4){lp.cs[so + oh1], 0.f, 0.f, 0.f};
         };
-        // column tiles of a pair: 1 (no input gradient wanted), 2 (layers above the first / narrow outputs) or 3
+        // column tiles of a pair in GEMM1 / GEMM2: 1 (no input gradient wanted), 2 (layers above the first / narrow outputs) or 3
         auto pair_nt = [&](int l, int t) {
             if (l > 0) return 2;
             return t > 0 && ((feeds_mask >> (t - 1)) & 1ull) != 0 ? 1 + nx0 : 1;
@@ -750,8 +760,32 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
         // weights requested ahead of their GEMM: the first group of the projection transpose, the first PD quads of GEMM1 / GEMM2
         const int wt1[1] = {ct};
         float wpt[DT][1], wq1[PD + 1][4][3], wq2[PD + 1][4][3];
-        // (kCx column tiles in every c1 / c2 pack: the weight addresses are base + immediate; narrower pairs skip tiles)
+        // (a literal count of column tiles per c1 / c2 pack: the weight addresses are base + immediate; narrower pairs skip tiles)
+        auto prefetch1_cx0 = [&](auto cxtag, int nt_) {                    // layer 0 of the wide instantiations: CX0 tiles per pack
+            constexpr int nct = decltype(cxtag)::value;
+            const wbuf_t wb = make_wbuf(a.l[0].c1);
+            const unsigned v0 = wt0[0] * 64 + lane, v1 = wt0[1] * 64 + lane, v2 = wt0[2] * 64 + lane;
+#pragma unroll
+            for (int q = 0; q < PD; ++q)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) wq1[q][j][0] = wbuf_ld(wb, v0, (4 * q + j) * nct * 64);
+            if (nt_ > 1) {
+#pragma unroll
+                for (int q = 0; q < PD; ++q)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        wq1[q][j][1] = wbuf_ld(wb, v1, (4 * q + j) * nct * 64);
+                        wq1[q][j][2] = wbuf_ld(wb, v2, (4 * q + j) * nct * 64);
+                    }
+            }
+        };
         auto prefetch1 = [&](int l, int nt_) {
+            if constexpr (WIDE) {
+                if (l == 0) {
+                    prefetch1_cx0(std::integral_constant<int, CX0>{}, nt_);
+                    return;
+                }
+            }
             const int(&wt)[3] = l == 0 ? wt0 : wtu;
             const wbuf_t wb = make_wbuf(a.l[l].c1);
             const unsigned v0 = wt[0] * 64 + lane, v1 = wt[1] * 64 + lane, v2 = wt[2] * 64 + lane;
@@ -852,9 +886,9 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
                 __syncthreads();                                         // (1) P_m^T dC complete
                 pp.mark(2, l);
                 const int ntp = pair_nt(l, t);
-                f32x4 dx[2][2] = {{zero4, zero4}, {zero4, zero4}};      // this wave's input-gradient tiles
-                auto cell = [&](auto ntag) {
-                    constexpr int NT = decltype(ntag)::value, nct = kCx;
+                f32x4 dx[2][2] = {{zero4, zero4}, {zero4, zero4}};      // this wave's input-gradient tiles (wave, wave + 4)
+                auto cell = [&](auto ntag, auto cxtag) {
+                    constexpr int NT = decltype(ntag)::value, nct = decltype(cxtag)::value;
                     int wtn[NT];
 #pragma unroll
                     for (int i = 0; i < NT; ++i) wtn[i] = wt[i];
@@ -895,10 +929,43 @@ __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
                     st4(dhl + l * 2048 + 1 * 256, acc[0][1]);
 #pragma unroll
                     for (int i = 1; i < NT; ++i) { dx[i - 1][0] = acc[i][0]; dx[i - 1][1] = acc[i][1]; }
+                    // ---- wide tail (layer 0, dX wanted): tiles wave + 8, wave + 12 of dX from a second pass over the same operand
+                    // tiles -- P_m^T dC and P_m^T [dR|dU] stay intact until barrier (3) -- with GEMM1's and GEMM2's terms summed in
+                    // one accumulator set like the first two tiles; the weight rings are free (the next pair's prefetch follows)
+                    if constexpr (WIDE && NT == 3) {
+                        auto tail = [&](auto n2tag) __attribute__((always_inline)) {
+                            constexpr int NT2 = decltype(n2tag)::value;
+                            int wt2[NT2];
+#pragma unroll
+                            for (int i = 0; i < NT2; ++i) wt2[i] = wtt[i];
+                            f32x4 ax[NT2][2];
+#pragma unroll
+                            for (int i = 0; i < NT2; ++i) { ax[i][0] = zero4; ax[i][1] = zero4; }
+                            gemm_stream_quad<NT2, NQ, PD, false, 3>(EC, KAP, lp.c1, nct, wt2, lane, lr, lg, ax, wq1);
+                            gemm_stream_quad<NT2, 2 * NQ, PD, false, 3>(EG, KGP, lp.c2, nct, wt2, lane, lr, lg, ax, wq2);
+#pragma unroll
+                            for (int i = 0; i < NT2; ++i) {              // straight to DX (first read behind barrier (3))
+                                const int j = wave + 8 + 4 * i;
+                                st4(DX + lr * FS + j * 16 + 4 * lg, ax[i][0]);
+                                DX[node1 * FS + j * 16 + lr] = ax[i][1][0];
+                            }
+                        };
+                        if (nt2 == 2) tail(std::integral_constant<int, 2>{});
+                        else if (nt2 == 1) tail(std::integral_constant<int, 1>{});
+                        pp.mark(5, l);
+                    }
                 };
-                if (ntp == 3) cell(std::integral_constant<int, 3>{});
-                else if (ntp == 2) cell(std::integral_constant<int, 2>{});
-                else cell(std::integral_constant<int, 1>{});
+                using CxU = std::integral_constant<int, kCx>;
+                if constexpr (WIDE) {                                    // layer 0: CX0 tiles per pack, 1 or 3 tiles of them per wave
+                    using Cx0 = std::integral_constant<int, CX0>;
+                    if (l > 0) cell(std::integral_constant<int, 2>{}, CxU{});
+                    else if (ntp == 3) cell(std::integral_constant<int, 3>{}, Cx0{});
+                    else cell(std::integral_constant<int, 1>{}, Cx0{});
+                } else {
+                    if (ntp == 3) cell(std::integral_constant<int, 3>{}, CxU{});
+                    else if (ntp == 2) cell(std::integral_constant<int, 2>{}, CxU{});
+                    else cell(std::integral_constant<int, 1>{}, CxU{});
+                }
                 // the next pair's first weights fly across the barrier
                 if (l > 0) prefetch1(l - 1, pair_nt(l - 1, t));
                 else if (t > 0) plain_wload<1, DT>(a.tpack, nct_h, wt1, lane, 0, wpt);

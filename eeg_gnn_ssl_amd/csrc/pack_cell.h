@@ -19,7 +19,8 @@ struct CellPack {
     // persistent decoder backward (kernels_decoder.h): b1 / b2 widened by the input-feature columns, so that the
     // recurrent GEMMs also produce dX = sum_m (P_m^T dXW) W^x_m^T from the SAME adjoint hop rows
     // (O = cell_pack_cx_cols: 12 column tiles for 64 units and up to 128 input features -- ONE literal tile count for every
-    //  layer of the decoder, so the streamed-weight addresses are base + immediate)
+    //  layer of the decoder, so the streamed-weight addresses are base + immediate; a first layer of 129..192 / 193..256 input
+    //  features has 16 / 20 tiles, a literal of the wide instantiations of dec_bwd_persist_kernel)
     size_t c1;     // K = M*H  (k = m*H + o),  O columns: [Wc^h | Wc^x | 0] transposed, quad-permuted K
     size_t c2;     // K = M*2H (k = m*2H + o), O columns: [Wg^h | Wg^x | 0] transposed, quad-permuted K
     // round 3, gemm_nnr_kernel (kernels_gemm_q.h): the same two right-hand sides in quad order (one ds_read_b128 per lane feeds

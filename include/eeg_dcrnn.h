@@ -271,7 +271,9 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
  * over the T steps.  dWg/dbg/dWc/dbc: HOST arrays of L device pointers (entries 1..L-1 equal:
  * gradients of the shared cell are summed); dh0 (L,B,N,H); dWp (Dout,H); dbp (Dout).
  * d->teacher_on_device = 1: `teacher` is a device array (targets must then be given); available where the persistent decoder
- * kernels run (64 units, <= 20 nodes, <= 4 layers, T <= 64, Dout <= 128 with Dout/4 divisible by 4 or 5), refused elsewhere:
+ * kernels run (64 units, <= 20 nodes, <= 4 layers, T <= 64, Dout <= 256 with Dout/4 divisible by 4 or 5, where the kernels'
+ * LDS tiles fit: past 128 outputs that is up to 5 hop matrices with two layers at Dout <= 200, up to 3 with three layers at
+ * Dout <= 256; eeg_dcrnn_decoder_is_persistent answers for a shape), refused elsewhere:
  * the per-step launch sequence is selected by the flags and cannot depend on device memory. */
 size_t eeg_dcrnn_decoder_saved_floats(const eeg_decoder_dims* d);
 size_t eeg_dcrnn_decoder_fwd_ws_floats(const eeg_decoder_dims* d);
@@ -281,7 +283,8 @@ size_t eeg_dcrnn_decoder_bwd_ws_floats(const eeg_decoder_dims* d);
  * for T*B*N*H/4 counters: element e = ((t*B + b)*N + n)*H + h of the top-layer outputs takes word e%4 of counter offset + e/4.
  * The masks are fused into the persistent kernels (nothing is stored but the dropped rows that dW_p needs) and recomputed in the
  * backward from the same pair.  dropout_p == 0: rng_used may be NULL. */
-/* 1 if the persistent decoder kernels cover this shape (then d->teacher_on_device = 1 is available), else 0. */
+/* 1 if the persistent decoder kernels cover this shape (then d->teacher_on_device = 1 is available), else 0: the conditions above,
+ * both LDS budgets included (e.g. Dout = 200: M = 5, L = 2 yes; M = 5, L = 3 and every M = 7 no). */
 int eeg_dcrnn_decoder_is_persistent(const eeg_decoder_dims* d);
 int eeg_dcrnn_decoder_fwd(const eeg_decoder_dims* d, const float* targets, const int32_t* teacher,
                           const float* h0, const float* P, const float* const* packs, const float* Wp,

@@ -5,12 +5,14 @@ B = 512 with 60 s in / 12 s out (the SSL pair) and at B = 256 with 60 s (a super
   2. `ops.augment_windows` against its ATen expression `x.gather(2, idx) * a + c` (x and y);
   3. `ops.correlation_supports_raw` on the raw rows (B, N, 12000) against the existing `corr_graph` kernel on a (B, 120, N, 100)
      tensor of equal bytes;
-  4. the captured raw time-domain step against the captured step from ready windows (both augmented, correlation graph), clips/s.
+  4. the captured raw time-domain step against the captured step from ready windows (both augmented, correlation graph), clips/s;
+     `--curriculum`: the SSL step once more with `use_curriculum_learning=True` (teacher-forcing flags drawn inside the graph).  Where
+     the decoder shape is outside the persistent decoder kernels the capture is refused and the row reads "not available".
 Every figure: warm, `--rounds` rounds alternating between the candidates, each round ~0.1 s per candidate; median and spread
 (min..max) over the rounds.  Achieved TB/s are against ALGORITHMIC bytes (8*B*N*(Tx+Ty)*W for the two streaming kernels, 4*B*N*L for
 the Gram) beside the 8 TB/s of the data sheet; the rate of a plain device copy of the same bytes is given as a footnote.
 Kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/time_timedomain_ops.py --skip-step`.
-usage: python tools/time_timedomain_ops.py [--rounds 7] [--skip-step] [--out profiles/timedomain_time_ops.json]"""
+usage: python tools/time_timedomain_ops.py [--rounds 7] [--skip-step] [--curriculum] [--out profiles/timedomain_time_ops.json]"""
 import argparse
 import json
 import os
@@ -27,6 +29,7 @@ from eeg_gnn_ssl_amd.train_step import TrainStep  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--skip-step", action="store_true")
+ap.add_argument("--curriculum", action="store_true")
 ap.add_argument("--out", default=None)
 opt = ap.parse_args()
 
@@ -147,10 +150,11 @@ def one_shape(B, TX, TY):
 
     # 4. the whole captured step (forward + backward + update; clips/s): raw signals against ready windows
     if not opt.skip_step:
-        def step_rate(raw):
+        def step_rate(raw, curriculum=False):
             torch.manual_seed(5)
             args = bench.make_args("dual_random_walk")
             args.input_dim = args.output_dim = W
+            args.use_curriculum_learning = curriculum
             if TY:
                 model, task = DCRNNModel_nextTimePred(args, device=dev).to(dev).train(), "ssl"
                 yi = raw_y if raw else ys
@@ -160,7 +164,12 @@ def one_shape(B, TX, TY):
             kw = dict(raw_window=W, raw_mean=MEAN, raw_std=STD) if raw else dict(feature_mean=MEAN, feature_std=STD)
             st = TrainStep(model, task=task, use_fft=False, data_augment=True, **kw)
             lengths = torch.full((B,), TX, dtype=torch.int64, device=dev)
-            st.capture(raw_x if raw else xs, yi, lengths, None)
+            try:
+                st.capture(raw_x if raw else xs, yi, lengths, None)
+            except RuntimeError as e:
+                if curriculum and "outside the persistent decoder kernels" in str(e):
+                    return "not available"
+                raise
             for _ in range(3):
                 st.replay_step()
             torch.cuda.synchronize()
@@ -169,6 +178,9 @@ def one_shape(B, TX, TY):
 
         out["step_from_raw_signals"] = step_rate(True)
         out["step_from_ready_windows"] = step_rate(False)
+        if opt.curriculum and TY:
+            out["step_from_raw_signals_curriculum"] = step_rate(True, curriculum=True)
+            out["step_from_ready_windows_curriculum"] = step_rate(False, curriculum=True)
     return out
 
 
