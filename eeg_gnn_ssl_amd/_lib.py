@@ -88,6 +88,11 @@ _SIGNATURES = {
     "eeg_dcrnn_augment_windows": (c_int, [_FP, _FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_corr_graph_rows_ws_floats": (c_size_t, [c_int, c_int, c_int]),
     "eeg_dcrnn_corr_graph_rows": (c_int, [_FP, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    # variable-length clips (dataloader_classification.py:25-85,321-343,356-361): `lengths` is a device int64 (B) pointer
+    "eeg_dcrnn_fft_features_len": (c_int, [_FP, c_int, c_int, c_int, c_int, _FP, _FP, c_float, c_float, _FP, c_float, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_window_features_len": (c_int, [_FP, c_int, c_int, c_int, c_int, _FP, _FP, c_float, c_float, _FP, c_float, _FP, c_void_p]),
+    "eeg_dcrnn_corr_graph_len": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_corr_graph_rows_len": (c_int, [_FP, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_augment_draw": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, _FP, c_void_p]),
     "eeg_dcrnn_pack_cells": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32),
                              c_int, c_int, POINTER(c_void_p), _FP, c_int, POINTER(c_void_p), c_void_p]),

@@ -929,8 +929,10 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
 
 
 /* ---- input featurisation -------------------------------------------------------------------------- */
-int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* log_scale,
-                           float mean, float std_, float* feat_raw, float* feat_std, void* stream) {
+// lengths == nullptr: the plain kernels (every window transformed); else their length-aware variants
+static int fft_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* log_scale, float mean, float std_,
+                        const int64_t* lengths, float pad_val, float* feat_raw, float* feat_std, void* stream) {
+    const long long* len = reinterpret_cast<const long long*>(lengths);
     if (B < 1 || N < 1 || T < 1) return fail("fft_features: empty input (B=%d, N=%d, T=%d)", B, N, T);
     if (W < 4 || W % 4 != 0 || W / 4 + 1 > 64) return fail("fft_features: window=%d unsupported (multiple of 4, <= 252)", W);
     if (feat_raw == nullptr && feat_std == nullptr) return fail("fft_features: no output requested");
@@ -942,16 +944,37 @@ int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const i
         const long long cap = (long long)platform_num_cus() * kFftWgPerCu;  // workgroups of 4 waves per CU the kernel's registers allow, persistent
         if (blocks > cap) blocks = cap;
         const size_t lds = 4 * (size_t)kFftWaveDoubles * sizeof(double);
-        EEG_SET_MAX_LDS(fft200_features_kernel, lds);
-        EEG_LAUNCH_P("fft_features", fft200_features_kernel, dim3((unsigned)blocks), dim3(256), lds, S_(stream), raw, N, T, n_windows,
-                     reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std);
+        if (len == nullptr) {
+            EEG_SET_MAX_LDS(fft200_features_kernel<false>, lds);
+            EEG_LAUNCH_P("fft_features", fft200_features_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, S_(stream), raw, N, T, n_windows,
+                         reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std, len, 0.f);
+        } else {
+            EEG_SET_MAX_LDS(fft200_features_kernel<true>, lds);
+            EEG_LAUNCH_P("fft_features_len", fft200_features_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, S_(stream), raw, N, T, n_windows,
+                         reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std, len, pad_val);
+        }
         return check_launch("fft_features");
     }
     int tchunk = T;                                   // ~8 waves per SIMD in total
     while (tchunk > 1 && (long long)B * N * ceil_div(T, tchunk) < 8192) tchunk = ceil_div(tchunk, 2);
-    EEG_LAUNCH_P("fft_features", fft_features_kernel, dim3(B * N, ceil_div(T, tchunk)), dim3(64), (size_t)W * sizeof(double), S_(stream),
-                 raw, N, T, W, tchunk, reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std);
+    if (len == nullptr)
+        EEG_LAUNCH_P("fft_features", fft_features_kernel<false>, dim3(B * N, ceil_div(T, tchunk)), dim3(64), (size_t)W * sizeof(double), S_(stream),
+                     raw, N, T, W, tchunk, reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std, len, 0.f);
+    else
+        EEG_LAUNCH_P("fft_features_len", fft_features_kernel<true>, dim3(B * N, ceil_div(T, tchunk)), dim3(64), (size_t)W * sizeof(double), S_(stream),
+                     raw, N, T, W, tchunk, reinterpret_cast<const int*>(perm), log_scale, mean, 1.0f / std_, feat_raw, feat_std, len, pad_val);
     return check_launch("fft_features");
+}
+
+int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* log_scale,
+                           float mean, float std_, float* feat_raw, float* feat_std, void* stream) {
+    return fft_features(raw, B, N, T, W, perm, log_scale, mean, std_, nullptr, 0.f, feat_raw, feat_std, stream);
+}
+
+int eeg_dcrnn_fft_features_len(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* log_scale, float mean,
+                               float std_, const int64_t* lengths, float pad_val, float* feat_raw, float* feat_std, void* stream) {
+    if (raw == nullptr || lengths == nullptr) return fail("fft_features_len: null input / lengths");
+    return fft_features(raw, B, N, T, W, perm, log_scale, mean, std_, lengths, pad_val, feat_raw, feat_std, stream);
 }
 
 int eeg_dcrnn_fft_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
@@ -1003,7 +1026,8 @@ int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, in
 /* ---- time-domain inputs: windows of the raw signals, multiplicative augmentation -------------------- */
 // one launch of window_stream_kernel over x (and y when Ty > 0); `what` names the entry point in refusals
 static int window_stream(const char* what, bool raw, const float* x, const float* y, int B, int Tx, int Ty, int N, int W, const int32_t* perm,
-                         const float* a, const float* c, float mean, float std_, float* x_out, float* y_out, void* stream) {
+                         const float* a, const float* c, float mean, float std_, float* x_out, float* y_out, void* stream,
+                         const int64_t* lengths = nullptr, float pad_val = 0.f) {
     if (B < 1 || N < 1 || Tx < 1 || Ty < 0) return fail("%s: empty input (B=%d, N=%d, Tx=%d, Ty=%d)", what, B, N, Tx, Ty);
     if (W < 4 || W % 4 != 0) return fail("%s: window=%d unsupported (positive multiple of 4)", what, W);
     if (x_out == x || (Ty > 0 && y_out == y)) return fail("%s: in-place call (rows move between nodes: outputs must not alias inputs)", what);
@@ -1013,10 +1037,18 @@ static int window_stream(const char* what, bool raw, const float* x, const float
     if (chunks > 65535) return fail("%s: %lld values per clip exceed one launch (limit %lld)", what, 4 * pieces, 4LL * 65535 * kAugPerBlock);
     const dim3 grid((unsigned)B, (unsigned)chunks);
     const int* pm = reinterpret_cast<const int*>(perm);
+    const long long* len = reinterpret_cast<const long long*>(lengths);
 #define EEG_WSTREAM(RAW, D4C) \
-    EEG_LAUNCH_P(what, (window_stream_kernel<RAW, D4C>), grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, W / 4, pm, a, c, mean, std_, x_out, y_out)
-    if (raw) { if (W == 200) EEG_WSTREAM(true, 50); else EEG_WSTREAM(true, 0); }
+    EEG_LAUNCH_P(what, (window_stream_kernel<RAW, D4C>), grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, W / 4, pm, a, c, mean, std_, x_out, y_out, \
+                 len, 0.f)
+#define EEG_WSTREAM_LEN(D4C)                                                                                                            \
+    EEG_LAUNCH_P(what, (window_stream_kernel<true, D4C, true>), grid, dim3(kAugThreads), 0, S_(stream), x, y, N, Tx, Ty, W / 4, pm, a, c, mean, \
+                 std_, x_out, y_out, len, pad_val)
+    if (lengths != nullptr) {                         // raw signals of ONE clip per sample (the callers see to that): the padded variant
+        if (W == 200) EEG_WSTREAM_LEN(50); else EEG_WSTREAM_LEN(0);
+    } else if (raw) { if (W == 200) EEG_WSTREAM(true, 50); else EEG_WSTREAM(true, 0); }
     else { if (W == 200) EEG_WSTREAM(false, 50); else EEG_WSTREAM(false, 0); }
+#undef EEG_WSTREAM_LEN
 #undef EEG_WSTREAM
     return check_launch(what);
 }
@@ -1027,6 +1059,15 @@ int eeg_dcrnn_window_features(const float* raw, int B, int N, int T, int W, cons
     if (x_std == nullptr) return fail("window_features: null output");
     if (!(std_ != 0.f)) return fail("window_features: std must be non-zero");
     return window_stream("window_features", true, raw, nullptr, B, T, 0, N, W, perm, scale, nullptr, mean, std_, x_std, nullptr, stream);
+}
+
+int eeg_dcrnn_window_features_len(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* scale, float mean,
+                                  float std_, const int64_t* lengths, float pad_val, float* x_std, void* stream) {
+    if (raw == nullptr || lengths == nullptr) return fail("window_features_len: null input / lengths");
+    if (x_std == nullptr) return fail("window_features_len: null output");
+    if (!(std_ != 0.f)) return fail("window_features_len: std must be non-zero");
+    return window_stream("window_features_len", true, raw, nullptr, B, T, 0, N, W, perm, scale, nullptr, mean, std_, x_std, nullptr, stream,
+                         lengths, pad_val);
 }
 
 int eeg_dcrnn_window_features_pair(const float* raw_x, const float* raw_y, int B, int N, int Tx, int Ty, int W, const int32_t* perm,
@@ -1069,8 +1110,9 @@ int eeg_dcrnn_augment_draw(const uint64_t* rng_used, int B, int N, const int32_t
 }
 
 size_t eeg_dcrnn_corr_graph_ws_floats(int B, int T) { return (B >= 1 && T >= 1) ? (size_t)B * corr_nsplit(B, T) * kGramFloats : 0; }
-int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, float* adj, float* S1, float* S2,
-                         float* ws, void* stream) {
+static int corr_graph(const float* X, int B, int T, int N, int D, int top_k, const int64_t* lengths, float* adj, float* S1, float* S2,
+                      float* ws, void* stream) {
+    const long long* len = reinterpret_cast<const long long*>(lengths);
     if (N < 1 || N > kMaxNodes) return fail("corr_graph: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
     if (D < 4 || D % 4 != 0) return fail("corr_graph: feature dim=%d unsupported (positive multiple of 4)", D);
     if (B < 1 || T < 1) return fail("corr_graph: empty batch/clip (B=%d, T=%d)", B, T);
@@ -1081,23 +1123,41 @@ int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, 
     const size_t lds = 4 * (size_t)(step_floats > kGramFloats ? step_floats : kGramFloats) * sizeof(float);
     if (lds > 64 * 1024) return fail("corr_graph: N*D=%d too large for the per-wave staging buffers", N * D);
     switch (ceil_div(D, 16)) {
+#define EEG_GRAM_LEN(NQ, REM4)                                                                                                \
+    do {                                                                                                                      \
+        EEG_SET_MAX_LDS((corr_gram_kernel<NQ, REM4, true>), lds);                                                             \
+        EEG_LAUNCH_P("corr_gram_len", (corr_gram_kernel<NQ, REM4, true>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len); \
+    } while (0)
 #define EEG_GRAM(NQ)                                                                                                          \
     case NQ:                                                                                                                  \
-        if (N <= 20) {                                                                                                        \
+        if (len != nullptr) {                                                                                                 \
+            if (N <= 20) EEG_GRAM_LEN(NQ, true); else EEG_GRAM_LEN(NQ, false);                                                \
+        } else if (N <= 20) {                                                                                                        \
             EEG_SET_MAX_LDS((corr_gram_kernel<NQ, true>), lds);                                                               \
-            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, true>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats);  \
+            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, true>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len);  \
         } else {                                                                                                              \
             EEG_SET_MAX_LDS((corr_gram_kernel<NQ, false>), lds);                                                              \
-            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, false>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats); \
+            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, false>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len); \
         }                                                                                                                     \
         break;
         EEG_GRAM(1) EEG_GRAM(2) EEG_GRAM(3) EEG_GRAM(4) EEG_GRAM(5) EEG_GRAM(6) EEG_GRAM(7) EEG_GRAM(8)
 #undef EEG_GRAM
+#undef EEG_GRAM_LEN
         default: return fail("corr_graph: feature dim=%d unsupported (<= 128)", D);
     }
     if (check_launch("corr_gram")) return 1;
     EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
     return check_launch("corr_finish");
+}
+int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, float* adj, float* S1, float* S2,
+                         float* ws, void* stream) {
+    return corr_graph(X, B, T, N, D, top_k, nullptr, adj, S1, S2, ws, stream);
+}
+int eeg_dcrnn_corr_graph_len(const float* X, int B, int T, int N, int D, int top_k, const int64_t* lengths, float* adj, float* S1, float* S2,
+                             float* ws, void* stream) {
+    if (X == nullptr || ws == nullptr || lengths == nullptr) return fail("corr_graph_len: null input / workspace / lengths");
+    if (S1 == nullptr || S2 == nullptr) return fail("corr_graph_len: null output (S1=%p, S2=%p)", (void*)S1, (void*)S2);
+    return corr_graph(X, B, T, N, D, top_k, lengths, adj, S1, S2, ws, stream);
 }
 
 // chunks of a clip's channel rows (P pieces of Q floats), and the workgroups per clip that share them
@@ -1111,8 +1171,10 @@ static int corr_rows_nsplit(int B, int P, int Q) {
 size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q) {
     return (B >= 1 && P >= 1 && Q >= 1) ? (size_t)B * corr_rows_nsplit(B, P, Q) * kGramFloats : 0;
 }
-int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1, float* S2,
-                              float* ws, void* stream) {
+// lengths != nullptr: `steps` = the steps of a full clip (raw rows: Q = steps * samples per step; window tensors: steps = P)
+static int corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, const int64_t* lengths, int steps,
+                           float* adj, float* S1, float* S2, float* ws, void* stream) {
+    const long long* len = reinterpret_cast<const long long*>(lengths);
     if (X == nullptr || ws == nullptr) return fail("corr_graph_rows: null input / workspace");
     if (S1 == nullptr || S2 == nullptr) return fail("corr_graph_rows: null output (S1=%p, S2=%p)", (void*)S1, (void*)S2);
     if (N < 1 || N > kMaxNodes) return fail("corr_graph_rows: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
@@ -1130,16 +1192,41 @@ int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long l
     const int tile_floats = N * kRowChunk > kGramFloats ? N * kRowChunk : kGramFloats;
     const size_t lds = 4 * (size_t)tile_floats * sizeof(float);            // <= 128 KB (N = 32)
     const unsigned ps = P > 1 ? (unsigned)piece_stride : 0u;
-    if (N <= 20) {
+    if (len != nullptr) {
+        int unit = 0;                                 // samples per step of raw rows; 0: window tensors, a step = a piece
+        if (P == 1) {
+            if (steps < 1 || Q % steps != 0 || (Q / steps) % 4 != 0)
+                return fail("corr_graph_rows_len: rows of %d floats are not %d steps of a multiple of 4 samples", Q, steps);
+            unit = Q / steps;
+        } else if (steps != P) {
+            return fail("corr_graph_rows_len: steps=%d for a window tensor of %d pieces (a step is a piece)", steps, P);
+        }
+        if (N <= 20) {
+            EEG_SET_MAX_LDS((corr_gram_rows_kernel<true, true>), lds);
+            EEG_LAUNCH_P("corr_gram_rows_len", (corr_gram_rows_kernel<true, true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, unit);
+        } else {
+            EEG_SET_MAX_LDS((corr_gram_rows_kernel<false, true>), lds);
+            EEG_LAUNCH_P("corr_gram_rows_len", (corr_gram_rows_kernel<false, true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, unit);
+        }
+    } else if (N <= 20) {
         EEG_SET_MAX_LDS((corr_gram_rows_kernel<true>), lds);
-        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats);
+        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, 0);
     } else {
         EEG_SET_MAX_LDS((corr_gram_rows_kernel<false>), lds);
-        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<false>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats);
+        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<false>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, 0);
     }
     if (check_launch("corr_gram_rows")) return 1;
     EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
     return check_launch("corr_finish");
+}
+int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1, float* S2,
+                              float* ws, void* stream) {
+    return corr_graph_rows(X, B, N, P, Q, piece_stride, top_k, nullptr, 0, adj, S1, S2, ws, stream);
+}
+int eeg_dcrnn_corr_graph_rows_len(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, const int64_t* lengths,
+                                  int steps, float* adj, float* S1, float* S2, float* ws, void* stream) {
+    if (lengths == nullptr) return fail("corr_graph_rows_len: null lengths");
+    return corr_graph_rows(X, B, N, P, Q, piece_stride, top_k, lengths, steps, adj, S1, S2, ws, stream);
 }
 
 /* ---- decoder ---------------------------------------------------------------------------------- */

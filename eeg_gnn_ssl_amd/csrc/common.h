@@ -31,6 +31,12 @@ constexpr bool kDevBuild = false;
 
 __host__ __device__ constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ constexpr int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// valid steps of clip b of a padded batch (dataloader_classification.py:333-335 `seq_len`): a length outside 1..T is clamped, like
+// the gather of the model's last relevant output without strict_lengths
+__device__ __forceinline__ int clip_steps(const long long* __restrict__ lengths, int b, int T) {
+    const long long l = lengths[b];
+    return l < 1 ? 1 : (l > (long long)T ? T : (int)l);
+}
 
 // LDS row stride (floats) for an MFMA A-operand tile with K logical columns: K rounded so that
 // stride % 32 == 2 -> the 16 rows of a tile land on 16 distinct even banks and the two k-lanes

@@ -23,10 +23,15 @@ __device__ __forceinline__ int perm_source(const int* __restrict__ perm, int b, 
     return (unsigned)s < (unsigned)N ? s : nd;
 }
 
+// LEN (variable-length clips, dataloader_classification.py:25-85,321-343: a clip has curr_len <= max_seq_len steps, is augmented and
+// standardised as it is and THEN padded with padding_val): clip b has clip_steps(lengths, b, T) valid windows; a window behind them is
+// not transformed -- its feat_std row is pad_val (the padding behind the scaler), its feat_raw row 0 (adds nothing to a Gram).
+template <bool LEN>
 __global__ __launch_bounds__(64) void fft_features_kernel(const float* __restrict__ raw, int N, int T, int W, int tchunk,
                                                           const int* __restrict__ perm, const float* __restrict__ log_scale,
                                                           float mean, float inv_std, float* __restrict__ feat_raw,
-                                                          float* __restrict__ feat_std) {
+                                                          float* __restrict__ feat_std, const long long* __restrict__ lengths,
+                                                          float pad_val) {
     EEG_DYN_SMEM(sm);
     double* xs = reinterpret_cast<double*>(sm);          // [W]
     const int lane = threadIdx.x, b = blockIdx.x / N, nd = blockIdx.x % N, H2 = W / 2;
@@ -37,7 +42,19 @@ __global__ __launch_bounds__(64) void fft_features_kernel(const float* __restric
     double c1 = 1.0, s1 = 0.0;
     if (active) sincos(6.283185307179586476925286766559 * (double)lane / (double)W, &s1, &c1);
     const int t0 = blockIdx.y * tchunk, t1 = (t0 + tchunk < T) ? t0 + tchunk : T;
+    int tv = T;
+    if constexpr (LEN) tv = clip_steps(lengths, b, T);
     for (int t = t0; t < t1; ++t) {
+        if constexpr (LEN) {
+            if (t >= tv) {                                // padding (wave-uniform): the un-augmented zero row stays at the source channel
+                const size_t o_raw = (((size_t)b * T + t) * N + src) * H2, o_std = (((size_t)b * T + t) * N + nd) * H2;
+                for (int k = lane; k < H2; k += 64) {
+                    if (feat_raw != nullptr) feat_raw[o_raw + k] = 0.f;
+                    if (feat_std != nullptr) feat_std[o_std + k] = pad_val;
+                }
+                continue;
+            }
+        }
         EEG_WAVE_SYNC();                                  // previous window fully consumed
         for (int i = lane; i < W; i += 64) xs[i] = (double)sig[(size_t)t * W + i];
         EEG_WAVE_SYNC();
@@ -136,17 +153,55 @@ __device__ __forceinline__ void fft200_twiddles(int q, cplx (&tw1)[10], cplx (&t
     }
 }
 
+// the 16-byte piece at `pos` of a PADDED window wj = (bt, nd) of clip b: pad_val in feat_std at the window's own slot, 0 in feat_raw
+// at the source node's slot (where a transformed window's un-augmented row goes)
+__device__ __forceinline__ void fft200_store_pad(int N, const int* __restrict__ perm, float* __restrict__ feat_raw, float* __restrict__ feat_std,
+                                                 long long wj, long long bt, int b, int nd, int pos, float pad_val) {
+    if (feat_raw != nullptr) {
+        const int src = perm_source(perm, b, N, nd);
+        *reinterpret_cast<f32x4*>(feat_raw + ((size_t)bt * N + src) * kFftBins + pos) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (feat_std != nullptr) *reinterpret_cast<f32x4*>(feat_std + (size_t)wj * kFftBins + pos) = f32x4{pad_val, pad_val, pad_val, pad_val};
+}
+
 // One item = 6 consecutive (b, t, node) windows of ONE (B, N, T*200) buffer, transformed by one wave (the body shared by the
 // single-buffer and the paired kernel: the same instructions on the same operands, so both give the same bits).
+// LEN: windows (b, t >= clip_steps(lengths, b, T)) are padding (see fft_features_kernel).  `vmask` = the valid windows of the item, the
+// same value in every lane: an item wholly in padding stores its 150 pad pieces and returns (a wave-uniform branch: no load, no
+// transform); in an item that straddles the end of a clip -- or two rows or clips when 6 does not divide N -- the ten lanes of a
+// padded window sit the transform out and its pieces leave as padding.  A valid window takes the instructions of the plain item.
+template <bool LEN = false>
 __device__ __forceinline__ void fft200_item(const float* __restrict__ raw, int N, int T, long long n_windows, const int* __restrict__ perm,
                                             const float* __restrict__ log_scale, float mean, float inv_std, float* __restrict__ feat_raw,
                                             float* __restrict__ feat_std, long long item, cplx* tile, int lane, const cplx (&tw1)[10],
-                                            const cplx (&tw2)[10], double log_floor) {
+                                            const cplx (&tw2)[10], double log_floor, const long long* __restrict__ lengths = nullptr,
+                                            float pad_val = 0.f) {
     float* ftile = reinterpret_cast<float*>(tile);                       // [6][100] log amplitudes (aliases the tile, behind a wave sync)
     const int w = lane / 10, q = lane - 10 * w;                          // window of the wave, position (n2 in stage 1, k1 in stage 2)
     const bool active = w < kFftPerWave;
     const long long w0 = item * kFftPerWave, wg = w0 + w;
-    const bool live = active && wg < n_windows;
+    unsigned vmask = (1u << kFftPerWave) - 1u;
+    if constexpr (LEN) {
+        vmask = 0u;
+        const long long bt0 = w0 / N;
+        int nd = (int)(w0 % N), t = (int)(bt0 % T), b = (int)(bt0 / T);
+        for (int j = 0; j < kFftPerWave && w0 + j < n_windows; ++j) {    // (b < B while w0 + j < n_windows: lengths is read in bounds)
+            if (t < clip_steps(lengths, b, T)) vmask |= 1u << j;
+            if (++nd == N) { nd = 0; if (++t == T) { t = 0; ++b; } }
+        }
+        vmask = (unsigned)wave_uniform((int)vmask);
+        if (vmask == 0u) {
+            for (int c = lane; c < kFftPerWave * kFftBins / 4; c += 64) {
+                const int j = c / 25, pos = 4 * (c - 25 * j);
+                const long long wj = w0 + j;
+                if (wj >= n_windows) continue;
+                const long long bt = wj / N;
+                fft200_store_pad(N, perm, feat_raw, feat_std, wj, bt, (int)(bt / T), (int)(wj % N), pos, pad_val);
+            }
+            return;
+        }
+    }
+    const bool live = active && wg < n_windows && (!LEN || ((vmask >> w) & 1u) != 0u);
     cplx a[10], A[10];
     if (live) {
         const int nd = (int)(wg % N);
@@ -211,6 +266,12 @@ __device__ __forceinline__ void fft200_item(const float* __restrict__ raw, int N
         const int nd = (int)(wj % N);
         const long long bt = wj / N;
         const int b = (int)(bt / T);
+        if constexpr (LEN) {
+            if (((vmask >> j) & 1u) == 0u) {
+                fft200_store_pad(N, perm, feat_raw, feat_std, wj, bt, b, nd, pos, pad_val);
+                continue;
+            }
+        }
         if (feat_raw != nullptr) {
             const int src = perm_source(perm, b, N, nd);
             *reinterpret_cast<f32x4*>(feat_raw + ((size_t)bt * N + src) * kFftBins + pos) = val;
@@ -226,10 +287,12 @@ __device__ __forceinline__ void fft200_item(const float* __restrict__ raw, int N
     EEG_WAVE_SYNC();                                                 // the output tile is free again
 }
 
+template <bool LEN>
 __global__ __launch_bounds__(256, EEG_FFT_MINW) void fft200_features_kernel(const float* __restrict__ raw, int N, int T, long long n_windows,
                                                               const int* __restrict__ perm, const float* __restrict__ log_scale,
                                                               float mean, float inv_std, float* __restrict__ feat_raw,
-                                                              float* __restrict__ feat_std) {
+                                                              float* __restrict__ feat_std, const long long* __restrict__ lengths,
+                                                              float pad_val) {
     EEG_DYN_SMEM(sm);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     cplx* tile = reinterpret_cast<cplx*>(sm) + (size_t)wave * (kFftWaveDoubles / 2);
@@ -238,7 +301,8 @@ __global__ __launch_bounds__(256, EEG_FFT_MINW) void fft200_features_kernel(cons
     const double log_floor = log(1e-8);                                  // computeFFT: amp == 0 -> 1e-8
     const long long n_items = (n_windows + kFftPerWave - 1) / kFftPerWave;
     for (long long item = (long long)blockIdx.x * 4 + wave; item < n_items; item += (long long)gridDim.x * 4)
-        fft200_item(raw, N, T, n_windows, perm, log_scale, mean, inv_std, feat_raw, feat_std, item, tile, lane, tw1, tw2, log_floor);
+        fft200_item<LEN>(raw, N, T, n_windows, perm, log_scale, mean, inv_std, feat_raw, feat_std, item, tile, lane, tw1, tw2, log_floor, lengths,
+                         pad_val);
 }
 
 // The SSL sample is a PAIR (dataloader_ssl.py:317-341): 60 s of input and the first seconds of the following clip as target, ONE
@@ -330,12 +394,18 @@ __global__ __launch_bounds__(kAugThreads) void augment_features_kernel(const flo
 // clip's (Tx + Ty) * N output rows (x rows first, Ty = 0: no second half), kAugUnroll pieces in flight per thread; consecutive
 // lanes hold consecutive pieces, so stores are whole lines and loads whole rows of 4*W bytes.  Every element takes the same
 // instructions whether its half travels alone or in a pair: the paired launch is a re-scheduling, bit for bit.
-template <bool RAW, int D4C>    // D4C: 16-byte pieces per row when known at compile time (50: W = 200), 0 = read D4
+// LEN (single clip, Ty = 0; dataloader_classification.py:321-343: the short clip is scaled and standardised, then padded): the pieces
+// of the steps t >= clip_steps(lengths, b, Tx) are not loaded, pad_val is stored in their place; every other piece as without LEN.
+template <bool RAW, int D4C, bool LEN = false>    // D4C: 16-byte pieces per row when known at compile time (50: W = 200), 0 = read D4
 __global__ __launch_bounds__(kAugThreads) void window_stream_kernel(const float* __restrict__ x, const float* __restrict__ y, int N, int Tx,
                                                                     int Ty, int D4, const int* __restrict__ perm, const float* __restrict__ a,
                                                                     const float* __restrict__ c, float mean, float std_,
-                                                                    float* __restrict__ x_out, float* __restrict__ y_out) {
+                                                                    float* __restrict__ x_out, float* __restrict__ y_out,
+                                                                    const long long* __restrict__ lengths, float pad_val) {
     const int d4 = D4C > 0 ? D4C : D4, b = blockIdx.x;
+    unsigned tv = (unsigned)Tx;
+    if constexpr (LEN) tv = (unsigned)clip_steps(lengths, b, Tx);
+    bool pad[kAugUnroll];
     const unsigned rows_x = (unsigned)Tx * N, total = (rows_x + (unsigned)Ty * N) * d4;
     const float ab = a != nullptr ? a[b] : 1.0f, cb = (!RAW && c != nullptr) ? c[b] : 0.0f;
     const unsigned e0 = blockIdx.y * (unsigned)kAugPerBlock + threadIdx.x;
@@ -356,6 +426,8 @@ __global__ __launch_bounds__(kAugThreads) void window_stream_kernel(const float*
         const int src = perm_source(perm, b, N, (int)nd);
         const size_t clip = (size_t)b * T * N;
         dst[u] = ((clip + row) * d4 + p) * 4;
+        pad[u] = LEN && t >= tv;
+        if (pad[u]) { v[u] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
         const size_t from = RAW ? (((size_t)b * N + src) * T + t) : (clip + (size_t)t * N + src);
         v[u] = *reinterpret_cast<const f32x4*>((in_y[u] ? y : x) + (from * d4 + p) * 4);
     }
@@ -364,7 +436,7 @@ __global__ __launch_bounds__(kAugThreads) void window_stream_kernel(const float*
         if (!on[u]) continue;
         f32x4 o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = RAW ? __builtin_fmaf(v[u][k], ab, -mean) / std_ : unfused_mul_add(v[u][k], ab, cb);
+        for (int k = 0; k < 4; ++k) o[k] = (LEN && pad[u]) ? pad_val : RAW ? __builtin_fmaf(v[u][k], ab, -mean) / std_ : unfused_mul_add(v[u][k], ab, cb);
         *reinterpret_cast<f32x4*>((in_y[u] ? y_out : x_out) + dst[u]) = o;
     }
 }

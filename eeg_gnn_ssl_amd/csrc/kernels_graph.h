@@ -98,9 +98,13 @@ __device__ __forceinline__ void gram_write_partial(GramAcc& a, float* sm, int wa
 // cost of a 16x16x4): A operand = X[16 + (lane & 3)][k], B operand = the tile-0 fragment (-> rows 16.. x cols 0..15) or
 // the same A register (-> rows 16.. x cols 16..); every lane group then holds the partial sum of ITS k quarter, and
 // the four are added once, at the end, in a fixed order.
-template <int NQ, bool REM4>
+// LEN (variable-length clips: dataloader_classification.py:356-361 builds the graph of the UNPADDED clip): every wave walks its share
+// of the steps t < clip_steps(lengths, b, T) of its own clip; T stays the stride between clips.  A wave without a step hands over a
+// zero partial, so corr_finish_kernel sums the same NS partials.
+template <int NQ, bool REM4, bool LEN = false>
 __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict__ X, int T, int N, int D,
-                                                        float* __restrict__ part, int step_floats) {
+                                                        float* __restrict__ part, int step_floats,
+                                                        const long long* __restrict__ lengths) {
     EEG_DYN_SMEM(sm);                          // [4 waves][step_floats] staging | reused as [4 waves][kGramFloats] at the end
     const int lane = threadIdx.x & 63, wave = wave_uniform(threadIdx.x >> 6), i = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, sp = blockIdx.y, NS = gridDim.y;
@@ -120,8 +124,10 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
     };
     const int r0 = (has0 ? i : 0) * D, r1 = (has1 ? i1 : 0) * D;
     const int t0 = sp * 4 + wave, dt = 4 * NS;
-    if (t0 < T) stage(t0);
-    for (int t = t0; t < T; t += dt) {
+    int Tv = T;                                            // steps of this clip that enter the Gram
+    if constexpr (LEN) Tv = clip_steps(lengths, b, T);
+    if (t0 < Tv) stage(t0);
+    for (int t = t0; t < Tv; t += dt) {
         float4 a0[NQ], a1[NQ];
         EEG_WAVE_SYNC();                                    // every lane's pieces of the step have been requested
 #pragma unroll
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
         // waiting when the next step's data -- L2-hot, through the texture path -- landed in the buffer.
         EEG_LDS_WAIT();
         EEG_WAVE_SYNC();
-        if (t + dt < T) stage(t + dt);                      // next step of this wave: flies during the MFMAs below
+        if (t + dt < Tv) stage(t + dt);                     // next step of this wave: flies during the MFMAs below
 #pragma unroll
         for (int q = 0; q < NQ; ++q) gram_mma<REM4>(acc, a0[q], a1[q]);
     }
@@ -159,9 +165,13 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
 // Same pipeline as corr_gram_kernel: fragments to registers, then the next chunk's DMA flies during the MFMAs; same partial-Gram
 // layout, so corr_finish_kernel serves both.  Fixed chunk -> wave assignment, fixed order: bit-reproducible.
 constexpr int kRowChunk = 256, kRowQuads = kRowChunk / 16;
-template <bool REM4>
+// LEN (variable-length clips, dataloader_classification.py:356-361): the valid extent of a row is separate from its stride.  Raw rows
+// (P = 1, unit = samples per step): the first clip_steps(lengths, b, Q / unit) * unit floats of every row, the row stride stays Q and
+// the ragged last chunk is masked as above; window tensors (unit = 0): the first clip_steps(lengths, b, P) pieces.
+template <bool REM4, bool LEN = false>
 __global__ __launch_bounds__(256) void corr_gram_rows_kernel(const float* __restrict__ X, int N, int P, int Q, unsigned pstride,
-                                                             unsigned clip_floats, float* __restrict__ part, int tile_floats) {
+                                                             unsigned clip_floats, float* __restrict__ part, int tile_floats,
+                                                             const long long* __restrict__ lengths, int unit) {
     EEG_DYN_SMEM(sm);                          // [4 waves][tile_floats] staging | reused as [4 waves][kGramFloats] at the end
     const int lane = threadIdx.x & 63, wave = wave_uniform(threadIdx.x >> 6), i = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, sp = blockIdx.y, NS = gridDim.y;
@@ -170,14 +180,19 @@ __global__ __launch_bounds__(256) void corr_gram_rows_kernel(const float* __rest
     const bool has0 = i < N, has1 = i1 < N;
     float* buf = sm + wave * tile_floats;
     const wbuf_t clip = make_wbuf_n(X + (size_t)b * clip_floats, clip_floats * 4u);
-    const int cpp = ceil_div(Q, kRowChunk), nchunks = P * cpp;          // chunks per piece, per clip
+    int Pv = P, Qv = Q;                                                  // valid pieces, valid floats of a piece (Q: the row stride)
+    if constexpr (LEN) {
+        if (unit > 0) Qv = clip_steps(lengths, b, Q / unit) * unit;
+        else Pv = clip_steps(lengths, b, P);
+    }
+    const int cpp = ceil_div(Qv, kRowChunk), nchunks = Pv * cpp;        // chunks per piece, per clip
     auto stage = [&](int k) {
         const int p = k / cpp, q0 = (k - p * cpp) * kRowChunk;
         const unsigned base = (unsigned)p * pstride;
         for (int n = 0; n < N; ++n) {
             const int q = q0 + 4 * (lane ^ (n & 15));
             // (host: clip bytes < 2^31, so 0x80000000 lies outside every descriptor)
-            wbuf_dma16(clip, buf + n * kRowChunk, q < Q ? (base + (unsigned)(n * Q + q)) * 4u : 0x80000000u, 0u);
+            wbuf_dma16(clip, buf + n * kRowChunk, q < Qv ? (base + (unsigned)(n * Q + q)) * 4u : 0x80000000u, 0u);
         }
     };
     const int n0 = has0 ? i : 0, n1 = has1 ? i1 : 0;
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(256) void corr_gram_rows_kernel(const float* __rest
     const int k0 = sp * 4 + wave, dk = 4 * NS;
     if (k0 < nchunks) stage(k0);
     for (int k = k0; k < nchunks; k += dk) {
-        const int q0 = (k % cpp) * kRowChunk, valid = Q - q0 < kRowChunk ? Q - q0 : kRowChunk;          // wave-uniform
+        const int q0 = (k % cpp) * kRowChunk, valid = Qv - q0 < kRowChunk ? Qv - q0 : kRowChunk;        // wave-uniform
         float4 a0[kRowQuads], a1[kRowQuads];
         EEG_WAVE_SYNC();                                    // every lane's pieces of the chunk have been requested
         EEG_VM_WAIT(0);                                     // ... and have landed (this wave's only vector-memory traffic)

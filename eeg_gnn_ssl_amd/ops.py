@@ -11,7 +11,7 @@ dispatcher's "no kernel for the CPU backend" error, and the C-ABI stub refuses n
 Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
-    fft_features, fft_features_pair, augment_features, window_features, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
+    fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
@@ -103,6 +103,15 @@ def _check_polys(p: torch.Tensor, p_batched: int, b: int, n: int, m: int, what: 
 def _check_lengths(lengths: torch.Tensor, b: int):
     if lengths.numel() != b:
         raise RuntimeError(f"seq_lengths has {lengths.numel()} entries for a batch of {b}")
+
+
+def _clip_lengths(what: str, lengths: torch.Tensor, b: int, ref: torch.Tensor):
+    """`lengths` of the length-aware data-side operators: read by the kernels ON THE DEVICE, so no conversion happens here -- anything
+    but an int64 (B,) tensor on the device of the clips is refused"""
+    if lengths.dtype != torch.int64 or tuple(lengths.shape) != (b,) or lengths.device != ref.device:
+        raise RuntimeError(f"{what}: lengths must be an int64 tensor of shape ({b},) on {ref.device} (valid steps per clip, read on the "
+                           f"device), got {lengths.dtype} {tuple(lengths.shape)} on {lengths.device}")
+    return lengths.contiguous()
 
 
 def _new(shape, like: torch.Tensor, dtype=torch.float32):
@@ -1050,24 +1059,32 @@ _define("gather_last", "(Tensor htop, Tensor lengths) -> Tensor", _gather_last_i
         lambda htop, lengths: htop.new_empty((htop.shape[1], htop.shape[2])))
 
 
-def _corr_graph_impl(x, top_k: int):
+def _corr_graph_impl(x, top_k: int, lengths=None):
     lib = _lib.get_lib()
     x = x.contiguous()
     _check(lib, x, "clips")
     if x.dim() != 4:
         raise RuntimeError(f"clips must be (B,T,N,D), got {tuple(x.shape)}")
     b, t_len, n, d = x.shape
+    if lengths is not None:
+        lengths = _clip_lengths("corr_graph_len", lengths, b, x)
     adj, s1, s2 = (_new((b, n, n), x) for _ in range(3))
     ws = _new((lib.query("eeg_dcrnn_corr_graph_ws_floats", b, t_len),), x)
-    lib.call("eeg_dcrnn_corr_graph", _p(x), b, t_len, n, d, int(top_k), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
+    if lengths is None:
+        lib.call("eeg_dcrnn_corr_graph", _p(x), b, t_len, n, d, int(top_k), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
+    else:
+        lib.call("eeg_dcrnn_corr_graph_len", _p(x), b, t_len, n, d, int(top_k), _p(lengths), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
     return adj, s1, s2
 
 
 _define("corr_graph", "(Tensor x, int top_k) -> (Tensor adj, Tensor s1, Tensor s2)", _corr_graph_impl,
         lambda x, top_k: tuple(x.new_empty((x.shape[0], x.shape[2], x.shape[2])) for _ in range(3)))
+# the graph of the UNPADDED clips (dataloader_classification.py:356-361): steps t >= lengths[b] of clip b do not enter the Gram
+_define("corr_graph_len", "(Tensor x, int top_k, Tensor lengths) -> (Tensor adj, Tensor s1, Tensor s2)", _corr_graph_impl,
+        lambda x, top_k, lengths: tuple(x.new_empty((x.shape[0], x.shape[2], x.shape[2])) for _ in range(3)))
 
 
-def _fft_features_impl(raw, window: int, mean: float, std: float, standardise: bool, perm, log_scale):
+def _fft_features_impl(raw, window: int, mean: float, std: float, standardise: bool, perm, log_scale, lengths=None, padding_val: float = 0.0):
     lib = _lib.get_lib()
     raw = raw.contiguous()
     _check(lib, raw, "raw signals")
@@ -1091,8 +1108,13 @@ def _fft_features_impl(raw, window: int, mean: float, std: float, standardise: b
         raise RuntimeError(f"fft_features: log_scale has {log_scale.numel()} entries for {b} clips")
     if log_scale is not None:
         log_scale = log_scale.to(device=raw.device, dtype=torch.float32).contiguous()
-    lib.call("eeg_dcrnn_fft_features", _p(raw), b, n, t_len, window, _p(perm), _p(log_scale), float(mean), float(std),
-             _p(feat_raw), _p(feat_std) if standardise else None, _stream(raw))
+    if lengths is None:
+        lib.call("eeg_dcrnn_fft_features", _p(raw), b, n, t_len, window, _p(perm), _p(log_scale), float(mean), float(std),
+                 _p(feat_raw), _p(feat_std) if standardise else None, _stream(raw))
+    else:
+        lengths = _clip_lengths("fft_features_len", lengths, b, raw)
+        lib.call("eeg_dcrnn_fft_features_len", _p(raw), b, n, t_len, window, _p(perm), _p(log_scale), float(mean), float(std), _p(lengths),
+                 float(padding_val), _p(feat_raw), _p(feat_std) if standardise else None, _stream(raw))
     return feat_raw, feat_std
 
 
@@ -1103,6 +1125,11 @@ def _fft_features_fake(raw, window, mean, std, standardise, perm, log_scale):
 
 _define("fft_features", "(Tensor raw, int window, float mean, float std, bool standardise, Tensor? perm, Tensor? log_scale) -> (Tensor, Tensor)",
         _fft_features_impl, _fft_features_fake)
+# variable-length clips (dataloader_classification.py:25-85,321-343): windows t >= lengths[b] are not transformed
+_define("fft_features_len", "(Tensor raw, int window, float mean, float std, bool standardise, Tensor? perm, Tensor? log_scale, Tensor lengths, "
+        "float padding_val) -> (Tensor, Tensor)", _fft_features_impl,
+        lambda raw, window, mean, std, standardise, perm, log_scale, lengths, padding_val: _fft_features_fake(raw, window, mean, std, standardise, perm,
+                                                                                                              log_scale))
 
 
 def _check_draws(what, perm, log_scale, b, n, ref, permutation=False):
@@ -1199,7 +1226,7 @@ def _raw_windows(what, raw, window, name, like=None):
     return raw.shape[0], raw.shape[1], raw.shape[2] // window
 
 
-def _window_features_impl(raw, window: int, mean: float, std: float, perm, scale):
+def _window_features_impl(raw, window: int, mean: float, std: float, perm, scale, lengths=None, padding_val: float = 0.0):
     lib = _lib.get_lib()
     raw = raw.contiguous()
     _check(lib, raw, "raw signals")
@@ -1209,12 +1236,20 @@ def _window_features_impl(raw, window: int, mean: float, std: float, perm, scale
     perm, _ = _check_draws("window_features", perm, None, b, n, raw)
     scale = _check_scale("window_features", scale, b, raw)
     out = _new((b, t_len, n, window), raw)
-    lib.call("eeg_dcrnn_window_features", _p(raw), b, n, t_len, int(window), _p(perm), _p(scale), float(mean), float(std), _p(out), _stream(raw))
+    if lengths is None:
+        lib.call("eeg_dcrnn_window_features", _p(raw), b, n, t_len, int(window), _p(perm), _p(scale), float(mean), float(std), _p(out), _stream(raw))
+    else:
+        lengths = _clip_lengths("window_features_len", lengths, b, raw)
+        lib.call("eeg_dcrnn_window_features_len", _p(raw), b, n, t_len, int(window), _p(perm), _p(scale), float(mean), float(std), _p(lengths),
+                 float(padding_val), _p(out), _stream(raw))
     return out
 
 
 _define("window_features", "(Tensor raw, int window, float mean, float std, Tensor? perm, Tensor? scale) -> Tensor", _window_features_impl,
         lambda raw, window, mean, std, perm, scale: raw.new_empty((raw.shape[0], raw.shape[2] // window, raw.shape[1], window)))
+_define("window_features_len", "(Tensor raw, int window, float mean, float std, Tensor? perm, Tensor? scale, Tensor lengths, float padding_val) -> Tensor",
+        _window_features_impl,
+        lambda raw, window, mean, std, perm, scale, lengths, padding_val: raw.new_empty((raw.shape[0], raw.shape[2] // window, raw.shape[1], window)))
 
 
 def _window_features_pair_impl(raw_x, raw_y, window: int, mean: float, std: float, perm, scale):
@@ -1274,8 +1309,9 @@ _define("augment_windows", "(Tensor x, Tensor? y, Tensor perm, Tensor scale, flo
         lambda x, y, perm, scale, mean, std: (torch.empty_like(x), torch.empty_like(y) if y is not None else x.new_empty((0,))))
 
 
-def _corr_graph_rows_impl(x, top_k: int):
-    """x (B, N, L) raw channel rows, or (B, T, N, D) windows whose channel rows are the T pieces of D samples"""
+def _corr_graph_rows_impl(x, top_k: int, lengths=None, steps: int = 0):
+    """x (B, N, L) raw channel rows, or (B, T, N, D) windows whose channel rows are the T pieces of D samples; with lengths, `steps`
+    = the steps of a full clip (raw rows: L = steps * samples per step; windows: T)"""
     lib = _lib.get_lib()
     x = x.contiguous()
     _check(lib, x, "clips")
@@ -1292,7 +1328,12 @@ def _corr_graph_rows_impl(x, top_k: int):
         raise RuntimeError(f"corr_graph_rows: empty batch/clip {tuple(x.shape)}")
     adj, s1, s2 = (_new((b, n, n), x) for _ in range(3))
     ws = _new((lib.query("eeg_dcrnn_corr_graph_rows_ws_floats", b, p, q),), x)
-    lib.call("eeg_dcrnn_corr_graph_rows", _p(x), b, n, p, q, stride, int(top_k), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
+    if lengths is None:
+        lib.call("eeg_dcrnn_corr_graph_rows", _p(x), b, n, p, q, stride, int(top_k), _p(adj), _p(s1), _p(s2), _p(ws), _stream(x))
+    else:
+        lengths = _clip_lengths("corr_graph_rows_len", lengths, b, x)
+        lib.call("eeg_dcrnn_corr_graph_rows_len", _p(x), b, n, p, q, stride, int(top_k), _p(lengths), int(steps), _p(adj), _p(s1), _p(s2), _p(ws),
+                 _stream(x))
     return adj, s1, s2
 
 
@@ -1302,6 +1343,8 @@ def _corr_graph_rows_fake(x, top_k):
 
 
 _define("corr_graph_rows", "(Tensor x, int top_k) -> (Tensor adj, Tensor s1, Tensor s2)", _corr_graph_rows_impl, _corr_graph_rows_fake)
+_define("corr_graph_rows_len", "(Tensor x, int top_k, Tensor lengths, int steps) -> (Tensor adj, Tensor s1, Tensor s2)", _corr_graph_rows_impl,
+        lambda x, top_k, lengths, steps: _corr_graph_rows_fake(x, top_k))
 
 
 # =============================================================================================
@@ -1531,15 +1574,26 @@ def collapse_shared_supports(supports):
 
 
 def fft_features(raw: torch.Tensor, window: int = 200, mean: Optional[float] = None, std: Optional[float] = None,
-                 perm: Optional[torch.Tensor] = None, log_scale: Optional[torch.Tensor] = None):
+                 perm: Optional[torch.Tensor] = None, log_scale: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+                 padding_val: float = 0.0):
     """Input featurisation on the device: raw (B,N,T*window) resampled signals ->
     (feat_raw (B,T,N,window/2) log|FFT| per 1-s step, feat_std = the standardised (and optionally
     augmented) model input or None when mean/std are not given).
 
     Replaces `computeFFT` per step (data_utils.py:13-35, dataloader_detection.py:57-71), the reflection /
     amplitude-jitter augmentation (perm (B,N) int32 source channel per node, log_scale (B);
-    dataloader_detection.py:233-256) and `StandardScaler.transform` (utils.py:393-428)."""
+    dataloader_detection.py:233-256) and `StandardScaler.transform` (utils.py:393-428).
+
+    lengths (B,) int64 on the device of `raw`: variable-length clips (dataloader_classification.py:25-85,321-343: the short clip is
+    augmented and standardised, then padded with `padding_val`).  Clip b has clamp(lengths[b], 1, T) valid windows; the windows
+    behind them are not transformed -- feat_std holds `padding_val` there and feat_raw 0 -- and the valid ones are bit-identical
+    to the call without lengths.  The kernel reads the lengths: no host synchronisation, a captured call replays with new ones."""
     std_on = mean is not None
+    if lengths is not None:
+        _clip_lengths("fft_features", lengths, raw.shape[0], raw)
+        fr, fs = torch.ops.eeg_dcrnn.fft_features_len(raw, int(window), float(mean) if std_on else 0.0, float(std) if std is not None else 1.0,
+                                                      std_on, perm, log_scale, lengths, float(padding_val))
+        return fr, (fs if std_on else None)
     fr, fs = torch.ops.eeg_dcrnn.fft_features(raw, int(window), float(mean) if std_on else 0.0,
                                               float(std) if std is not None else 1.0, std_on, perm, log_scale)
     return fr, (fs if std_on else None)
@@ -1560,12 +1614,17 @@ def fft_features_pair(raw_x: torch.Tensor, raw_y: torch.Tensor, window: int = 20
 
 
 def window_features(raw: torch.Tensor, window: int, mean: float, std: float, perm: Optional[torch.Tensor] = None,
-                    scale: Optional[torch.Tensor] = None):
+                    scale: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, padding_val: float = 0.0):
     """Time-domain input of the model on the device (the reference without --use_fft): raw (B,N,T*window) resampled signals ->
     (B,T,N,window) = (raw[b, perm[b][n], t*window ..] * scale[b] - mean) / std: the windowing of `computeSliceMatrix(is_fft=False)`
     (dataloader_detection.py:25-85), `_random_reflect` / `_random_scale` (`EEG_seq *= scale_factor`, :233-256) and
     `StandardScaler.transform` (utils.py:393-428) in one pass.  perm (B,N) int32 source channel per node, scale (B) the clip's
-    amplitude factor; None = no reflection / factor 1.  Forward-only."""
+    amplitude factor; None = no reflection / factor 1.  Forward-only.
+    lengths (B,) int64 on the device of `raw` (dataloader_classification.py:25-85,321-343): the steps t >= clamp(lengths[b], 1, T) of
+    clip b are not read and hold `padding_val`; every other value is bit-identical to the call without lengths."""
+    if lengths is not None:
+        _clip_lengths("window_features", lengths, raw.shape[0], raw)
+        return torch.ops.eeg_dcrnn.window_features_len(raw, int(window), float(mean), float(std), perm, scale, lengths, float(padding_val))
     return torch.ops.eeg_dcrnn.window_features(raw, int(window), float(mean), float(std), perm, scale)
 
 
@@ -1595,23 +1654,42 @@ def augment_features(x: torch.Tensor, y: torch.Tensor, perm: torch.Tensor, log_s
     return torch.ops.eeg_dcrnn.augment_features(x, y, perm, log_scale, float(feature_std))
 
 
-def correlation_supports(x: torch.Tensor, top_k: int = 3, return_adj: bool = False):
+def correlation_supports(x: torch.Tensor, top_k: int = 3, return_adj: bool = False, lengths: Optional[torch.Tensor] = None):
     """Per-clip correlation graph -> [S1, S2] dual random-walk supports, on the device.
 
     x (B,T,N,D) clips (the model input); D <= 128 (features) runs the kernel that stages whole time steps, a wider D (time-domain
     windows, D = 200) the kernel for wide channel rows.  Replaces the DataLoader-side `_get_indiv_graphs` +
     `keep_topk` + `_compute_supports('dual_random_walk')` (dataloader_detection.py:258-307,335-354).
+    lengths (B,) int64 on the device of x: the graph of the UNPADDED clips (dataloader_classification.py:356-361) -- only the steps
+    t < clamp(lengths[b], 1, T) of clip b enter it, whatever the padded steps hold.
     Returns [S1 (B,N,N), S2 (B,N,N)] (and the sparsified adjacency (B,N,N) if return_adj)."""
-    adj, s1, s2 = (torch.ops.eeg_dcrnn.corr_graph_rows if x.dim() == 4 and x.shape[3] > 128 else torch.ops.eeg_dcrnn.corr_graph)(x, int(top_k))
+    wide = x.dim() == 4 and x.shape[3] > 128
+    if lengths is not None:
+        _clip_lengths("correlation_supports", lengths, x.shape[0], x)
+        adj, s1, s2 = (torch.ops.eeg_dcrnn.corr_graph_rows_len(x, int(top_k), lengths, int(x.shape[1])) if wide
+                       else torch.ops.eeg_dcrnn.corr_graph_len(x, int(top_k), lengths))
+        return ([s1, s2], adj) if return_adj else [s1, s2]
+    adj, s1, s2 = (torch.ops.eeg_dcrnn.corr_graph_rows if wide else torch.ops.eeg_dcrnn.corr_graph)(x, int(top_k))
     return ([s1, s2], adj) if return_adj else [s1, s2]
 
 
-def correlation_supports_raw(raw: torch.Tensor, top_k: int = 3, return_adj: bool = False):
+def correlation_supports_raw(raw: torch.Tensor, top_k: int = 3, return_adj: bool = False, lengths: Optional[torch.Tensor] = None,
+                             window: int = 200):
     """The same graph for a time-domain clip, from its raw signals: raw (B,N,L) channel rows, L a multiple of 4 (the clip of
     `computeSliceMatrix(is_fft=False)` reshaped by `_get_indiv_graphs` to (N, T*200) is these rows again; dataloader_detection.py:
-    25-85,258-307).  Returns [S1 (B,N,N), S2 (B,N,N)] (and the sparsified adjacency if return_adj)."""
+    25-85,258-307).  Returns [S1 (B,N,N), S2 (B,N,N)] (and the sparsified adjacency if return_adj).
+    lengths (B,) int64 on the device of raw: clips of L / window steps of `window` samples (a multiple of 4) of which clip b has
+    clamp(lengths[b], 1, L / window) -- the graph of its first lengths[b] * window samples per row (dataloader_classification.py:
+    356-361: the unpadded clip); `window` is read only then."""
     if raw.dim() != 3:
         raise RuntimeError(f"raw signals must be (B, N, L) channel rows, got {tuple(raw.shape)}")
+    if lengths is not None:
+        if window < 4 or window % 4 != 0 or raw.shape[2] % window != 0 or raw.shape[2] == 0:
+            raise RuntimeError(f"correlation_supports_raw: rows of {raw.shape[2]} samples are not whole steps of window={window} samples "
+                               f"(a positive multiple of 4)")
+        _clip_lengths("correlation_supports_raw", lengths, raw.shape[0], raw)
+        adj, s1, s2 = torch.ops.eeg_dcrnn.corr_graph_rows_len(raw, int(top_k), lengths, int(raw.shape[2] // window))
+        return ([s1, s2], adj) if return_adj else [s1, s2]
     adj, s1, s2 = torch.ops.eeg_dcrnn.corr_graph_rows(raw, int(top_k))
     return ([s1, s2], adj) if return_adj else [s1, s2]
 

@@ -58,7 +58,8 @@ class TrainStep:
                  scaler_mean: Optional[float] = None, scaler_std: Optional[float] = None,
                  always_reduce: bool = False, raw_window: Optional[int] = None, raw_mean: float = 0.0, raw_std: float = 1.0,
                  shared_graph: bool = True, data_augment: bool = False, swap_perm=None, reflected_supports=None,
-                 feature_std: Optional[float] = None, use_fft: bool = True, feature_mean: Optional[float] = None):
+                 feature_std: Optional[float] = None, use_fft: bool = True, feature_mean: Optional[float] = None,
+                 padding_val: Optional[float] = None):
         """shared_graph: batched supports whose clips all carry one and the same graph (the reference's trainers pass the distance
         graph that way) are handed to the model in their 2-D form, which lets the encoder run its hoisted GEMMs in the
         eigenbasis of that graph (`ops.collapse_shared_supports`: one comparison + one flag read per supports TENSOR, cached; a
@@ -94,8 +95,19 @@ class TrainStep:
         raw_window: the step takes RAW resampled signals (B, N, T*raw_window) instead of features and runs the reference's
         DataLoader-side chain on the device in front of the model (dataloader_detection.py:57-71,346-354,384-393): log|FFT| of every
         raw_window-sample step (`eeg_dcrnn_fft_features`) -> z-score with (raw_mean, raw_std) = the model input; with
-        supports=None the per-clip correlation graph is built from the UN-standardised features, as `_get_indiv_graphs` does."""
+        supports=None the per-clip correlation graph is built from the UN-standardised features, as `_get_indiv_graphs` does.
+        padding_val: variable-length clips, the classification loader (dataloader_classification.py:25-85,321-343,356-361: a clip of
+        curr_len <= max_seq_len steps is augmented and standardised, THEN padded with `padding_val`, and its correlation graph is that
+        of the unpadded, un-augmented clip).  None: every clip is taken at full length, as before.  A number, with `seq_lengths` at
+        `step` / `forward_backward` / `capture` (int64, read on the device: a captured step replays with refilled lengths): with
+        raw_window the steps t >= seq_lengths[b] of clip b are not featurised / windowed and the model input holds `padding_val`
+        there (whatever the raw signals hold behind the clip); with supports=None the graph is built from the first seq_lengths[b]
+        steps only -- of the un-augmented features, raw rows or windows.  Feature or ready-window inputs are taken as given (the
+        caller padded them): only that graph changes.  seq_lengths=None: full length.  Not for task="ssl" (no lengths there)."""
         assert task in ("detection", "classification", "ssl")
+        if padding_val is not None and task == "ssl":
+            raise ValueError("TrainStep: padding_val (variable-length clips) is for the supervised tasks; the SSL pair has no seq_lengths")
+        self.padding_val = None if padding_val is None else float(padding_val)
         self.model, self.task, self.max_grad_norm = model, task, max_grad_norm
         self.fp = FlatParameters(model)
         # optimiser state lives in flat buffers; the update is ONE fused HIP kernel (clip + Adam)
@@ -234,23 +246,28 @@ class TrainStep:
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
             supports, perm, log_scale = self._draw_augmentation(x.shape[0], supports)
+        # variable-length clips: the data side stops at the clip's own length (None: every step, the calls below as they always were)
+        lens, pad = None, 0.0
+        if self.padding_val is not None and seq_lengths is not None:
+            lens, pad = seq_lengths.to(device=x.device, dtype=torch.int64), self.padding_val
         if not self.use_fft:
-            x, y, supports = self._time_domain_inputs(x, y, supports, perm, log_scale)
+            x, y, supports = self._time_domain_inputs(x, y, supports, perm, log_scale, lens, pad)
         elif self.task == "ssl" and (self.raw_window is not None or perm is not None):
             # the SSL sample is a pair: the target takes the clip's draws and the scaler like the input (dataloader_ssl.py:317-341)
             x, y, supports = self._ssl_pair(x, y, supports, perm, log_scale)
         elif self.raw_window is not None:            # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
-            feat_raw, x = ops.fft_features(x, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm, log_scale=log_scale)
+            feat_raw, x = ops.fft_features(x, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm, log_scale=log_scale,
+                                           lengths=lens, padding_val=pad)
             if supports is None:
-                supports = ops.correlation_supports(feat_raw, top_k=3)       # (feat_raw: un-reflected, un-scaled, un-standardised)
+                supports = ops.correlation_supports(feat_raw, top_k=3, lengths=lens)   # (feat_raw: un-reflected, un-scaled, un-standardised)
         elif perm is not None:
             plain = x
             idx = perm.to(torch.int64)[:, None, :, None].expand(-1, x.shape[1], -1, x.shape[3])
             x = x.gather(2, idx) + (log_scale / self.feature_std)[:, None, None, None]
             if supports is None:
-                supports = ops.correlation_supports(plain, top_k=3)
+                supports = ops.correlation_supports(plain, top_k=3, lengths=lens)
         if supports is None:
-            supports = ops.correlation_supports(x, top_k=3)
+            supports = ops.correlation_supports(x, top_k=3, lengths=lens)
         elif self.shared_graph:
             supports = ops.collapse_shared_supports(supports)
         if self.task == "ssl":
@@ -306,10 +323,11 @@ class TrainStep:
             supports = ops.correlation_supports(plain, top_k=3)
         return x, y, supports
 
-    def _time_domain_inputs(self, x, y, supports, perm, log_scale):
+    def _time_domain_inputs(self, x, y, supports, perm, log_scale, lens=None, pad=0.0):
         """data side of a use_fft=False step (dataloader_detection.py:25-85,233-256,384-393; dataloader_ssl.py:317-355): (model
         input, target, supports) with this step's draws (or none) -- on BOTH halves of an SSL pair; the correlation graph comes
-        from the un-reflected, un-scaled INPUT clip"""
+        from the un-reflected, un-scaled INPUT clip.  lens (supervised tasks): the clips' valid steps -- raw signals are windowed up
+        to them and padded with `pad` behind, and the graph is that of the unpadded clip (dataloader_classification.py:321-361)"""
         scale = None
         if log_scale is not None:
             scale = torch.exp(log_scale)             # B floats, a framework op (capturable): `EEG_seq *= scale_factor`
@@ -324,15 +342,15 @@ class TrainStep:
                                      f"{self.raw_window}) with the input's {x.shape[0]} clips and {x.shape[1]} nodes, got {tuple(y.shape)}")
                 x, y = ops.window_features_pair(x, y, self.raw_window, self.raw_mean, self.raw_std, perm=perm, scale=scale)
             else:
-                x = ops.window_features(x, self.raw_window, self.raw_mean, self.raw_std, perm=perm, scale=scale)
+                x = ops.window_features(x, self.raw_window, self.raw_mean, self.raw_std, perm=perm, scale=scale, lengths=lens, padding_val=pad)
             if supports is None:
-                supports = ops.correlation_supports_raw(raw, top_k=3)
+                supports = ops.correlation_supports_raw(raw, top_k=3, lengths=lens, window=self.raw_window)
         elif perm is not None:
             plain = x
             x, ya = ops.augment_windows(x, y if pair else None, perm, scale, self.feature_mean, self.feature_std)
             y = ya if pair else y
             if supports is None:
-                supports = ops.correlation_supports(plain, top_k=3)
+                supports = ops.correlation_supports(plain, top_k=3, lengths=lens)
         return x, y, supports
 
     def _draw_augmentation(self, batch, supports):

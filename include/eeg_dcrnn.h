@@ -105,6 +105,15 @@ int eeg_dcrnn_fft_features(const float* raw, int B, int N, int T, int W, const i
                            const float* log_scale, float mean, float std_, float* feat_raw,
                            float* feat_std, void* stream);
 
+/* Variable-length clips (the classification loader: dataloader_classification.py:25-85 cuts a clip of curr_len <= max_seq_len
+ * steps, :321-343 augments and standardises the short clip and THEN pads it to max_seq_len with padding_val; :356-361 builds the
+ * correlation graph of the unpadded clip).  eeg_dcrnn_fft_features with lengths (B) int64 ON THE DEVICE (read by the kernel: the
+ * launch does not depend on them, a captured launch replays with new lengths): clip b has len_b = clamp(lengths[b], 1, T) valid
+ * windows.  A window (b, n, t >= len_b) is not transformed: its feat_std row is pad_val, its feat_raw row 0 (a zero row adds nothing
+ * to a Gram).  Valid windows are bit-identical to eeg_dcrnn_fft_features; W = 200 skips the padding six windows at a time. */
+int eeg_dcrnn_fft_features_len(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* log_scale, float mean,
+                               float std_, const int64_t* lengths, float pad_val, float* feat_raw, float* feat_std, void* stream);
+
 /* The data side of the SSL sample, which is a PAIR (dataloader_ssl.py:317-341): 60 s of input and the first seconds of the
  * following clip as target; ONE coin and ONE scale factor per sample (`_random_reflect(…, reflect)` / `_random_scale(…,
  * scale_factor)`, dataloader_ssl.py:159-182) applied to both halves, then the StandardScaler on both.  raw_x (B,N,Tx*W),
@@ -136,6 +145,12 @@ int eeg_dcrnn_augment_features(const float* x, const float* y, int B, int Tx, in
 int eeg_dcrnn_window_features(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* scale, float mean,
                               float std_, float* x_std, void* stream);
 
+/* eeg_dcrnn_window_features for variable-length clips (dataloader_classification.py:25-85,321-343: the short clip is scaled and
+ * standardised, then padded): lengths (B) int64 on the device, len_b = clamp(lengths[b], 1, T); the steps t >= len_b of clip b are
+ * not loaded and x_std holds pad_val there; every other value is bit-identical to eeg_dcrnn_window_features. */
+int eeg_dcrnn_window_features_len(const float* raw, int B, int N, int T, int W, const int32_t* perm, const float* scale, float mean,
+                                  float std_, const int64_t* lengths, float pad_val, float* x_std, void* stream);
+
 /* The same for the SSL pair (dataloader_ssl.py:159-182,317-341: one coin and one scale factor per sample on input AND target, the
  * scaler on both): raw_x (B,N,Tx*W), raw_y (B,N,Ty*W) -> x_std (B,Tx,N,W), y_std (B,Ty,N,W) in ONE launch; every output is
  * bit-identical to eeg_dcrnn_window_features on that half. */
@@ -160,6 +175,12 @@ size_t eeg_dcrnn_corr_graph_ws_floats(int B, int T);
 int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, float* adj, float* S1,
                          float* S2, float* ws, void* stream);
 
+/* The graph of the UNPADDED clip (dataloader_classification.py:356-361 on the clip of :25-85): only the steps t < len_b =
+ * clamp(lengths[b], 1, T) of clip b enter the Gram, whatever the padded steps hold; lengths (B) int64 on the device.
+ * ws: eeg_dcrnn_corr_graph_ws_floats(B, T) floats, as for eeg_dcrnn_corr_graph. */
+int eeg_dcrnn_corr_graph_len(const float* X, int B, int T, int N, int D, int top_k, const int64_t* lengths, float* adj, float* S1,
+                             float* S2, float* ws, void* stream);
+
 /* The same graph from WIDE channel rows (time-domain clips: dataloader_detection.py:258-307 on a clip of :25-85, whose
  * `eeg_clip.reshape((num_sensors, -1))` is the raw (N, T*200) rows again).  The row of node n of clip b is P pieces of Q floats,
  * piece p at X[b*clip + p*piece_stride + n*Q ..]: raw rows (B,N,L) are P = 1, Q = L (piece_stride ignored); a window tensor
@@ -169,6 +190,13 @@ int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, 
 size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q);
 int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1,
                               float* S2, float* ws, void* stream);
+
+/* eeg_dcrnn_corr_graph_rows of the UNPADDED clip (dataloader_classification.py:356-361 on a time-domain clip of :25-85): `steps` =
+ * the steps of a full clip, len_b = clamp(lengths[b], 1, steps), lengths (B) int64 on the device.  Raw rows (P = 1): Q = steps * w
+ * with w % 4 == 0, and the first len_b * w floats of every row enter the Gram (the row stride stays Q); window tensors: steps = P,
+ * and the first len_b pieces do.  ws: eeg_dcrnn_corr_graph_rows_ws_floats(B, P, Q) floats. */
+int eeg_dcrnn_corr_graph_rows_len(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, const int64_t* lengths,
+                                  int steps, float* adj, float* S1, float* S2, float* ws, void* stream);
 
 /* Number of floats of the packed weight block of one DCGRU cell. */
 size_t eeg_dcrnn_pack_floats(int Fin, int H, int M);
