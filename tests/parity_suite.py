@@ -50,6 +50,29 @@ def assert_view(arr, gold_view, what, step=97, tol=TOL):
     assert abs(v[2] - gold_view[2]) <= 1e-4 * max(1e-9, gold_view[2]), f"{what}: sum of squares differs"
 
 
+def kernels_run(fn):
+    """The event recorder (include/eeg_dcrnn_prof.h) around fn() -> {role: {kernel symbol: launches}}: which kernel instantiation took
+    each launch role, as the library itself records it at the launch (the symbol of the function pointer it launched)."""
+    import ctypes
+    from eeg_gnn_ssl_amd import _lib
+    lib = _lib.get_lib()
+    lib.query("eeg_dcrnn_prof_enable", 1)
+    try:
+        fn()
+        if lib.is_device_build:
+            torch.cuda.synchronize()
+    finally:
+        lib.query("eeg_dcrnn_prof_enable", 0)
+    buf = ctypes.create_string_buffer(1 << 16)
+    lib.call("eeg_dcrnn_prof_report", buf, len(buf))
+    ran = {}
+    for line in buf.value.decode().strip().splitlines():
+        role, cnt, _ms, symbol = line.split(None, 3)
+        by_symbol = ran.setdefault(role, {})
+        by_symbol[symbol] = by_symbol.get(symbol, 0) + int(cnt)
+    return ran
+
+
 def make_args(cfg):
     return types.SimpleNamespace(num_nodes=cfg.num_nodes, num_rnn_layers=cfg.num_rnn_layers, rnn_units=cfg.rnn_units,
                                  input_dim=cfg.input_dim, output_dim=cfg.output_dim,

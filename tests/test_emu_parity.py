@@ -6,6 +6,7 @@ import pytest
 
 import cases
 import parity_suite as ps
+import quad_gemm_suite as qg
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -185,8 +186,8 @@ def test_round3_hoisted_gemms_and_the_paired_h_part_launch(emulator, adj3d, filt
 
 def test_randomized_shapes_through_the_whole_block_gemms(emulator, adj3d):
     """Dev knob 2 hands every hoisted GEMM to the round-3 kernels (kernels_gemm_q.h: gemm_nnr, gemm_tnq, the paired h-part launch) where
-    they cover the shape -- on the GPU they only start at 256 rows per CU, i.e. at the few full-size shapes of the GPU suite.  A
-    seeded draw over filter types, hop counts, widths (planar 64-wide planes and per-lane pointers), layer counts, row counts that are
+    they cover the shape -- on the GPU they start at 256 rows per CU, where tests/test_quad_gemm.py runs every reachable instance of
+    them at the smallest such row count, beside the full-size shapes of the GPU suite.  A seeded draw over filter types, hop counts, widths (planar 64-wide planes and per-lane pointers), layer counts, row counts that are
     and are not multiples of 16 (the TN kernel's condition: the others fall back), ragged lengths: logits and every gradient vs the
     oracle.  (600 s of the same generator: 427 cases, 0 mismatches.)"""
     import random
@@ -213,6 +214,19 @@ def test_randomized_shapes_through_the_whole_block_gemms(emulator, adj3d):
     finally:
         emulator.call("eeg_dcrnn_set_tuning", 2, 0)
         ps.assert_close_scaled = keep
+
+
+@pytest.mark.parametrize("name", list(qg.CASES))
+def test_quad_gemm_case_table(emulator, name):
+    """The case table of tests/quad_gemm_suite.py (one layer per reachable instance of the whole-block GEMMs; on the MI355X:
+    tests/test_quad_gemm.py) at emulator row counts: dev knob 2 lowers the kernels' threshold to one row per CU, T x B shrinks to the
+    smallest count with the case's row residues and two row splits (quad_gemm_suite.emu_dims).  Same float64 reference, same
+    tolerances, and the emulator's recorder proves the same quad instances took the GEMMs."""
+    emulator.call("eeg_dcrnn_set_tuning", 2, qg.EMU_KNOB_QUAD)
+    try:
+        qg.check_case(name, "cpu", None, exact=False, dims=qg.emu_dims(qg.CASES[name]))
+    finally:
+        emulator.call("eeg_dcrnn_set_tuning", 2, 0)
 
 
 def test_training_tail_kernels():

@@ -2,8 +2,6 @@
 they cover, decoder and model against the oracle under the decoder's own criteria (parity_suite.check_decoder_vs_oracle,
 parity_suite.check_ssl_device_curriculum), that the persistent kernels are what ran, graph replay under curriculum learning, and
 run-to-run determinism.  Run by tests/test_wide_decoder.py on the emulator build of the kernel sources and on the MI355X library."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -84,23 +82,10 @@ def _decoder_run(device, adj3d, shape):
 def check_persistent_kernels_ran(device, adj3d):
     """the event recorder around one forward + backward at the first wide shape: one persistent forward, one persistent backward, and
     none of the per-step decoder launches (x-part / projection / input-gradient GEMMs, T = 1 recurrent launches, node mixes)"""
-    from eeg_gnn_ssl_amd import _lib
-    lib = _lib.get_lib()
     run = _decoder_run(device, adj3d, WIDE_SHAPES["m5_autoregressive_200"])
     run()                                                   # (first call: allocations)
     torch.cuda.synchronize()
-    lib.query("eeg_dcrnn_prof_enable", 1)
-    try:
-        run()
-        torch.cuda.synchronize()
-    finally:
-        lib.query("eeg_dcrnn_prof_enable", 0)
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.call("eeg_dcrnn_prof_report", buf, len(buf))
-    counts = {}
-    for line in buf.value.decode().strip().splitlines():
-        role, cnt = line.split(None, 3)[:2]
-        counts[role] = counts.get(role, 0) + int(cnt)
+    counts = {role: sum(by_symbol.values()) for role, by_symbol in ps.kernels_run(run).items()}
     assert counts.get("dec_fwd_persist") == 1 and counts.get("dec_bwd_persist") == 1, counts
     per_step = [r for r in counts if r.startswith(("dec_gemm_nn", "dec_seq_", "dec_diffuse_", "dec_gemm_dx"))]
     assert not per_step, counts
