@@ -326,6 +326,19 @@ int seq_bwd(int H, int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st)
     return 0;
 }
 
+// The spectral form (spec_common.h): the caller makes the plans (spec_launch.h) from its dims, the CU count and these knobs
+// (compile-time zeros in the product build), sizes its workspace by them, and the launchers of spec_inst.cpp execute them.
+SpecKnobs spec_knobs() { return SpecKnobs{g_tune[EEG_TUNE_SPEC_NN_GROUPED], g_tune[EEG_TUNE_SPEC_TN_SEPARATE], g_tune[EEG_TUNE_SPEC_DX_PASSES]}; }
+int spec_plan_error(const char* what, int error) {
+    if (error == kSpecBadNct) return fail("%s: the grouped GEMM has no instance for this column count", what);
+    if (error == kSpecNotCovered) return fail("%s: the spectral form does not cover this shape", what);
+    return 0;
+}
+int spec_mix(int to_nodes, const float* in, const float* basis, int N, int T, int B, int F, int bm, float* out, hipStream_t st, const char* tag,
+             int node_rows = 0) {
+    return launch_spec_mix(spec_mix_plan(to_nodes, N, T, B, F, node_rows), in, basis, N, T, B, F, bm, out, st, tag) ? fail("spec_mix: launch failed") : 0;
+}
+
 struct BwdWs {
     size_t dxw, dbias, hplanes, rhplanes, partial, part_g, part_c, z, total;   // partial = x-part region; part_g / part_c follow it
     TnCall cx, chg, chc;       // the three weight-gradient TNs of the cell (x-part, h-part of the gate, of the candidate) ...
@@ -334,8 +347,7 @@ struct BwdWs {
     // spectral form (d->spectral): dyh = U^T dXW (N, Sp, 3H); hplanes / rhplanes = U^T h_{t-1}, U^T (r*h_{t-1}) (N, Sp, H); partial /
     // part_g / part_c = the grouped TNs' [N*spg][K][O]; z = dXh (N, Sp, Fin)
     size_t dyh;
-    TngPlan gx, gh;
-    TnfPlan gf;                // the three problems in one pass (kernels_gemm_f.h); ok: gx.spg = gh.spg = gf.spg
+    SpecTnPlan gs;             // the three problems in one pass or as the grouped launches, their row splits and partial sizes
 };
 BwdWs bwd_ws(const eeg_layer_dims* d, int need_dx) {
     BwdWs w;
@@ -348,11 +360,7 @@ BwdWs bwd_ws(const eeg_layer_dims* d, int need_dx) {
     w.hplanes = o;  o += spec ? Rp * d->H : (size_t)(d->M - 1) * R * d->H;
     w.rhplanes = o; o += spec ? Rp * d->H : (size_t)(d->M - 1) * R * d->H;
     w.dyh = o;      o += spec ? Rp * 3 * d->H : 0;
-    w.gx = spec ? tng_plan(d->Fin, spec_rows(d->T * d->B), d->N, num_cus()) : TngPlan{};
-    w.gh = spec ? tng_plan(d->H, spec_rows(d->T * d->B), d->N, num_cus()) : TngPlan{};
-    // dev knob 23 = 1: the three separate grouped launches
-    w.gf = spec && g_tune[EEG_TUNE_SPEC_TN_SEPARATE] == 0 ? tnf_plan(d->Fin, d->H, spec_rows(d->T * d->B), d->N, num_cus()) : TnfPlan{};
-    if (w.gf.ok) { w.gx.spg = w.gh.spg = w.gf.spg; w.gx.rps = w.gh.rps = w.gf.rps; }
+    w.gs = spec ? spec_tn_plan(d->Fin, d->H, spec_rows(d->T * d->B), d->N, num_cus(), spec_knobs()) : SpecTnPlan{};
     w.cx = tn_call(d->M, d->Fin, (int)R, 3 * d->H, d->x_batch_major != 0, true);
     w.chg = tn_call(d->M, d->H, (int)R, 2 * d->H, false, true);
     w.chc = tn_call(d->M, d->H, (int)R, d->H, false, true);
@@ -363,14 +371,12 @@ BwdWs bwd_ws(const eeg_layer_dims* d, int need_dx) {
     size_t px = (size_t)w.tx.nsplit * d->M * d->Fin * 3 * d->H;
     size_t pg = (size_t)w.thg.nsplit * d->M * d->H * 2 * d->H;
     size_t pc = (size_t)w.thc.nsplit * d->M * d->H * d->H;
-    if (spec) {
-        px = (size_t)d->N * w.gx.spg * d->Fin * 3 * d->H;
-        pg = (size_t)d->N * w.gh.spg * d->H * 2 * d->H;
-        pc = (size_t)d->N * w.gh.spg * d->H * d->H;
-    }
+    if (spec) { px = w.gs.px; pg = w.gs.pg; pc = w.gs.pc; }
     w.partial = o;  o += (px + 63) / 64 * 64;      // one region per GEMM: the three are reduced by one launch
     w.part_g = o;   o += (pg + 63) / 64 * 64;
     w.part_c = o;   o += (pc + 63) / 64 * 64;
+    // (spectral: dXh, read only by the two passes of a spec_dx_plan with needs_dxh; reserved whenever dX is asked for, because
+    // eeg_dcrnn_layer_bwd_ws_floats is part of the ABI -- a bwd_ws that asked that plan first could drop it)
     w.z = o;        o += need_dx ? (spec ? Rp * d->Fin : R * d->M * d->Fin) : 0;
     w.total = o;
     return w;
@@ -453,22 +459,24 @@ int cell_weight_grads_spectral(const eeg_layer_dims* d, const float* Xh, size_t 
     const int S = d->T * d->B, H = d->H, M = d->M, Fin = d->Fin, N = d->N, Sp = spec_rows(S);
     float* part_g = part + (w.part_g - w.partial);
     float* part_c = part + (w.part_c - w.partial);
-    if (w.gf.ok) {
-        if (launch_tnf(w.gf, Xh, x_gs, Fin, hh, hh_gs, rhh, dYh, Sp, N, part, part_g, part_c, st, "gemm_tn_f")) return fail("gemm_tnf: launch failed");
+    const SpecTnPlan& g = w.gs;
+    if (spec_plan_error("weight gradients (spectral)", g.error)) return 1;
+    if (g.fused) {
+        if (launch_tnf(g, Xh, x_gs, Fin, hh, hh_gs, rhh, dYh, Sp, N, part, part_g, part_c, st, "gemm_tn_f")) return fail("gemm_tnf: launch failed");
     } else {
-        if (launch_tng(w.gx, Xh, Fin, Sp, N, dYh, part, st, "gemm_tn_x", x_gs)) return fail("gemm_tng: launch failed");
-        if (launch_tng_pair(w.gh, hh, rhh, Sp, N, dYh, part_g, part_c, st, "gemm_tn_h", hh_gs)) return fail("gemm_tng_pair: launch failed");
+        if (launch_tng(g, Xh, x_gs, Fin, Sp, N, dYh, part, st, "gemm_tn_x")) return fail("gemm_tng: launch failed");
+        if (launch_tng_pair(g, hh, hh_gs, rhh, Sp, N, dYh, part_g, part_c, st, "gemm_tn_h")) return fail("gemm_tng_pair: launch failed");
     }
     ReduceJobs jobs{};
     SpecFoldJobs sj{};
     sj.basis = d->spectral; sj.N = N;
-    sj.j[0] = SpecFoldJob{part, w.gx.spg, Fin, 3 * H, ceil_div(Fin * 3 * H, 64)};
-    sj.j[1] = SpecFoldJob{part_g, w.gh.spg, H, 2 * H, ceil_div(H * 2 * H, 64)};
-    sj.j[2] = SpecFoldJob{part_c, w.gh.spg, H, H, ceil_div(H * H, 64)};
+    sj.j[0] = SpecFoldJob{part, g.spg_x, Fin, 3 * H, ceil_div(Fin * 3 * H, 64)};
+    sj.j[1] = SpecFoldJob{part_g, g.spg_h, H, 2 * H, ceil_div(H * 2 * H, 64)};
+    sj.j[2] = SpecFoldJob{part_c, g.spg_h, H, H, ceil_div(H * H, 64)};
     int nblocks = sj.j[0].nblocks + sj.j[1].nblocks + sj.j[2].nblocks;
     jobs.bias_part = bias_part; jobs.bias_B = d->B; jobs.dbg = dbg; jobs.dbc = dbc;
     if (bias_part != nullptr) nblocks += ceil_div(3 * H, 16);
-    const int ns_max = N * (w.gx.spg > w.gh.spg ? w.gx.spg : w.gh.spg);
+    const int ns_max = N * (g.spg_x > g.spg_h ? g.spg_x : g.spg_h);
     const size_t fold_lds = spec_fold_lds_bytes(M, ns_max);
     EEG_SET_MAX_LDS(reduce_unpack3s_kernel, fold_lds);
     EEG_LAUNCH_P("reduce_unpack", reduce_unpack3s_kernel, dim3(nblocks), dim3(256), fold_lds, st, jobs, sj, 0, Fin, H, M, dWg, dWc);
@@ -797,13 +805,12 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
         const int N = d->N, Sp = spec_rows(S), SpE = d->B + Sp;
         const size_t xgs = d->x_plane_stride > 0 ? (size_t)d->x_plane_stride : (size_t)Sp * Fin;
         float* Yh = ws + (size_t)R * 3 * H;
-        if (!d->x_planes_ready && launch_spec_mix(1, X, d->spectral, nullptr, N, d->T, d->B, Fin, d->x_batch_major ? 1 : 0, planes, st, "spec_mix_x"))
-            return fail("spec_mix: launch failed");
-        int nnf = g_tune[EEG_TUNE_SPEC_NN_GROUPED] == 0 ? launch_nnf(planes, xgs, Fin, Sp, N, d->spack + sp.sxr, sp.sxr_stride, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
-                                               d->spectral + spec_csum_offset(N)) : -1;
-        if (nnf > 0) return fail("gemm_nnf: launch failed");
-        if (nnf < 0 && launch_nng(planes, Fin, Sp, N, d->spack + sp.sxq, sp.sxq_stride, sp.nct_x, Yh, num_cus(), st, "gemm_nn_xw", pack + p.bias,
-                                  d->spectral + spec_csum_offset(N), xgs)) return fail("gemm_nng: launch failed");
+        if (!d->x_planes_ready && spec_mix(1, X, d->spectral, N, d->T, d->B, Fin, d->x_batch_major ? 1 : 0, planes, st, "spec_mix_x")) return 1;
+        const SpecNnPlan nn = spec_nn_plan(Fin, Sp, N, sp.nct_x, num_cus(), spec_knobs());
+        if (spec_plan_error("layer_fwd (spectral x-part)", nn.error)) return 1;
+        const bool regs = nn.kind == SpecNnKind::Regs;       // the weights of a frequency row-major (sxr) or in the quad order (sxq)
+        if (launch_spec_nn(nn, planes, xgs, Fin, Sp, N, d->spack + (regs ? sp.sxr : sp.sxq), regs ? sp.sxr_stride : sp.sxq_stride, Yh, st, "gemm_nn_xw",
+                           pack + p.bias, d->spectral + spec_csum_offset(N))) return fail("gemm_nn (spectral): launch failed");
         SeqFwdArgs a{XW, h0 != nullptr ? Hext : nullptr, P, d->p_batched, pack + p.bhg, pack + p.bhc, Hext + state, Rs, Us, Cs, RHs, nullptr, nullptr,
                      (size_t)0, d->T, d->B, N, d->act, seq_probe_arg(st)};
         SeqCall call = seq_fwd_call(H, M, N, d->T, d->B, 0, a.probe);
@@ -817,11 +824,11 @@ int eeg_dcrnn_layer_fwd(const eeg_layer_dims* d, const float* X, float* Xtm, con
                 if (launch_spec_zero_pad(RHplanes, N, S, H, st)) return fail("spec_zero_pad: launch failed");
             }
         } else {                                   // the mixes as separate passes
-            if (launch_spec_mix(0, Yh, d->spectral, nullptr, N, d->T, d->B, 3 * H, 0, XW, st, "spec_mix_y")) return fail("spec_mix: launch failed");
+            if (spec_mix(0, Yh, d->spectral, N, d->T, d->B, 3 * H, 0, XW, st, "spec_mix_y")) return 1;
             if (seq_fwd(H, M, plan, a, st)) return 1;
             if (Hplanes != nullptr) {
-                if (launch_spec_mix(1, Hext, d->spectral, nullptr, N, d->T + 1, d->B, H, 0, Hplanes, st, "spec_mix_h", SpE)) return fail("spec_mix: launch failed");
-                if (launch_spec_mix(1, RHs, d->spectral, nullptr, N, d->T, d->B, H, 0, RHplanes, st, "spec_mix_h")) return fail("spec_mix: launch failed");
+                if (spec_mix(1, Hext, d->spectral, N, d->T + 1, d->B, H, 0, Hplanes, st, "spec_mix_h", SpE)) return 1;
+                if (spec_mix(1, RHs, d->spectral, N, d->T, d->B, H, 0, RHplanes, st, "spec_mix_h")) return 1;
             }
         }
         return check_launch("layer_fwd (spectral)");
@@ -890,23 +897,25 @@ int eeg_dcrnn_layer_bwd(const eeg_layer_dims* d, const float* X, const float* P,
         float* dYh = ws + w.dyh;
         if (dyh_done) {
             if (launch_spec_zero_pad(dYh, N, S, 3 * H, st)) return fail("spec_zero_pad: launch failed");
-        } else if (launch_spec_mix(1, dXW, d->spectral, nullptr, N, d->T, d->B, 3 * H, 0, dYh, st, "spec_mix_dy")) return fail("spec_mix: launch failed");
+        } else if (spec_mix(1, dXW, d->spectral, N, d->T, d->B, 3 * H, 0, dYh, st, "spec_mix_dy")) return 1;
         const float *hh = Hplanes, *rhh = RHplanes;
         size_t hh_gs = (size_t)SpE * H;
         if (hh == nullptr) {                        // no by-products from the forward: U^T h_{t-1}, U^T (r*h_{t-1}) here
-            if (launch_spec_mix(1, Hext, d->spectral, nullptr, N, d->T, d->B, H, 0, ws + w.hplanes, st, "spec_mix_h")) return fail("spec_mix: launch failed");
-            if (launch_spec_mix(1, RHs, d->spectral, nullptr, N, d->T, d->B, H, 0, ws + w.rhplanes, st, "spec_mix_h")) return fail("spec_mix: launch failed");
+            if (spec_mix(1, Hext, d->spectral, N, d->T, d->B, H, 0, ws + w.hplanes, st, "spec_mix_h")) return 1;
+            if (spec_mix(1, RHs, d->spectral, N, d->T, d->B, H, 0, ws + w.rhplanes, st, "spec_mix_h")) return 1;
             hh = ws + w.hplanes; rhh = ws + w.rhplanes; hh_gs = 0;
         }
         if (cell_weight_grads_spectral(d, planes, xs_spec(d), hh, hh_gs, rhh, dYh, ws + w.partial, w, dWg, dWc, st, dbias, dbg, dbc)) return 1;
         if (dX != nullptr) {
-            // one kernel (GEMM over K = 3H + the node mix back) where it applies; dev knob 17 = 1: the grouped GEMM and the mix as passes
-            const int dxf = g_tune[EEG_TUNE_SPEC_DX_PASSES] == 0 ? launch_dxf(dYh, Sp, S, N, Fin, d->spack + sp.sxtq, sp.sxtq_stride, d->spectral, dX, st, "gemm_dx_f") : -1;
-            if (dxf > 0) return fail("gemm_dxf: launch failed");
-            if (dxf < 0) {
+            // one kernel (GEMM over K = 3H + the node mix back) where it applies, else the grouped GEMM and the mix as passes
+            const SpecDxPlan dx = spec_dx_plan(Fin, N, d->T, d->B, num_cus(), spec_knobs());
+            if (spec_plan_error("layer_bwd (spectral dX)", dx.error)) return 1;
+            if (dx.kind == SpecDxKind::Fused) {
+                if (launch_dxf(dx, dYh, Sp, S, N, d->spack + sp.sxtq, sp.sxtq_stride, d->spectral, dX, st, "gemm_dx_f")) return fail("gemm_dxf: launch failed");
+            } else {
                 float* dXh = ws + w.z;
-                if (launch_nng(dYh, 3 * H, Sp, N, d->spack + sp.sxtq, sp.sxtq_stride, sp.nct_t, dXh, num_cus(), st, "gemm_nn_dx")) return fail("gemm_nng: launch failed");
-                if (launch_spec_mix(0, dXh, d->spectral, nullptr, N, d->T, d->B, Fin, 0, dX, st, "spec_mix_dx")) return fail("spec_mix: launch failed");
+                if (launch_spec_nn(dx.nn, dYh, 0, 3 * H, Sp, N, d->spack + sp.sxtq, sp.sxtq_stride, dXh, st, "gemm_nn_dx")) return fail("gemm_nng: launch failed");
+                if (launch_spec_mix(dx.mix, dXh, d->spectral, N, d->T, d->B, Fin, 0, dX, st, "spec_mix_dx")) return fail("spec_mix: launch failed");
             }
         }
         return check_launch("layer_bwd (spectral)");

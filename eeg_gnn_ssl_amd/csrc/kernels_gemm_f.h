@@ -28,31 +28,11 @@
 #pragma once
 #include "common.h"
 #include "kernels_gemm_q.h"      // IntC
+#include "spec_launch.h"         // tnf_ns, tnf_wgs_per_cu, tnf_stage_floats, nnf_stage_floats, kDxf*
 
 namespace eeg {
 
-#ifndef EEG_X_TNF_RC
-#define EEG_X_TNF_RC 8
-#endif
-#ifndef EEG_X_TNF_NS
-#define EEG_X_TNF_NS 5
-#endif
-#ifndef EEG_X_TNF_MINW
-#define EEG_X_TNF_MINW 2
-#endif
-// narrow inputs (FXT <= 2: 96 accumulator registers) run three workgroups per CU on a three-stage ring (measured: -3 % against 2 x 5)
-#ifndef EEG_X_TNF_NS2
-#define EEG_X_TNF_NS2 3
-#endif
-#ifndef EEG_X_TNF_MINW2
-#define EEG_X_TNF_MINW2 3
-#endif
-constexpr int kTnfRC = EEG_X_TNF_RC;
-__host__ __device__ constexpr int tnf_ns(int FXT) { return FXT <= 2 ? EEG_X_TNF_NS2 : EEG_X_TNF_NS; }
-__host__ __device__ constexpr int tnf_wgs_per_cu(int FXT) { return FXT <= 2 ? EEG_X_TNF_MINW2 : EEG_X_TNF_MINW; }
-// floats of one stage: Xh image (FXT pieces of 256 floats) | Hh (8 x 64) | RHh (8 x 64) | dYh (8 x 192)
-__host__ __device__ constexpr int tnf_stage_floats(int FXT) { return (kTnfRC / 8) * (FXT * 256 + 512 + 512 + 1536); }
-__host__ __device__ constexpr size_t tnf_lds_bytes(int FXT) { return (size_t)tnf_ns(FXT) * tnf_stage_floats(FXT) * sizeof(float); }
+// (ring depth, rows per stage, workgroups per CU and the LDS bytes of the three kernels: spec_launch.h, next to the rules that use them)
 
 // 1-KB requests per chunk: [Xh: FXT | Hh: 2 | RHh: 2 | dYh: 6] per 8 rows; per wave a quarter of them, rounded up
 __host__ __device__ constexpr int tnf_ndma(int FXT) { return (kTnfRC / 8) * (FXT + 10); }
@@ -351,13 +331,6 @@ __global__ __launch_bounds__(256, tnf_wgs_per_cu(FXT)) void gemm_tnf_kernel(cons
 //   * persistent workgroups (2 per CU) over a balanced contiguous range of 64-row chunks; a range may cross into the next frequency
 //     (weights reloaded there); ragged ends (Sp % 64) through bounded descriptors: no per-lane guards anywhere.
 // KQ = ceil(K / 8); SWZ: K == 64.  A: (G, Sp, K) with a_gstride floats between frequencies; Wr: SpecPack::sxr; C: (G, Sp, 192).
-#ifndef EEG_X_NNF_NS
-#define EEG_X_NNF_NS 3
-#endif
-constexpr int kNnfNS = EEG_X_NNF_NS;
-__host__ __device__ constexpr int nnf_stage_floats(int K) { return 64 * K + 4; }          // + one zeroed 16-byte unit behind the last row
-__host__ __device__ constexpr size_t nnf_lds_bytes(int K) { return (size_t)kNnfNS * nnf_stage_floats(K) * sizeof(float); }
-
 template <int KQ, bool SWZ>
 __global__ __launch_bounds__(256, 2) void gemm_nnf_kernel(const float* __restrict__ A, long long a_gstride, int K, int Sp, int G,
                                                          const float* __restrict__ Wr, unsigned w_gstride, float* __restrict__ C,
@@ -491,8 +464,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nnf_kernel(const float* __restric
 //     accumulators on the VALU (acc_j += U[j][i] * T: 8 N FMAs per 96 MFMAs), so nothing but dX leaves the kernel;
 //   * rows past S / Sp through bounded descriptors (dropped stores / zero-filled requests).
 // N <= kDxfMaxN (accumulators: 8 N registers).
-constexpr int kDxfMaxN = 20, kDxfNS = 3, kDxfRows = 32, kDxfStage = kDxfRows * 192;
-__host__ __device__ constexpr size_t dxf_lds_bytes() { return (size_t)kDxfNS * kDxfStage * sizeof(float); }
 
 // NT: the node count as a literal (19: the EEG montage -- no branches in the fold), 0 = the runtime argument.
 template <int NT>

@@ -20,15 +20,13 @@
 // Reference semantics: model/cell.py:98-117 in the eigenbasis of the support.
 #pragma once
 #include "kernels_gemm_q.h"
+#include "spec_launch.h"         // kNngStages, nng_lds_bytes
 
 namespace eeg {
 
 #ifndef EEG_X_NNG_STAUX
 #define EEG_X_NNG_STAUX 0
 #endif
-constexpr int kNngStages = 4;
-// LDS of one workgroup: the ring of kNngStages stages, each 128 rows x 16 floats of activations + 4 NJ column tiles of weights
-__host__ __device__ constexpr size_t nng_lds_bytes(int NJ) { return (size_t)kNngStages * (128 * 16 + 4 * NJ * 256) * sizeof(float); }
 
 template <int NJ, int MINW>
 __global__ __launch_bounds__(256, MINW) void gemm_nng_kernel(const float* __restrict__ A, unsigned a_gstride, int F, int Sp, int G,

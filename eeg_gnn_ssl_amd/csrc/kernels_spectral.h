@@ -2,6 +2,7 @@
 // weight packs, the two HBM-bound node mixes.  Included by spec_inst.cpp only.
 #pragma once
 #include "spec_common.h"
+#include "spec_launch.h"         // kSpecBasisLds, spec_mix_generic_lds_bytes
 
 namespace eeg {
 
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void spectral_basis_kernel(const float* __rest
         out[N * N + kSpecTc + kSpecInfo + tid] = (float)c;
     }
 }
-constexpr size_t kSpecBasisLds = (2 * 32 * 32 + 32 + 256) * sizeof(double) + 32 * sizeof(int);
+// (LDS of the kernel above: kSpecBasisLds, spec_launch.h)
 
 __device__ __forceinline__ void pack_spectral_body(const float* __restrict__ Wg, const float* __restrict__ Wc, const float* __restrict__ basis,
                                                    float* __restrict__ out, const SpecPack& p, int bid, int nb) {

@@ -43,10 +43,10 @@ enum {
     EEG_TUNE_DIFFUSE_ADJ_LDS = 9,    /* 1: LDS/MFMA adjoint diffusion */
     EEG_TUNE_DEC_BWD_PER_STEP = 10,  /* 1: per-step launches in the decoder backward instead of the persistent kernel */
     EEG_TUNE_DEC_FWD_PER_STEP = 11,  /* 1: the same for the decoder forward */
-    EEG_TUNE_SPEC_DX_PASSES = 17,    /* 1: input gradient of a spectral layer as grouped GEMM + node-mix pass instead of gemm_dxf_kernel */
+    EEG_TUNE_SPEC_DX_PASSES = 17,    /* 1: input gradient of a spectral layer as grouped GEMM + node-mix pass instead of gemm_dxf_kernel (read by the spectral plan, csrc/spec_launch.h) */
     EEG_TUNE_DIFFUSE_ADJ_PLANES = 18, /* 1: the round-4 adjoint diffusion (hop planes one at a time) instead of the row-streaming one */
-    EEG_TUNE_SPEC_NN_GROUPED = 20,   /* 1: the round-5 grouped NN GEMM for the spectral x-part instead of gemm_nnf_kernel */
-    EEG_TUNE_SPEC_TN_SEPARATE = 23,  /* 1: the three grouped weight-gradient launches instead of the fused one */
+    EEG_TUNE_SPEC_NN_GROUPED = 20,   /* 1: the round-5 grouped NN GEMM for the spectral x-part instead of gemm_nnf_kernel (read by the spectral plan) */
+    EEG_TUNE_SPEC_TN_SEPARATE = 23,  /* 1: the three grouped weight-gradient launches instead of the fused one (read by the spectral plan) */
     EEG_TUNE_COUNT = 24
 };
 

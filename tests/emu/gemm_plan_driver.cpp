@@ -1,14 +1,23 @@
-// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h for the calls read from stdin, one line each (see
-// tests/test_gemm_plans.py).  Host code only: the header must compile without kernel bodies.
+// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h and csrc/spec_launch.h for the calls read from stdin, one line
+// each (see tests/test_gemm_plans.py, tests/test_spec_plans.py).  Host code only: the headers must compile without kernel bodies.
 //   nn   nseg F R nct_total ldc O batch_major quad_pack bf3_nct num_cus KNOBS  ->  kind t1 t2 t3 gx gy block lds error
 //   tn   nseg F R O batch_major offer_quad num_cus KNOBS                       ->  kind t1 t2 t3 nsplit rps gx gy block lds remap error
 //   pair M H R num_cus KNOBS   (the two h-part problems of a cell)             ->  1 / 0: one paired launch or not
 // KNOBS = keys 0 1 2 4 14 15 16 19 of include/eeg_dcrnn_dev.h.  t1..t3 are the template integers of the kind; a plan with an
 // error prints zeros for what never reaches a launch.
+// The spectral family (SKNOBS = keys 20 23 17) prints each launch as `kernel symbol ; grid.x grid.y block lds`, the symbol as the
+// event recorder spells it, launches and trailing fields joined by " ; "; a plan with an error prints `error <code>`:
+//   sup  T B N H Fin M need_dx            ->  1 / 0: spec_supported
+//   mix  to_nodes N T B F node_rows       ->  launch
+//   snn  K Sp G nct num_cus SKNOBS        ->  launch
+//   stn  Fin H Sp G num_cus SKNOBS        ->  launch (fused) or x-part launch ; pair launch, then spg_x rps_x spg_h rps_h px pg pc
+//   sdx  Fin N T B num_cus SKNOBS         ->  launch (fused) or grouped NN launch ; mix launch, then needs_dxh
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "gemm_launch.h"
+#include "spec_launch.h"
 using namespace eeg;
 
 static bool knobs(GemmKnobs& k) {
@@ -33,11 +42,78 @@ int pair_line(int M, int H, int R, int num_cus, const GemmKnobs& k) {
     return tn_pair_applies(gemm_tn_plan(g), gemm_tn_plan(c), k) ? 1 : 0;
 }
 
+static bool sknobs(SpecKnobs& k) { return scanf("%d %d %d", &k.nn_grouped, &k.tn_separate, &k.dx_passes) == 3; }
+static int launch(char* out, const char* symbol, int gx, int gy, int block, size_t lds) { return sprintf(out, "%s ; %d %d %d %zu", symbol, gx, gy, block, lds); }
+int mix_launch(const SpecMixPlan& p, char* out) {
+    char sym[64];
+    if (p.kind == SpecMixKind::Mfma) sprintf(sym, "spec_mix_mfma_kernel<%d, %d>", 1 - p.to_nodes, p.ks);
+    else sprintf(sym, p.kind == SpecMixKind::Valu19 ? (p.to_nodes ? "spec_mix_in_kernel<19>" : "spec_mix_out_kernel<19>") : "spec_mix_generic_kernel");
+    return launch(out, sym, p.grid, 1, p.block, p.lds);
+}
+int snn_launch(const SpecNnPlan& p, char* out) {
+    char sym[64];
+    if (p.error) return sprintf(out, "error %d", p.error);
+    if (p.kind == SpecNnKind::Regs) sprintf(sym, "gemm_nnf_kernel<%d, %s>", p.kq, p.swz ? "true" : "false");
+    else sprintf(sym, "gemm_nng_kernel<%d, 2>", p.nj);
+    return launch(out, sym, p.grid, 1, p.block, p.lds);
+}
+void stn_line(const SpecTnPlan& p, char* out) {
+    char sym[64];
+    if (p.error) { sprintf(out, "error %d", p.error); return; }
+    if (p.fused) {
+        sprintf(sym, "gemm_tnf_kernel<%d>", p.fxt);
+        out += launch(out, sym, p.grid_x, p.grid_y, p.block, p.lds_x);
+    } else {
+        sprintf(sym, "gemm_tnq_grouped_kernel<%d, %d, %d, %s>", p.KT, kSpecTngOt, kSpecTngRc, p.planar ? "true" : "false");
+        out += launch(out, sym, p.grid_x, p.grid_y, p.block, p.lds_x);
+        out += sprintf(out, " ; ");
+        sprintf(sym, "gemm_tnq_grouped_pair_kernel<2, %d, true>", kSpecTngRc);
+        out += launch(out, sym, 1, p.grid_h, p.block, p.lds_h);
+    }
+    sprintf(out, " ; %d %d %d %d %zu %zu %zu", p.spg_x, p.rps_x, p.spg_h, p.rps_h, p.px, p.pg, p.pc);
+}
+void sdx_line(const SpecDxPlan& p, char* out) {
+    if (p.error) { sprintf(out, "error %d", p.error); return; }
+    if (p.kind == SpecDxKind::Fused) {
+        out += launch(out, p.nt == 19 ? "gemm_dxf_kernel<19>" : "gemm_dxf_kernel<0>", p.grid, 1, p.block, p.lds);
+    } else {
+        out += snn_launch(p.nn, out);
+        out += sprintf(out, " ; ");
+        out += mix_launch(p.mix, out);
+    }
+    sprintf(out, " ; %d", p.needs_dxh ? 1 : 0);
+}
+// one spectral line; false: not a spectral op.  A malformed line ends the run (exit 2).
+static bool spec_line(const char* op, char* out) {
+    int a[7];
+    SpecKnobs k;
+    if (!strcmp(op, "sup")) {
+        if (scanf("%d %d %d %d %d %d %d", &a[0], &a[1], &a[2], &a[3], &a[4], &a[5], &a[6]) != 7) exit(2);
+        sprintf(out, "%d", spec_supported(a[0], a[1], a[2], a[3], a[4], a[5], a[6]) ? 1 : 0);
+    } else if (!strcmp(op, "mix")) {
+        if (scanf("%d %d %d %d %d %d", &a[0], &a[1], &a[2], &a[3], &a[4], &a[5]) != 6) exit(2);
+        mix_launch(spec_mix_plan(a[0], a[1], a[2], a[3], a[4], a[5]), out);
+    } else if (!strcmp(op, "snn")) {
+        if (scanf("%d %d %d %d %d", &a[0], &a[1], &a[2], &a[3], &a[4]) != 5 || !sknobs(k)) exit(2);
+        snn_launch(spec_nn_plan(a[0], a[1], a[2], a[3], a[4], k), out);
+    } else if (!strcmp(op, "stn")) {
+        if (scanf("%d %d %d %d %d", &a[0], &a[1], &a[2], &a[3], &a[4]) != 5 || !sknobs(k)) exit(2);
+        stn_line(spec_tn_plan(a[0], a[1], a[2], a[3], a[4], k), out);
+    } else if (!strcmp(op, "sdx")) {
+        if (scanf("%d %d %d %d %d", &a[0], &a[1], &a[2], &a[3], &a[4]) != 5 || !sknobs(k)) exit(2);
+        sdx_line(spec_dx_plan(a[0], a[1], a[2], a[3], a[4], k), out);
+    } else {
+        return false;
+    }
+    return true;
+}
+
 int main() {
-    char op[8], out[256];
+    char op[8], out[512];
     while (scanf("%7s", op) == 1) {
         int bm, quad;
-        if (!strcmp(op, "nn")) {
+        if (spec_line(op, out)) {
+        } else if (!strcmp(op, "nn")) {
             NnCall c{};
             if (scanf("%d %d %d %d %d %d %d %d %d %d", &c.nseg, &c.F, &c.R, &c.nct_total, &c.ldc, &c.O, &bm, &quad, &c.bf3_nct, &c.num_cus) != 10 || !knobs(c.knobs)) return 2;
             c.batch_major = bm != 0; c.quad_pack = quad != 0;

@@ -7,6 +7,7 @@ import pytest
 import cases
 import parity_suite as ps
 import quad_gemm_suite as qg
+import spec_plan_suite as sp
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -69,6 +70,18 @@ SPECTRAL_CASES = [dict(din=100, layers=2, t_len=3, b=4, classes=1),
 @pytest.mark.parametrize("case", SPECTRAL_CASES, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items() if k in ("din", "layers", "n", "b", "k")))
 def test_spectral_form_of_the_hoisted_x_part(case, adj3d):
     ps.check_spectral_form("cpu", adj3d, **case)
+
+
+@pytest.fixture(scope="module")
+def plan_driver(tmp_path_factory):
+    return qg.build_plan_driver(tmp_path_factory.mktemp("plan_driver"))
+
+
+@pytest.mark.parametrize("name", list(sp.CASES))
+def test_spectral_case_runs_the_planned_kernels(emulator, plan_driver, adj3d, name):
+    """tests/spec_plan_suite.py: every kernel instance the plans of csrc/spec_launch.h can return, each proven through the event recorder
+    to take the launches it is planned for (here also under the dev knobs; tests/test_spec_plans.py is the MI355X twin)"""
+    sp.check_case(name, "cpu", adj3d, plan_driver, sp.EMU_CUS, set_knob=lambda key, value: emulator.call("eeg_dcrnn_set_tuning", key, value))
 
 
 def test_spectral_basis_and_shared_support_detection(adj3d):
