@@ -94,6 +94,10 @@ _SIGNATURES = {
     "eeg_dcrnn_corr_graph_len": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_corr_graph_rows_len": (c_int, [_FP, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_augment_draw": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, _FP, c_void_p]),
+    # epochs from a device-resident data set (the DataLoader's shuffle and collate): perm / cursor are device int64 pointers
+    "eeg_dcrnn_epoch_keys": (c_int, [ctypes.c_uint64, c_int64, c_int64, _FP, c_void_p]),
+    "eeg_dcrnn_gather_clips": (c_int, [_FP, _FP, c_size_t, _FP, _FP, c_size_t, _FP, _FP, c_int, _FP, _FP, _FP, c_int64, c_int64, _FP, c_int, c_int,
+                                       c_int, c_void_p]),
     "eeg_dcrnn_pack_cells": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32),
                              c_int, c_int, POINTER(c_void_p), _FP, c_int, POINTER(c_void_p), c_void_p]),
     "eeg_dcrnn_cls_head_loss_ws_floats": (c_size_t, [c_int, c_int, c_int]),

@@ -13,6 +13,7 @@
 #include "../../include/eeg_dcrnn_prof.h"
 #include "kernels_decoder.h"
 #include "kernels_diffuse.h"
+#include "kernels_data.h"
 #include "kernels_feat.h"
 #include "kernels_gemm.h"
 #include "kernels_gemm_bf.h"
@@ -1096,6 +1097,57 @@ int eeg_dcrnn_augment_windows(const float* x, const float* y, int B, int Tx, int
     if ((y == nullptr) != (Ty == 0)) return fail("augment_windows: target and Ty=%d disagree (no target: y = NULL and Ty = 0)", Ty);
     if (x_out == nullptr || (y != nullptr && y_out == nullptr)) return fail("augment_windows: null output (x_out=%p, y_out=%p)", (void*)x_out, (void*)y_out);
     return window_stream("augment_windows", false, x, y, B, Tx, Ty, N, D, perm, a, c, 0.f, 1.f, x_out, y_out, stream);
+}
+
+/* ---- epochs from a device-resident data set: shuffle keys, batch gather ------------------------------- */
+int eeg_dcrnn_epoch_keys(uint64_t seed, int64_t epoch, int64_t P, int64_t* keys, void* stream) {
+    if (keys == nullptr) return fail("epoch_keys: null output");
+    if (P < 1) return fail("epoch_keys: P=%lld clips (P >= 1)", (long long)P);
+    if (epoch < 0 || epoch > 0x7fffffffLL) return fail("epoch_keys: epoch=%lld outside 0..2^31-1", (long long)epoch);
+    long long blocks = (P + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    EEG_LAUNCH_P("epoch_keys", epoch_keys_kernel, dim3((unsigned)blocks), dim3(256), 0, S_(stream), (unsigned long long)seed, (unsigned)epoch,
+                 (long long)P, reinterpret_cast<long long*>(keys));
+    return check_launch("epoch_keys");
+}
+
+int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                           const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                           const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, void* stream) {
+    if (x_pool == nullptr || x_out == nullptr) return fail("gather_clips: null x_pool / x_out");
+    if (perm == nullptr || cursor == nullptr) return fail("gather_clips: null perm / cursor");
+    if ((y_pool == nullptr) != (y_out == nullptr) || (y_pool == nullptr) != (y_row_bytes == 0))
+        return fail("gather_clips: y_pool, y_out and y_row_bytes=%zu disagree (no second wide tensor: NULL, NULL, 0)", y_row_bytes);
+    if ((label_pool == nullptr) != (label_out == nullptr) || (label_pool == nullptr) != (label_bytes == 0))
+        return fail("gather_clips: label_pool, label_out and label_bytes=%d disagree (no label: NULL, NULL, 0)", label_bytes);
+    if (label_bytes != 0 && label_bytes != 4 && label_bytes != 8) return fail("gather_clips: label_bytes=%d unsupported (4: float, 8: int64)", label_bytes);
+    if ((len_pool == nullptr) != (len_out == nullptr)) return fail("gather_clips: len_pool and len_out disagree (no lengths: both NULL)");
+    if (B < 1 || world < 1 || rank < 0 || rank >= world) return fail("gather_clips: B=%d, rank=%d, world=%d unsupported (B >= 1, 0 <= rank < world)", B, rank, world);
+    if (P < 1 || n_perm < 1) return fail("gather_clips: P=%lld clips, n_perm=%lld entries (both >= 1)", (long long)P, (long long)n_perm);
+    if ((long long)B * world > (long long)n_perm)
+        return fail("gather_clips: B*world=%lld clips per step exceed the %lld entries of perm", (long long)B * world, (long long)n_perm);
+    // a clip row of a wide tensor: whole 16-byte pieces, 16-byte aligned, inside one buffer descriptor and one launch
+    constexpr size_t kMaxRow = (size_t)65535 * kAugPerBlock * 16;
+    if (x_row_bytes < 16 || x_row_bytes % 16 != 0 || x_row_bytes > kMaxRow)
+        return fail("gather_clips: x_row_bytes=%zu unsupported (a positive multiple of 16, at most %zu)", x_row_bytes, kMaxRow);
+    if (y_row_bytes % 16 != 0 || y_row_bytes > kMaxRow)
+        return fail("gather_clips: y_row_bytes=%zu unsupported (a multiple of 16, at most %zu)", y_row_bytes, kMaxRow);
+    if ((((uintptr_t)x_pool | (uintptr_t)x_out | (uintptr_t)y_pool | (uintptr_t)y_out) & 15) != 0) return fail("gather_clips: wide tensors must be 16-byte aligned");
+    if ((((uintptr_t)label_pool | (uintptr_t)label_out) & (uintptr_t)(label_bytes == 8 ? 7 : 3)) != 0 ||
+        (((uintptr_t)len_pool | (uintptr_t)len_out | (uintptr_t)perm | (uintptr_t)cursor) & 7) != 0)
+        return fail("gather_clips: labels / lengths / perm / cursor must be aligned to their element size");
+    if (x_out == x_pool || (y_out != nullptr && y_out == y_pool)) return fail("gather_clips: in-place call (the batch tensors must not alias the pools)");
+    GatherWide w0{x_pool, x_out, (unsigned)(x_row_bytes / 16), 0u}, w1{y_pool, y_out, (unsigned)(y_row_bytes / 16), 0u};
+    w0.chunks = (w0.pieces + kAugPerBlock - 1) / kAugPerBlock;
+    w1.chunks = (w1.pieces + kAugPerBlock - 1) / kAugPerBlock;
+    if (w0.chunks + w1.chunks > 65535u) return fail("gather_clips: %zu + %zu bytes per clip exceed one launch", x_row_bytes, y_row_bytes);
+    EEG_LAUNCH_P("gather_clips", gather_clips_kernel, dim3((unsigned)B, w0.chunks + w1.chunks), dim3(kAugThreads), 0, S_(stream), w0, w1, label_pool,
+                 label_out, label_bytes, reinterpret_cast<const long long*>(len_pool), reinterpret_cast<long long*>(len_out),
+                 reinterpret_cast<const long long*>(perm), (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor),
+                 (long long)rank * B);
+    if (int rc = check_launch("gather_clips")) return rc;
+    EEG_LAUNCH_P("gather_clips_cursor", cursor_advance_kernel, dim3(1), dim3(64), 0, S_(stream), reinterpret_cast<long long*>(cursor), (long long)B * world);
+    return check_launch("gather_clips_cursor");
 }
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */

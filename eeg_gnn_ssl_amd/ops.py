@@ -12,7 +12,7 @@ Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
-    clip_adam_dev_, teacher_flags_, augment_draw_.
+    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1504,6 +1504,74 @@ _define("augment_draw_", "(Tensor(a!) rng_state, int batch, Tensor swap_perm, Te
         "(Tensor, Tensor, Tensor, Tensor)", _augment_draw_impl, _augment_draw_fake)
 
 
+# ---- epochs from a device-resident data set (the DataLoader's shuffle and collate, csrc/kernels_data.h) ----------------------------
+def _epoch_keys_impl(keys, seed: int, epoch: int) -> None:
+    """keys[i] <- the 63-bit Philox key of (seed, epoch, i): the epoch's permutation is their stable argsort"""
+    lib = _lib.get_lib()
+    _check(lib, keys, "keys", torch.int64)
+    if keys.dim() != 1 or keys.numel() < 1:
+        raise RuntimeError(f"epoch_keys: keys must be a non-empty int64 vector (one key per clip), got {tuple(keys.shape)}")
+    if not 0 <= int(seed) < 2 ** 63 or not 0 <= int(epoch) < 2 ** 31:
+        raise RuntimeError(f"epoch_keys: seed={seed} (0..2^63-1) / epoch={epoch} (0..2^31-1) out of range")
+    lib.call("eeg_dcrnn_epoch_keys", int(seed), int(epoch), keys.numel(), _p(keys), _stream(keys))
+
+
+_define("epoch_keys", "(Tensor(a!) keys, int seed, int epoch) -> ()", _epoch_keys_impl, lambda keys, seed, epoch: None)
+
+
+def _gather_pair(lib, pool, out, name, dtypes, wide, dev):
+    """one pool and its batch tensor -> (clips in the pool, bytes per clip); (0, 0) when absent"""
+    if pool is None and out is None:
+        return 0, 0
+    if pool is None or out is None:
+        raise RuntimeError(f"gather_clips: {name}_pool and {name}_out come together (one of them is None)")
+    if pool.dtype not in dtypes:
+        raise RuntimeError(f"gather_clips: {name}_pool must be {' or '.join(str(d) for d in dtypes)}, got {pool.dtype}")
+    _check(lib, pool, f"{name}_pool", pool.dtype)
+    _check(lib, out, f"{name}_out", pool.dtype)
+    if pool.device != dev or out.device != dev:
+        raise RuntimeError(f"gather_clips: {name}_pool is on {pool.device} and {name}_out on {out.device}, perm on {dev}: one device")
+    if pool.dim() < 1 or out.dim() != pool.dim() or tuple(out.shape[1:]) != tuple(pool.shape[1:]) or pool.shape[0] < 1 or out.shape[0] < 1:
+        raise RuntimeError(f"gather_clips: {name}_out {tuple(out.shape)} is not a batch of the clips of {name}_pool {tuple(pool.shape)}")
+    if (pool.dim() > 1) != wide:
+        raise RuntimeError(f"gather_clips: {name}_pool {tuple(pool.shape)} must be " + ("(P, ...): one row per clip" if wide else "(P,): one value per clip"))
+    row = pool[0].numel() * pool.element_size()
+    if wide and (row == 0 or row % 16 != 0):
+        raise RuntimeError(f"gather_clips: a clip of {name}_pool has {row} bytes; the rows of a wide pool must be whole 16-byte pieces "
+                           f"(a multiple of 4 floats per clip)")
+    return pool.shape[0], row
+
+
+def _gather_clips_impl(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, rank: int, world: int) -> None:
+    """x_out[b] <- x_pool[src_b] (and the second wide tensor, the labels, the lengths), src_b = clamp(perm[(cursor + rank*B + b) mod
+    len(perm)], 0, P-1); cursor += B*world on the stream"""
+    lib = _lib.get_lib()
+    _check(lib, perm, "perm", torch.int64)
+    _check(lib, cursor, "cursor", torch.int64)
+    dev = perm.device
+    if perm.dim() != 1 or perm.numel() < 1 or cursor.numel() != 1 or cursor.device != dev:
+        raise RuntimeError(f"gather_clips: perm must be an int64 vector and cursor one int64 on its device, got {tuple(perm.shape)} / "
+                           f"{tuple(cursor.shape)} on {cursor.device}")
+    p, x_row = _gather_pair(lib, x_pool, x_out, "x", (torch.float32,), True, dev)
+    b = x_out.shape[0]
+    py, y_row = _gather_pair(lib, y_pool, y_out, "y", (torch.float32,), True, dev)
+    pl, l_row = _gather_pair(lib, label_pool, label_out, "label", (torch.float32, torch.int64), False, dev)
+    pn, _ = _gather_pair(lib, len_pool, len_out, "len", (torch.int64,), False, dev)
+    for name, cnt, o in (("y", py, y_out), ("label", pl, label_out), ("len", pn, len_out)):
+        if o is not None and (cnt != p or o.shape[0] != b):
+            raise RuntimeError(f"gather_clips: {name}_pool holds {cnt} clips and {name}_out {o.shape[0]}; x_pool holds {p} and x_out {b}")
+    if world < 1 or not 0 <= rank < world:
+        raise RuntimeError(f"gather_clips: rank={rank} of world={world}")
+    if b * world > perm.numel():
+        raise RuntimeError(f"gather_clips: batch_size*world = {b * world} clips per step exceed the {perm.numel()} entries of perm")
+    lib.call("eeg_dcrnn_gather_clips", _p(x_pool), _p(x_out), x_row, _p(y_pool), _p(y_out), y_row, _p(label_pool), _p(label_out), int(l_row),
+             _p(len_pool), _p(len_out), _p(perm), perm.numel(), int(p), _p(cursor), int(b), int(rank), int(world), _stream(perm))
+
+
+_define("gather_clips", "(Tensor x_pool, Tensor(a!) x_out, Tensor? y_pool, Tensor(b!)? y_out, Tensor? label_pool, Tensor(c!)? label_out, "
+        "Tensor? len_pool, Tensor(d!)? len_out, Tensor perm, Tensor(e!) cursor, int rank, int world) -> ()", _gather_clips_impl, lambda *a: None)
+
+
 # =============================================================================================
 # Python conveniences used by model/, utils.py and train_step.py
 # =============================================================================================
@@ -1933,3 +2001,18 @@ def clip_adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, betas, eps, wei
     torch.ops.eeg_dcrnn.clip_adam_(params, grads, exp_avg, exp_avg_sq, int(step), float(lr), float(betas[0]), float(betas[1]),
                                    float(eps), float(weight_decay), float(max_norm), float(grad_scale), ws, norm_out)
 
+
+def epoch_keys(keys: torch.Tensor, seed: int, epoch: int) -> torch.Tensor:
+    """the shuffle keys of epoch `epoch` under `seed`, written into `keys` (int64 (P,)); `torch.sort(keys, stable=True)` gives the
+    epoch's permutation (the DataLoader's RandomSampler, dataloader_detection.py:505-523) -- `device_data.EpochSampler.begin_epoch`"""
+    torch.ops.eeg_dcrnn.epoch_keys(keys, int(seed), int(epoch))
+    return keys
+
+
+def gather_clips(x_pool, x_out, perm, cursor, rank: int = 0, world: int = 1, y_pool=None, y_out=None, label_pool=None, label_out=None,
+                 len_pool=None, len_out=None):
+    """One step's batch out of the device-resident pools (the DataLoader's collate): slot b of the batch tensors takes clip
+    clamp(perm[(cursor + rank*B + b) mod len(perm)], 0, P-1) of every pool given -- x (wide), y (a second wide tensor: the SSL
+    target), a float / int64 label and an int64 length per clip -- and `cursor` (int64[1], on the device) advances by B*world on the
+    stream.  Two launches, no allocation, capturable."""
+    torch.ops.eeg_dcrnn.gather_clips(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank), int(world))

@@ -159,6 +159,8 @@ class TrainStep:
             self._augment_rng = ops.make_rng_state(dev, stream_id=2)
         self.last_augmentation = None     # (flags, perm, log_scale) of the latest step (tests / logging)
         self._graphs = {}
+        self.sampler, self._epoch_batches = None, {}   # epochs from a device-resident data set (step_from / capture_epoch)
+        self._pending_sampler_state = None             # a checkpoint's sampler state loaded before any sampler was attached
         # curriculum learning (SSL, model.py:194-200): where the persistent decoder kernels apply, the teacher-forcing flags are
         # drawn on the device (`eeg_dcrnn_teacher_flags`) -- in eager steps and graph replays alike; elsewhere on the host
         self.device_curriculum = None     # decided at the first batch (needs the shapes)
@@ -464,9 +466,118 @@ class TrainStep:
         self.reduce_and_update()
         return loss
 
+    # -- epochs from a device-resident data set (device_data.py: DeviceDataset, EpochSampler) ---------------------
+    # The DataLoader's shuffle and collate (dataloader_detection.py:505-523 and its classification / SSL twins) on the device: the
+    # step's batch is gathered out of the pools through the sampler's device-resident permutation and cursor (`ops.gather_clips`,
+    # two launches) in front of the unchanged step -- in a captured graph as its first nodes, so an epoch replays with no host data
+    # traffic.  Everything behind the gather (augmentation, featurisation, padding, graphs) acts on the gathered batch as before.
+    def attach_sampler(self, sampler):
+        """the sampler whose (seed, epoch, cursor) `state_dict` carries and `begin_epoch` advances (step_from / capture_epoch attach
+        theirs themselves).  A sampler state that `load_state_dict` found with no sampler attached is applied to the first one
+        attached afterwards: loading the checkpoint before or after the first step_from / capture_epoch resumes on the same clips."""
+        self.sampler = sampler
+        if self._pending_sampler_state is not None:
+            state, self._pending_sampler_state = self._pending_sampler_state, None
+            sampler.load_state_dict(state)
+        return sampler
+
+    def _epoch_batch(self, dataset, sampler):
+        """the static batch tensors (x, y, seq_lengths) of this (dataset, batch size): allocated once, refilled by every gather"""
+        dev = self.fp.flat.device
+        if dataset.device != dev or sampler.device != dev:
+            raise ValueError(f"TrainStep: dataset on {dataset.device}, sampler on {sampler.device}, model on {dev}: one device")
+        if len(dataset) != sampler.P:
+            raise ValueError(f"TrainStep: the dataset holds {len(dataset)} clips, the sampler permutes P={sampler.P}")
+        if self.padding_val is not None and dataset.seq_lengths is None:
+            raise ValueError("TrainStep(padding_val=...): variable-length clips need the dataset's seq_lengths pool (DeviceDataset(x, y, "
+                             "seq_lengths=...)); it has none")
+        if (self.task == "ssl") != dataset.y_is_target:
+            raise ValueError(f"TrainStep(task={self.task!r}): y of the dataset is {tuple(dataset.y.shape)} -- labels (P,) for the supervised "
+                             f"tasks, the target pool (P, ...) for ssl")
+        self.attach_sampler(sampler)
+        key = (id(dataset), sampler.batch_size)
+        if key not in self._epoch_batches:
+            b = sampler.batch_size
+            x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=dataset.x.dtype, device=dev)
+            y = torch.empty((b,) + tuple(dataset.y.shape[1:]), dtype=dataset.y.dtype, device=dev)
+            if dataset.seq_lengths is not None:
+                lens, gathered = torch.empty(b, dtype=torch.int64, device=dev), True
+            else:                         # whole clips: the constant lengths the model's last-step gather reads (ssl: None); a raw
+                lens, gathered = dataset.full_lengths(b, self.raw_window, "TrainStep(raw_window=...)"), False      # pool needs raw_window
+            self._epoch_batches[key] = (dataset, x, y, lens, gathered)    # (the dataset is held: its id stays its own)
+        return self._epoch_batches[key][1:]
+
+    def _gather_batch(self, dataset, sampler, batch):
+        x, y, lens, gathered = batch
+        wide = dataset.y_is_target
+        ops.gather_clips(dataset.x, x, sampler.perm, sampler.cursor, sampler.rank, sampler.world,
+                         y_pool=dataset.y if wide else None, y_out=y if wide else None,
+                         label_pool=None if wide else dataset.y, label_out=None if wide else y,
+                         len_pool=dataset.seq_lengths if gathered else None, len_out=lens if gathered else None)
+
+    def step_from(self, dataset, sampler, supports=None):
+        """One eager step on the sampler's next batch of the dataset: gather into the batch tensors kept for it, then `step`.
+        supports: None (correlation graphs built on the device) or the shared graph."""
+        batch = self._epoch_batch(dataset, sampler)
+        self._gather_batch(dataset, sampler, batch)
+        return self.step(batch[0], batch[1], batch[2], supports)
+
+    def capture_epoch(self, dataset, sampler, supports=None, warmup: int = 2, slot: int = 0, include_update: bool = False):
+        """`capture` with the gather as the first nodes of the graph body, all on the one capture stream: every `replay_step(slot)`
+        then trains on the sampler's next batch -- the cursor advances inside the graph -- and `begin_epoch` (outside the graph)
+        starts the next epoch in the same tensors.  The warm-up launches and the upload replay run real gathers (and, with
+        include_update, real updates, as in `capture`); the cursor is put back to where it was."""
+        batch = self._epoch_batch(dataset, sampler)
+        x, y, lens, _ = batch
+        on_device = self.task == "ssl" and self._use_device_curriculum(self._ssl_target_steps(y), y.shape[0])
+        if self.task == "ssl" and getattr(self.model, "use_curriculum_learning", False) and not on_device:
+            raise RuntimeError("TrainStep.capture_epoch: this decoder shape is outside the persistent decoder kernels, so curriculum "
+                               "learning draws its teacher-forcing flags on the host every step; use step_from() (eager launches)")
+        keep = self.snapshot() if on_device and not include_update else None
+        cursor0 = sampler.cursor.clone()
+
+        def body():
+            self._gather_batch(dataset, sampler, batch)
+            loss = self.forward_backward(x, y, lens, supports)
+            if include_update:
+                self.reduce_and_update(count=False)
+            return loss
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):                       # populate the allocator before capture
+                body()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            loss = body()
+        graph.replay()                                    # the untimed upload replay of `capture`
+        sampler.cursor.copy_(cursor0)
+        if include_update:
+            self._advance(warmup + 1, (warmup + 1) * x.shape[0] * self.world)
+        elif keep is not None:
+            self.restore(keep, counters_only=True)
+        self._graphs[slot] = (graph, loss, (x, y, lens, supports), include_update)
+        return graph
+
+    def begin_epoch(self, epoch: int, num_epochs: int, sampler=None, eta_min: float = 0.0):
+        """Start epoch `epoch`: the sampler draws and sorts its permutation in place and zeroes the cursor, the learning rate takes
+        its cosine value (`set_epoch`).  Outside any captured graph; the graph of `capture_epoch` reads the same tensors."""
+        if sampler is not None:
+            self.attach_sampler(sampler)
+        if self.sampler is None:
+            raise RuntimeError("TrainStep.begin_epoch: no sampler attached (pass sampler=, or call step_from / capture_epoch first)")
+        self.sampler.begin_epoch(epoch)
+        return self.set_epoch(epoch, num_epochs, eta_min)
+
     # -- checkpointing (utils.CheckpointSaver / load_model_checkpoint use these like an optimizer's) -------
     def state_dict(self):
-        return {"step": self.step_count, "samples_seen": self.samples_seen, "lr": self.lr, "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone()}
+        """with a sampler attached also its (seed, epoch, cursor): a resumed run continues mid-epoch on the same clips"""
+        state = {"step": self.step_count, "samples_seen": self.samples_seen, "lr": self.lr, "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone()}
+        if self.sampler is not None:
+            state["sampler"] = self.sampler.state_dict()
+        return state
 
     def load_state_dict(self, state):
         self.step_count, self.lr = int(state["step"]), float(state["lr"])
@@ -475,6 +586,11 @@ class TrainStep:
         self.samples_seen_dev.fill_(self.samples_seen)
         self.exp_avg.copy_(state["exp_avg"])
         self.exp_avg_sq.copy_(state["exp_avg_sq"])
+        if "sampler" in state:            # no sampler attached yet: kept for `attach_sampler` (never dropped)
+            if self.sampler is not None:
+                self.sampler.load_state_dict(state["sampler"])
+            else:
+                self._pending_sampler_state = dict(state["sampler"])
 
 
 def _all_gather_uneven(t: torch.Tensor) -> torch.Tensor:

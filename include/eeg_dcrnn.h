@@ -344,6 +344,29 @@ int eeg_dcrnn_augment_draw(const uint64_t* rng_used, int B, int N, const int32_t
                            float* log_scale, const float* S_plain, const float* S_reflected, int n_supports, float* S_out,
                            void* stream);
 
+/* Epochs from a data set that stays in device memory: the DataLoader's shuffle and collate (data/dataloader_detection.py:505-523
+ * `DataLoader(dataset, shuffle=True, batch_size=...)`; dataloader_classification.py:449-467 and dataloader_ssl.py:441-459 alike: a
+ * RandomSampler permutation per epoch, the default collate stacks the samples of a batch).
+ *
+ * eeg_dcrnn_epoch_keys: keys[i] (DEVICE int64[P], 0 <= key < 2^63) = 63 bits of Philox4x32-10 at counter words (c0, c1, c2, c3) =
+ * (i low, i high, epoch, 3) under key `seed` as given.  The generator is that of the dropout masks and augmentation draws, whose
+ * draws all run at c2 = c3 = 0 under seeds into which their stream id (0..2) was mixed on the host: the keys are apart from them by
+ * the non-zero c3, which is a counter word and not a fourth stream id of that family.  The epoch's permutation is the STABLE argsort
+ * of the keys (the caller sorts, once per epoch): a function of (seed, epoch) alone, the same on every rank. */
+int eeg_dcrnn_epoch_keys(uint64_t seed, int64_t epoch, int64_t P, int64_t* keys, void* stream);
+/* eeg_dcrnn_gather_clips: batch slot b (0 <= b < B) of rank `rank` of `world` takes clip
+ *     src = clamp(perm[(cursor[0] + rank*B + b) mod n_perm], 0, P-1)
+ * of every pool: x_out[b] = x_pool[src] (rows of x_row_bytes bytes), y_out[b] = y_pool[src] (a second wide tensor, the SSL target;
+ * NULL, NULL, 0: none), label_out[b] = label_pool[src] (elements of label_bytes = 4 (float) or 8 (int64) bytes, copied as bits; NULL,
+ * NULL, 0: none), len_out[b] = len_pool[src] (int64; both NULL: none).  perm: DEVICE int64[n_perm]; cursor: DEVICE int64[1], read
+ * by the launch and advanced by B*world behind it ON THE STREAM (a second, one-thread launch), so a captured step walks through the
+ * epoch replay by replay.  The wrap and the clamp are part of the contract: no value of the cursor or of a perm entry makes the
+ * kernel touch memory outside the pools (P rows each) and the outputs (B rows each).  Wide rows are whole 16-byte pieces and
+ * 16-byte aligned; B*world <= n_perm; outputs must not alias the pools. */
+int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                           const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                           const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, void* stream);
+
 /* utils.last_relevant_pytorch (utils.py:346-357): last[b] = Htop[lengths[b]-1, b]. Htop (T,B,NH). */
 int eeg_dcrnn_gather_last(const float* Htop, const int64_t* lengths, int T, int B, int NH,
                           float* last, void* stream);
