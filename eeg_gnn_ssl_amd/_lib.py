@@ -98,6 +98,16 @@ _SIGNATURES = {
     "eeg_dcrnn_epoch_keys": (c_int, [ctypes.c_uint64, c_int64, c_int64, _FP, c_void_p]),
     "eeg_dcrnn_gather_clips": (c_int, [_FP, _FP, c_size_t, _FP, _FP, c_size_t, _FP, _FP, c_int, _FP, _FP, _FP, c_int64, c_int64, _FP, c_int, c_int,
                                        c_int, c_void_p]),
+    # an epoch that keeps its short last batch: validity of the batch slots (clip_w float[B], denom float[1], n_valid int64[1], device
+    # memory) out of the gather, read by the weighted criteria and the curriculum counter
+    "eeg_dcrnn_gather_clips_tail": (c_int, [_FP, _FP, c_size_t, _FP, _FP, c_size_t, _FP, _FP, c_int, _FP, _FP, _FP, c_int64, c_int64, _FP, c_int, c_int,
+                                            c_int, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_cls_head_loss_w": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_int, c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                          _FP, _FP, c_void_p]),
+    "eeg_dcrnn_bce_logits_w": (c_int, [_FP, _FP, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_ce_logits_w": (c_int, [_FP, _FP, c_int, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_masked_loss_w": (c_int, [_FP, _FP, c_size_t, c_int, _FP, _FP, c_int, c_float, c_float, c_float, c_int, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_teacher_flags_dev": (c_int, [_FP, _FP, _FP, ctypes.c_double, c_int, _FP, c_void_p]),
     "eeg_dcrnn_pack_cells": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32),
                              c_int, c_int, POINTER(c_void_p), _FP, c_int, POINTER(c_void_p), c_void_p]),
     "eeg_dcrnn_cls_head_loss_ws_floats": (c_size_t, [c_int, c_int, c_int]),

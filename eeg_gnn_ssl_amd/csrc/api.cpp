@@ -1111,9 +1111,11 @@ int eeg_dcrnn_epoch_keys(uint64_t seed, int64_t epoch, int64_t P, int64_t* keys,
     return check_launch("epoch_keys");
 }
 
-int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
-                           const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
-                           const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, void* stream) {
+// clip_w != nullptr: the validity gather (eeg_dcrnn_gather_clips_tail), else the plain one -- the same checks, the same two launches
+static int gather_clips_launch(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                               const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                               const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, float* clip_w,
+                               float* denom, int64_t* n_valid, void* stream) {
     if (x_pool == nullptr || x_out == nullptr) return fail("gather_clips: null x_pool / x_out");
     if (perm == nullptr || cursor == nullptr) return fail("gather_clips: null perm / cursor");
     if ((y_pool == nullptr) != (y_out == nullptr) || (y_pool == nullptr) != (y_row_bytes == 0))
@@ -1141,13 +1143,36 @@ int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes
     w0.chunks = (w0.pieces + kAugPerBlock - 1) / kAugPerBlock;
     w1.chunks = (w1.pieces + kAugPerBlock - 1) / kAugPerBlock;
     if (w0.chunks + w1.chunks > 65535u) return fail("gather_clips: %zu + %zu bytes per clip exceed one launch", x_row_bytes, y_row_bytes);
-    EEG_LAUNCH_P("gather_clips", gather_clips_kernel, dim3((unsigned)B, w0.chunks + w1.chunks), dim3(kAugThreads), 0, S_(stream), w0, w1, label_pool,
-                 label_out, label_bytes, reinterpret_cast<const long long*>(len_pool), reinterpret_cast<long long*>(len_out),
-                 reinterpret_cast<const long long*>(perm), (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor),
-                 (long long)rank * B);
+    if (clip_w == nullptr) {
+        EEG_LAUNCH_P("gather_clips", gather_clips_kernel, dim3((unsigned)B, w0.chunks + w1.chunks), dim3(kAugThreads), 0, S_(stream), w0, w1, label_pool,
+                     label_out, label_bytes, reinterpret_cast<const long long*>(len_pool), reinterpret_cast<long long*>(len_out),
+                     reinterpret_cast<const long long*>(perm), (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor),
+                     (long long)rank * B);
+    } else {
+        EEG_LAUNCH_P("gather_clips", gather_clips_tail_kernel, dim3((unsigned)B, w0.chunks + w1.chunks), dim3(kAugThreads), 0, S_(stream), w0, w1,
+                     label_pool, label_out, label_bytes, reinterpret_cast<const long long*>(len_pool), reinterpret_cast<long long*>(len_out),
+                     reinterpret_cast<const long long*>(perm), (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor),
+                     (long long)rank * B, (long long)B * world, world, clip_w, denom, reinterpret_cast<long long*>(n_valid));
+    }
     if (int rc = check_launch("gather_clips")) return rc;
     EEG_LAUNCH_P("gather_clips_cursor", cursor_advance_kernel, dim3(1), dim3(64), 0, S_(stream), reinterpret_cast<long long*>(cursor), (long long)B * world);
     return check_launch("gather_clips_cursor");
+}
+int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                           const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                           const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, void* stream) {
+    return gather_clips_launch(x_pool, x_out, x_row_bytes, y_pool, y_out, y_row_bytes, label_pool, label_out, label_bytes, len_pool, len_out, perm,
+                               n_perm, P, cursor, B, rank, world, nullptr, nullptr, nullptr, stream);
+}
+int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                                const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                                const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, float* clip_w,
+                                float* denom, int64_t* n_valid, void* stream) {
+    if (clip_w == nullptr || denom == nullptr || n_valid == nullptr) return fail("gather_clips_tail: null clip_w / denom / n_valid");
+    if ((((uintptr_t)clip_w | (uintptr_t)denom) & 3) != 0 || ((uintptr_t)n_valid & 7) != 0)
+        return fail("gather_clips_tail: clip_w / denom / n_valid must be aligned to their element size");
+    return gather_clips_launch(x_pool, x_out, x_row_bytes, y_pool, y_out, y_row_bytes, label_pool, label_out, label_bytes, len_pool, len_out, perm,
+                               n_perm, P, cursor, B, rank, world, clip_w, denom, n_valid, stream);
 }
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
@@ -1557,6 +1582,17 @@ int eeg_dcrnn_teacher_flags(uint64_t* rng_state, int64_t* samples_seen, int64_t 
                  reinterpret_cast<long long*>(samples_seen), (long long)increment, cl_decay_steps, T, reinterpret_cast<int*>(flags));
     return check_launch("teacher_flags");
 }
+int eeg_dcrnn_teacher_flags_dev(uint64_t* rng_state, int64_t* samples_seen, const int64_t* increment, double cl_decay_steps, int T,
+                                int32_t* flags, void* stream) {
+    if (rng_state == nullptr || samples_seen == nullptr || flags == nullptr) return fail("teacher_flags_dev: null state / counter / output");
+    if (increment == nullptr) return fail("teacher_flags_dev: null increment (a device int64[1])");
+    if (T < 1 || T > 64) return fail("teacher_flags_dev: T=%d unsupported (1..64)", T);
+    if (!(cl_decay_steps > 0.0)) return fail("teacher_flags_dev: cl_decay_steps must be positive");
+    EEG_LAUNCH_P("teacher_flags", teacher_flags_dev_kernel, dim3(1), dim3(64), 0, S_(stream), reinterpret_cast<unsigned long long*>(rng_state),
+                 reinterpret_cast<long long*>(samples_seen), reinterpret_cast<const long long*>(increment), cl_decay_steps, T,
+                 reinterpret_cast<int*>(flags));
+    return check_launch("teacher_flags_dev");
+}
 int eeg_dcrnn_cls_head_fwd(const float* z, const float* W, const float* bias, int B, int N, int H, int C, float dropout_p,
                            const uint64_t* rng_used, float* logits, int32_t* arg, void* stream) {
     if (N > 64) return fail("cls_head: num_nodes=%d unsupported (<= 64)", N);
@@ -1588,9 +1624,10 @@ int eeg_dcrnn_cls_head_bwd(const float* z, const float* W, const float* dlogits,
 size_t eeg_dcrnn_cls_head_loss_ws_floats(int B, int H, int C) {
     return (B >= 1 && H >= 1 && C >= 1) ? (size_t)ceil_div(B, 4) * ((size_t)C * H + C + 1) : 0;
 }
-int eeg_dcrnn_cls_head_loss(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
-                            float dropout_p, const uint64_t* rng_used, float* logits, int32_t* arg, float* dlogits, float* dz,
-                            float* dW, float* dbias, float* loss, float* ws, void* stream) {
+// clip_w != nullptr: the weighted head (eeg_dcrnn_cls_head_loss_w), else the plain one -- the same checks and launch shapes
+static int cls_head_loss_launch(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
+                                float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom, float* logits, int32_t* arg,
+                                float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
     if (B < 1 || N < 1 || H < 1 || C < 1) return fail("cls_head_loss: empty input (B=%d, N=%d, H=%d, C=%d)", B, N, H, C);
     if (N > 64) return fail("cls_head_loss: num_nodes=%d unsupported (<= 64)", N);
     if (H % 4 != 0) return fail("cls_head_loss: rnn_units=%d must be a multiple of 4", H);
@@ -1605,12 +1642,33 @@ int eeg_dcrnn_cls_head_loss(const float* z, const float* W, const float* bias, c
     const int O = C * H + C, nblk = ceil_div(B, 4);
     const size_t lds = (size_t)(4 * cls_tail_wave_floats(N, H, C) + 4 * (O + 1)) * sizeof(float);
     if (lds > kMaxLdsBytes) return fail("cls_head_loss: N=%d x (classes=%d + rnn_units=%d) floats of four clips do not fit the %zu-byte LDS", N, C, H, (size_t)kMaxLdsBytes);
+    if (clip_w != nullptr) {
+        EEG_SET_MAX_LDS(cls_head_loss_w_kernel, lds);
+        EEG_LAUNCH_P("cls_head_loss", cls_head_loss_w_kernel, dim3(nblk), dim3(256), lds, S_(stream), z, W, bias, targets, kind, B, N, H, C, drop,
+                     reinterpret_cast<const unsigned long long*>(rng_used), clip_w, denom, logits, reinterpret_cast<int*>(arg), dlogits, dz, ws);
+        if (check_launch("cls_head_loss_w")) return 1;
+        EEG_LAUNCH_P("cls_head_loss", cls_head_loss_w_finish_kernel, dim3(1), dim3(256), 0, S_(stream), ws, nblk, denom, H, C, dW, dbias, loss);
+        return check_launch("cls_head_loss_w_finish");
+    }
     EEG_SET_MAX_LDS(cls_head_loss_kernel, lds);
     EEG_LAUNCH_P("cls_head_loss", cls_head_loss_kernel, dim3(nblk), dim3(256), lds, S_(stream), z, W, bias, targets, kind, B, N, H, C, drop,
                  reinterpret_cast<const unsigned long long*>(rng_used), logits, reinterpret_cast<int*>(arg), dlogits, dz, ws);
     if (check_launch("cls_head_loss")) return 1;
     EEG_LAUNCH_P("cls_head_loss", cls_head_loss_finish_kernel, dim3(1), dim3(256), 0, S_(stream), ws, nblk, B, H, C, dW, dbias, loss);
     return check_launch("cls_head_loss_finish");
+}
+int eeg_dcrnn_cls_head_loss(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
+                            float dropout_p, const uint64_t* rng_used, float* logits, int32_t* arg, float* dlogits, float* dz,
+                            float* dW, float* dbias, float* loss, float* ws, void* stream) {
+    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, nullptr, nullptr, logits, arg, dlogits, dz, dW, dbias,
+                                loss, ws, stream);
+}
+int eeg_dcrnn_cls_head_loss_w(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
+                              float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom, float* logits, int32_t* arg,
+                              float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
+    if (clip_w == nullptr || denom == nullptr) return fail("cls_head_loss_w: null clip_w / denom");
+    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, clip_w, denom, logits, arg, dlogits, dz, dW, dbias,
+                                loss, ws, stream);
 }
 size_t eeg_dcrnn_dconv_fwd_ws_floats(int B, int N, int F, int M, int O) {
     if (B < 1 || N < 1 || F < 1 || M < 1 || O < 1) return 0;
@@ -1685,6 +1743,21 @@ int eeg_dcrnn_ce_logits(const float* logits, const int64_t* y, int B, int C, flo
                  reinterpret_cast<const long long*>(y), B, C, loss, dlogits);
     return check_launch("ce_logits");
 }
+int eeg_dcrnn_bce_logits_w(const float* logits, const float* y, int B, const float* clip_w, const float* denom, float* loss, float* dlogits,
+                           void* stream) {
+    if (B < 1) return fail("bce_logits_w: empty batch");
+    if (clip_w == nullptr || denom == nullptr) return fail("bce_logits_w: null clip_w / denom");
+    EEG_LAUNCH_P("loss_bce", bce_logits_w_kernel, dim3(1), dim3(256), 256 * sizeof(float), S_(stream), logits, y, B, clip_w, denom, loss, dlogits);
+    return check_launch("bce_logits_w");
+}
+int eeg_dcrnn_ce_logits_w(const float* logits, const int64_t* y, int B, int C, const float* clip_w, const float* denom, float* loss,
+                          float* dlogits, void* stream) {
+    if (B < 1 || C < 1) return fail("ce_logits_w: empty batch");
+    if (clip_w == nullptr || denom == nullptr) return fail("ce_logits_w: null clip_w / denom");
+    EEG_LAUNCH_P("loss_ce", ce_logits_w_kernel, dim3(1), dim3(256), 256 * sizeof(float), S_(stream), logits,
+                 reinterpret_cast<const long long*>(y), B, C, clip_w, denom, loss, dlogits);
+    return check_launch("ce_logits_w");
+}
 size_t eeg_dcrnn_masked_loss_ws_floats(void) { return 2 * kLossBlocks + 64; }
 int eeg_dcrnn_masked_loss(const float* pred, const float* y, size_t n, int use_scaler, float mean, float std_,
                           float mask_val, int kind, float* loss, float* dpred, float* ws, void* stream) {
@@ -1703,6 +1776,28 @@ int eeg_dcrnn_masked_loss(const float* pred, const float* y, size_t n, int use_s
     if (dpred != nullptr) {
         EEG_LAUNCH_P("loss_masked", masked_loss_grad_kernel, dim3(nblk * 2), dim3(256), 0, st, pred, y, n, mean, std_, use_scaler, mask_val, kind, ws, dpred);
         if (check_launch("masked_loss_grad")) return 1;
+    }
+    return 0;
+}
+int eeg_dcrnn_masked_loss_w(const float* pred, const float* y, size_t n, int B, const float* clip_w, const float* denom, int use_scaler,
+                            float mean, float std_, float mask_val, int kind, float* loss, float* dpred, float* ws, void* stream) {
+    if (n < 1) return fail("masked_loss_w: empty tensors");
+    if (kind != 0 && kind != 1) return fail("masked_loss_w: kind=%d unsupported (0 = MAE, 1 = RMSE)", kind);
+    if (B < 1 || n % (size_t)B != 0) return fail("masked_loss_w: n=%zu elements are not B=%d clips of equal size", n, B);
+    if (clip_w == nullptr || denom == nullptr) return fail("masked_loss_w: null clip_w / denom");
+    hipStream_t st = S_(stream);
+    int nblk = (int)((n + 256 * 8 - 1) / (256 * 8));
+    if (nblk > kLossBlocks) nblk = kLossBlocks;
+    if (((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dpred)) & 15) != 0)
+        return fail("masked_loss_w: tensors must be 16-byte aligned");
+    const ClipWeights cw{clip_w, n / (size_t)B};
+    EEG_LAUNCH_P("loss_masked", masked_loss_w_partial_kernel, dim3(nblk), dim3(256), 512 * sizeof(float), st, pred, y, n, mean, std_, use_scaler, mask_val, kind, ws, cw);
+    if (check_launch("masked_loss_w_partial")) return 1;
+    EEG_LAUNCH_P("loss_masked", masked_loss_w_finish_kernel, dim3(1), dim3(256), 768 * sizeof(float), st, ws, nblk, kind, loss, B, clip_w, denom);
+    if (check_launch("masked_loss_w_finish")) return 1;
+    if (dpred != nullptr) {
+        EEG_LAUNCH_P("loss_masked", masked_loss_w_grad_kernel, dim3(nblk * 2), dim3(256), 0, st, pred, y, n, mean, std_, use_scaler, mask_val, kind, ws, dpred, cw);
+        if (check_launch("masked_loss_w_grad")) return 1;
     }
     return 0;
 }

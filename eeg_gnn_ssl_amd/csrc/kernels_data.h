@@ -36,7 +36,7 @@ __device__ __forceinline__ long long gather_source(const long long* __restrict__
     return s < 0 ? 0 : (s >= P ? P - 1 : s);
 }
 
-// One launch per step: blockIdx.x = clip b of the batch, blockIdx.y = a stretch of kAugPerBlock 16-byte pieces of that clip's row of
+// One launch per step (the body of gather_clips_kernel and gather_clips_tail_kernel): blockIdx.x = clip b of the batch, blockIdx.y = a stretch of kAugPerBlock 16-byte pieces of that clip's row of
 // the first wide tensor (blockIdx.y < w0.chunks) or of the second (the SSL target pool) -- the launch shape of
 // augment_features_kernel / window_stream_kernel: kAugUnroll pieces in flight per thread, consecutive lanes hold consecutive pieces
 // (whole-line loads and stores; rows are multiples of 16 bytes and 16-byte aligned, the host refuses anything else).  Source and
@@ -44,11 +44,10 @@ __device__ __forceinline__ long long gather_source(const long long* __restrict__
 // cannot reach a neighbouring clip whatever the index arithmetic does.  The block (b, 0) also copies the clip's scalars: a label of
 // 4 or 8 bytes (float / int64, copied as bits) and an int64 length.  Nothing here writes the cursor: cursor_advance_kernel follows on
 // the stream.
-__global__ __launch_bounds__(kAugThreads) void gather_clips_kernel(GatherWide w0, GatherWide w1, const void* __restrict__ label_pool,
-                                                                   void* __restrict__ label_out, int label_bytes,
-                                                                   const long long* __restrict__ len_pool, long long* __restrict__ len_out,
-                                                                   const long long* __restrict__ perm, long long n_perm, long long P,
-                                                                   const long long* __restrict__ cursor, long long slot0) {
+__device__ __forceinline__ void gather_clip_rows(const GatherWide& w0, const GatherWide& w1, const void* __restrict__ label_pool,
+                                                 void* __restrict__ label_out, int label_bytes, const long long* __restrict__ len_pool,
+                                                 long long* __restrict__ len_out, const long long* __restrict__ perm, long long n_perm,
+                                                 long long P, const long long* __restrict__ cursor, long long slot0) {
     const unsigned b = blockIdx.x;
     const long long src = gather_source(perm, n_perm, P, cursor, slot0 + (long long)b);
     const bool second = blockIdx.y >= w0.chunks;                        // block-uniform
@@ -74,6 +73,39 @@ __global__ __launch_bounds__(kAugThreads) void gather_clips_kernel(GatherWide w0
     }
 #pragma unroll
     for (int u = 0; u < kAugUnroll; ++u) wbuf_st4(to, 4u * (e0 + u * kAugThreads), 0, v[u]);
+}
+__global__ __launch_bounds__(kAugThreads) void gather_clips_kernel(GatherWide w0, GatherWide w1, const void* __restrict__ label_pool,
+                                                                   void* __restrict__ label_out, int label_bytes,
+                                                                   const long long* __restrict__ len_pool, long long* __restrict__ len_out,
+                                                                   const long long* __restrict__ perm, long long n_perm, long long P,
+                                                                   const long long* __restrict__ cursor, long long slot0) {
+    gather_clip_rows(w0, w1, label_pool, label_out, label_bytes, len_pool, len_out, perm, n_perm, P, cursor, slot0);
+}
+
+// The gather of an epoch that KEEPS its short last batch (the reference's DataLoader, drop_last=False): the same copy -- the wrap
+// fills the slots behind the end of the epoch with real, finite clips -- plus which slots count.  With pos_b = cursor + slot0 + b
+// (the cursor as it stands, not wrapped): clip_w[b] = 1 if 0 <= pos_b < n_perm else 0, written by block (b, 0); block (0, 0) also
+// writes the GLOBAL count of the step, n_valid = clamp(n_perm - cursor, 0, step) with step = B * world clips, and the divisor of
+// this rank's criterion, denom = max(n_valid, 1) / world: behind the summed all-reduce and its 1/world, sum_valid g / denom is the
+// mean over the clips that are there.  A full batch gives clip_w = 1 and denom = B exactly.  The sums run in unsigned arithmetic:
+// no cursor overflows them.  Plain stores, in front of cursor_advance_kernel on the stream.
+__global__ __launch_bounds__(kAugThreads) void gather_clips_tail_kernel(GatherWide w0, GatherWide w1, const void* __restrict__ label_pool,
+                                                                        void* __restrict__ label_out, int label_bytes,
+                                                                        const long long* __restrict__ len_pool, long long* __restrict__ len_out,
+                                                                        const long long* __restrict__ perm, long long n_perm, long long P,
+                                                                        const long long* __restrict__ cursor, long long slot0, long long step,
+                                                                        int world, float* __restrict__ clip_w, float* __restrict__ denom,
+                                                                        long long* __restrict__ n_valid) {
+    gather_clip_rows(w0, w1, label_pool, label_out, label_bytes, len_pool, len_out, perm, n_perm, P, cursor, slot0);
+    if (blockIdx.y != 0 || threadIdx.x != 0) return;
+    const long long c = cursor[0];
+    const unsigned long long pos = (unsigned long long)c + (unsigned long long)slot0 + blockIdx.x;
+    clip_w[blockIdx.x] = pos < (unsigned long long)n_perm ? 1.f : 0.f;
+    if (blockIdx.x == 0) {
+        const long long nv = c >= n_perm ? 0 : (c <= n_perm - step ? step : n_perm - c);     // (step <= n_perm: the host refuses more)
+        n_valid[0] = nv;
+        denom[0] = (float)(nv > 1 ? nv : 1) / (float)world;
+    }
 }
 
 // cursor += step (B * world clips), behind the gather on the stream and in front of the next one: one thread of one wave (the launch

@@ -125,11 +125,17 @@ __global__ void cls_head_bwd_w_kernel(const float* __restrict__ z, const float* 
 // kind 0: nn.BCEWithLogitsLoss on logits (B,1), float targets; kind 1: nn.CrossEntropyLoss on (B,C), int64 targets (a label outside
 // 0..C-1 makes the LOSS NaN, see ce_logits_kernel).  LDS per wave: [N][C] node logits | [N][H] masked relu(z) | [C] dlogits | [C] arg.
 __host__ __device__ inline int cls_tail_wave_floats(int N, int H, int C) { return N * C + N * H + 2 * C; }
-__global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
-                                                            const void* __restrict__ targets, int kind, int B, int N, int H, int C, DropCfg drop,
-                                                            const unsigned long long* __restrict__ used, float* __restrict__ logits,
-                                                            int* __restrict__ arg, float* __restrict__ dlogits, float* __restrict__ dz,
-                                                            float* __restrict__ partial) {
+// kWeighted (cls_head_loss_w_kernel, an epoch's short last batch): clip b counts iff clip_w[b] != 0 and the mean divides by denom[0]
+// (device memory) instead of B.  A clip that does not count is SELECTED out, not multiplied: its dlogits are zero -- hence dz and
+// its dW / dbias contributions -- and its loss term is zero whatever its label holds (no NaN from a label outside 0..C-1 there);
+// logits and arg are written for it as for every clip.  The arithmetic and the order of the sums are those of the unweighted kernel.
+template <bool kWeighted>
+__device__ __forceinline__ void cls_head_loss_body(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
+                                                   const void* __restrict__ targets, int kind, int B, int N, int H, int C, const DropCfg& drop,
+                                                   const unsigned long long* __restrict__ used, float* __restrict__ logits,
+                                                   int* __restrict__ arg, float* __restrict__ dlogits, float* __restrict__ dz,
+                                                   float* __restrict__ partial, const float* __restrict__ clip_w,
+                                                   const float* __restrict__ denom) {
     EEG_DYN_SMEM(sm);
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * 4 + w, O = C * H + C;
     float* nl = sm + w * cls_tail_wave_floats(N, H, C);       // [N][C]
@@ -171,10 +177,14 @@ __global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restr
         EEG_WAVE_SYNC();
         if (lane == 0) {                                       // the clip's loss term and d loss / d logits (C is a handful)
             float term;
-            if (kind == 0) {
+            const float div = kWeighted ? denom[0] : (float)B;
+            if (kWeighted && clip_w[b] == 0.f) {
+                term = 0.f;
+                for (int c = 0; c < C; ++c) dl[c] = 0.f;
+            } else if (kind == 0) {
                 const float v = dl[0], t = reinterpret_cast<const float*>(targets)[b];
                 term = fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
-                dl[0] = (1.f / (1.f + expf(-v)) - t) / (float)B;
+                dl[0] = (1.f / (1.f + expf(-v)) - t) / div;
             } else {
                 float mx = dl[0];
                 for (int c = 1; c < C; ++c) mx = fmaxf(mx, dl[c]);
@@ -185,7 +195,7 @@ __global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restr
                 const bool t_ok = tl >= 0 && tl < (long long)C;
                 const int t = t_ok ? (int)tl : -1;
                 term = lse - (t_ok ? dl[t] : __builtin_nanf(""));
-                for (int c = 0; c < C; ++c) dl[c] = (expf(dl[c] - lse) - (c == t ? 1.f : 0.f)) / (float)B;
+                for (int c = 0; c < C; ++c) dl[c] = (expf(dl[c] - lse) - (c == t ? 1.f : 0.f)) / div;
             }
             contrib[w * (O + 1) + O] = term;
             for (int c = 0; c < C; ++c) dlogits[(size_t)b * C + c] = dl[c];
@@ -221,9 +231,23 @@ __global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restr
         partial[(size_t)blockIdx.x * (O + 1) + i] = s;
     }
 }
-// dW / dbias / loss from the per-workgroup partials, in block order
-__global__ __launch_bounds__(256) void cls_head_loss_finish_kernel(const float* __restrict__ partial, int nblk, int B, int H, int C,
-                                                                   float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ loss) {
+__global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
+                                                            const void* __restrict__ targets, int kind, int B, int N, int H, int C, DropCfg drop,
+                                                            const unsigned long long* __restrict__ used, float* __restrict__ logits,
+                                                            int* __restrict__ arg, float* __restrict__ dlogits, float* __restrict__ dz,
+                                                            float* __restrict__ partial) {
+    cls_head_loss_body<false>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void cls_head_loss_w_kernel(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
+                                                              const void* __restrict__ targets, int kind, int B, int N, int H, int C, DropCfg drop,
+                                                              const unsigned long long* __restrict__ used, const float* __restrict__ clip_w,
+                                                              const float* __restrict__ denom, float* __restrict__ logits, int* __restrict__ arg,
+                                                              float* __restrict__ dlogits, float* __restrict__ dz, float* __restrict__ partial) {
+    cls_head_loss_body<true>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, clip_w, denom);
+}
+// dW / dbias / loss from the per-workgroup partials, in block order; div: the divisor of the mean
+__device__ __forceinline__ void cls_head_loss_finish_body(const float* __restrict__ partial, int nblk, float div, int H, int C,
+                                                          float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ loss) {
     const int O = C * H + C;
     for (int i = threadIdx.x; i <= O; i += blockDim.x) {
         float s = 0.f;
@@ -238,8 +262,18 @@ __global__ __launch_bounds__(256) void cls_head_loss_finish_kernel(const float* 
         for (; q < nblk; ++q) s += partial[(size_t)q * (O + 1) + i];
         if (i < C * H) dW[i] = s;
         else if (i < O) dbias[i - C * H] = s;
-        else loss[0] = s / (float)B;
+        else loss[0] = s / div;
     }
+}
+__global__ __launch_bounds__(256) void cls_head_loss_finish_kernel(const float* __restrict__ partial, int nblk, int B, int H, int C,
+                                                                   float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ loss) {
+    cls_head_loss_finish_body(partial, nblk, (float)B, H, C, dW, dbias, loss);
+}
+// the weighted entry point: the divisor is denom[0] in device memory (one load ahead of the partials')
+__global__ __launch_bounds__(256) void cls_head_loss_w_finish_kernel(const float* __restrict__ partial, int nblk, const float* __restrict__ denom,
+                                                                     int H, int C, float* __restrict__ dW, float* __restrict__ dbias,
+                                                                     float* __restrict__ loss) {
+    cls_head_loss_finish_body(partial, nblk, denom[0], H, C, dW, dbias, loss);
 }
 
 // ---- dropout generator plumbing (common.h: Philox4x32-10 keep masks) --------------------------------------------------------
@@ -258,9 +292,8 @@ __global__ void rng_take_kernel(unsigned long long* __restrict__ state, unsigned
 // same Philox generator as the dropout masks (flag t = word t % 4 of counter offset + t / 4, u = word / 2^32 in fp64), and both the
 // generator offset and the `samples_seen` counter advance ON THE STREAM -- a captured training step replays with a fresh draw and
 // the decayed threshold.  seen[0] (int64) is read, then incremented by `inc` (the global batch: train_ssl.py:178 `step += batch_size`).
-__global__ void teacher_flags_kernel(unsigned long long* __restrict__ state, long long* __restrict__ seen, long long inc,
-                                     double decay_steps, int T, int* __restrict__ flags) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+__device__ __forceinline__ void teacher_flags_body(unsigned long long* __restrict__ state, long long* __restrict__ seen, long long inc,
+                                                   double decay_steps, int T, int* __restrict__ flags) {
     const unsigned long long seed = state[0], off = state[1];
     const long long n = seen[0];
     const double ratio = decay_steps / (decay_steps + exp((double)n / decay_steps));
@@ -272,6 +305,18 @@ __global__ void teacher_flags_kernel(unsigned long long* __restrict__ state, lon
     }
     state[1] = off + (unsigned long long)((T + 3) / 4);
     seen[0] = n + inc;
+}
+__global__ void teacher_flags_kernel(unsigned long long* __restrict__ state, long long* __restrict__ seen, long long inc,
+                                     double decay_steps, int T, int* __restrict__ flags) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    teacher_flags_body(state, seen, inc, decay_steps, T, flags);
+}
+// the increment in device memory (inc[0], int64): the gather of an epoch that keeps its short last batch writes the step's real
+// global size there (gather_clips_tail_kernel: n_valid), so a replayed graph counts the clips that were there
+__global__ void teacher_flags_dev_kernel(unsigned long long* __restrict__ state, long long* __restrict__ seen, const long long* __restrict__ inc,
+                                         double decay_steps, int T, int* __restrict__ flags) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    teacher_flags_body(state, seen, inc[0], decay_steps, T, flags);
 }
 // mask[e] = keep(e) * scale for e < n: the values the fused kernels multiply with, materialised (tests hand them to the oracle)
 __global__ void dropout_mask_kernel(const unsigned long long* __restrict__ used, size_t n, DropCfg drop, float* __restrict__ mask) {

@@ -56,6 +56,60 @@ __global__ void ce_logits_kernel(const float* __restrict__ x, const long long* _
     if (threadIdx.x == 0) loss[0] = sm[0] / (float)B;
 }
 
+// The two criteria over the clips that count (an epoch's short last batch, gather_clips_tail_kernel): clip i takes part iff
+// clip_w[i] != 0 and the mean divides by denom[0] (device memory) instead of B.  Selection, not multiplication: a clip that does not
+// count adds nothing to the loss -- whatever its label holds -- and its gradient is zero.  Same launch shape, same order of the sums:
+// with clip_w = 1 and denom = B the results are those of bce_logits_kernel / ce_logits_kernel bit for bit.
+__global__ void bce_logits_w_kernel(const float* __restrict__ x, const float* __restrict__ y, int B, const float* __restrict__ clip_w,
+                                    const float* __restrict__ denom, float* __restrict__ loss, float* __restrict__ dx) {
+    EEG_DYN_SMEM(sm);
+    const float div = denom[0];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+        if (clip_w[i] == 0.f) { dx[i] = 0.f; continue; }
+        const float v = x[i], t = y[i];
+        acc += fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
+        dx[i] = (1.f / (1.f + expf(-v)) - t) / div;
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = sm[0] / div;
+}
+__global__ void ce_logits_w_kernel(const float* __restrict__ x, const long long* __restrict__ y, int B, int C, const float* __restrict__ clip_w,
+                                   const float* __restrict__ denom, float* __restrict__ loss, float* __restrict__ dx) {
+    EEG_DYN_SMEM(sm);
+    const float div = denom[0];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+        if (clip_w[i] == 0.f) {
+            for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = 0.f;
+            continue;
+        }
+        const float* r = x + (size_t)i * C;
+        float mx = r[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
+        const float lse = mx + logf(se);
+        const long long tl = y[i];                                  // (a label outside 0..C-1 on a clip that counts: NaN, as ce_logits_kernel)
+        const bool t_ok = tl >= 0 && tl < (long long)C;
+        const int t = t_ok ? (int)tl : -1;
+        acc += lse - (t_ok ? r[t] : __builtin_nanf(""));
+        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (expf(r[c] - lse) - (c == t ? 1.f : 0.f)) / div;
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = sm[0] / div;
+}
+
 // utils.compute_regression_loss (utils.py:431-495): optional scalar StandardScaler inverse transform
 // (v*std + mean), mask = (y_true != mask_val), loss = sum(e * mask) / count(mask) with e = |d| (kind 0,
 // masked MAE) or d^2 followed by sqrt (kind 1: `masked_mse_loss`, really a masked RMSE).
@@ -69,34 +123,58 @@ __device__ __forceinline__ void masked_terms(float p, float y, float mean, float
     d = ps - ys;
     mk = ys != mask_val ? 1.f : 0.f;
 }
+// Per-clip weights of the weighted loss (masked_loss_w_*): the tensors are (B, ...) contiguous, element e belongs to clip e / per
+// (per = n / B elements per clip, n % B == 0: the host refuses anything else, so the clip of every e < n is below B) and counts iff
+// clip_w[clip] != 0.  One division per 16-byte piece; a piece that straddles clips looks its elements up one by one.
+struct ClipWeights {
+    const float* w;     // clip_w (B), nullptr: every element counts (the unweighted kernels)
+    size_t per;
+};
+__device__ __forceinline__ size_t clip_of(size_t e, size_t per) {
+    return ((e | per) >> 32) != 0 ? e / per : (size_t)((unsigned)e / (unsigned)per);
+}
+__device__ __forceinline__ void clip_on4(const ClipWeights& cw, size_t e0, bool on[4]) {
+    const size_t c0 = clip_of(e0, cw.per);
+    if (e0 - c0 * cw.per + 3 < cw.per) {
+        on[0] = on[1] = on[2] = on[3] = cw.w[c0] != 0.f;
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) on[r] = cw.w[clip_of(e0 + r, cw.per)] != 0.f;
+    }
+}
 // 16-byte loads, two per operand in flight per thread; the n % 4 tail elements go to the last thread of the grid.
-__global__ __launch_bounds__(256) void masked_loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
-                                                                  size_t n, float mean, float std_, int scaled,
-                                                                  float mask_val, int kind, float* __restrict__ part) {
+template <bool kWeighted>
+__device__ __forceinline__ void masked_loss_partial_body(const float* __restrict__ pred, const float* __restrict__ y, size_t n, float mean,
+                                                         float std_, int scaled, float mask_val, int kind, float* __restrict__ part,
+                                                         const ClipWeights& cw) {
     EEG_DYN_SMEM(sm);                                   // [2][256]
     float s = 0.f, c = 0.f;
-    auto term = [&](float p, float yv) {
+    auto term = [&](float p, float yv, bool on) {
         float d, mk;
         masked_terms(p, yv, mean, std_, scaled, mask_val, d, mk);
+        if (kWeighted) mk = on ? mk : 0.f;
         s += (kind == 0 ? fabsf(d) : d * d) * mk;
         c += mk;
     };
     const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool on0[4] = {true, true, true, true}, on1[4] = {true, true, true, true};
     for (; i + stride < n4; i += 2 * stride) {
         const f32x4 p0 = ld4(pred + 4 * i), y0 = ld4(y + 4 * i), p1 = ld4(pred + 4 * (i + stride)), y1 = ld4(y + 4 * (i + stride));
+        if (kWeighted) { clip_on4(cw, 4 * i, on0); clip_on4(cw, 4 * (i + stride), on1); }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) term(p0[r], y0[r]);
+        for (int r = 0; r < 4; ++r) term(p0[r], y0[r], on0[r]);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) term(p1[r], y1[r]);
+        for (int r = 0; r < 4; ++r) term(p1[r], y1[r], on1[r]);
     }
     if (i < n4) {
         const f32x4 p0 = ld4(pred + 4 * i), y0 = ld4(y + 4 * i);
+        if (kWeighted) clip_on4(cw, 4 * i, on0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) term(p0[r], y0[r]);
+        for (int r = 0; r < 4; ++r) term(p0[r], y0[r], on0[r]);
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == blockDim.x - 1)
-        for (size_t e = 4 * n4; e < n; ++e) term(pred[e], y[e]);
+        for (size_t e = 4 * n4; e < n; ++e) term(pred[e], y[e], !kWeighted || cw.w[clip_of(e, cw.per)] != 0.f);
     sm[threadIdx.x] = s;
     sm[256 + threadIdx.x] = c;
     __syncthreads();
@@ -106,9 +184,20 @@ __global__ __launch_bounds__(256) void masked_loss_partial_kernel(const float* _
     }
     if (threadIdx.x == 0) { part[blockIdx.x] = sm[0]; part[kLossBlocks + blockIdx.x] = sm[256]; }
 }
+__global__ __launch_bounds__(256) void masked_loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                                  size_t n, float mean, float std_, int scaled,
+                                                                  float mask_val, int kind, float* __restrict__ part) {
+    masked_loss_partial_body<false>(pred, y, n, mean, std_, scaled, mask_val, kind, part, ClipWeights{nullptr, 1});
+}
+__global__ __launch_bounds__(256) void masked_loss_w_partial_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                                    size_t n, float mean, float std_, int scaled, float mask_val,
+                                                                    int kind, float* __restrict__ part, ClipWeights cw) {
+    masked_loss_partial_body<true>(pred, y, n, mean, std_, scaled, mask_val, kind, part, cw);
+}
 // part[2*kLossBlocks] = loss, [+1] = gradient scale (MAE: 1/count; RMSE: 1/(count*loss)); 0 when count == 0
 // one block of 256 threads: thread i adds parts i, i + 256, ...; then a fixed tree.
-__global__ __launch_bounds__(256) void masked_loss_finish_kernel(float* __restrict__ part, int nblk, int kind, float* __restrict__ loss) {
+// f: the rank's factor on value and gradient (1 for the unweighted loss)
+__device__ __forceinline__ void masked_loss_finish_body(float* __restrict__ part, int nblk, int kind, float* __restrict__ loss, float f) {
     EEG_DYN_SMEM(sm);                                   // [2][256]
     float s = 0.f, c = 0.f;
     for (int i = threadIdx.x; i < nblk; i += 256) { s += part[i]; c += part[kLossBlocks + i]; }
@@ -126,31 +215,68 @@ __global__ __launch_bounds__(256) void masked_loss_finish_kernel(float* __restri
     if (c > 0.f) {
         l = kind == 0 ? s / c : sqrtf(s / c);
         sc = kind == 0 ? 1.f / c : (l > 0.f ? 1.f / (c * l) : 0.f);
+        l *= f;
+        sc *= f;
     }
     loss[0] = l;
     part[2 * kLossBlocks] = l;
     part[2 * kLossBlocks + 1] = sc;
 }
-__global__ __launch_bounds__(256) void masked_loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ y,
-                                                               size_t n, float mean, float std_, int scaled, float mask_val,
-                                                               int kind, const float* __restrict__ part, float* __restrict__ dpred) {
+__global__ __launch_bounds__(256) void masked_loss_finish_kernel(float* __restrict__ part, int nblk, int kind, float* __restrict__ loss) {
+    masked_loss_finish_body(part, nblk, kind, loss, 1.f);
+}
+// The weighted loss of a rank: L = the masked MAE / RMSE over the elements of the clips that count, times f = (sum_b clip_w[b]) /
+// denom[0] on value and gradient -- the rank's share of the mean over the clips of ALL ranks (denom = global count / world, and the
+// summed all-reduce is followed by 1/world).  The weights are 0 or 1: their sum is exact in any order.  No element left (every
+// weight 0): loss 0 and gradient 0, no 0/0.  clip_w = 1, denom = B: f is exactly 1.
+__global__ __launch_bounds__(256) void masked_loss_w_finish_kernel(float* __restrict__ part, int nblk, int kind, float* __restrict__ loss, int B,
+                                                                   const float* __restrict__ clip_w, const float* __restrict__ denom) {
+    EEG_DYN_SMEM(sm);                                   // [3][256]: the third row is this sum's
+    float* wsum = sm + 512;
+    float w = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) w += clip_w[i];
+    wsum[threadIdx.x] = w;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) wsum[threadIdx.x] += wsum[threadIdx.x + k];
+        __syncthreads();
+    }
+    masked_loss_finish_body(part, nblk, kind, loss, wsum[0] / denom[0]);
+}
+template <bool kWeighted>
+__device__ __forceinline__ void masked_loss_grad_body(const float* __restrict__ pred, const float* __restrict__ y, size_t n, float mean,
+                                                      float std_, int scaled, float mask_val, int kind, const float* __restrict__ part,
+                                                      float* __restrict__ dpred, const ClipWeights& cw) {
     const float sc = part[2 * kLossBlocks + 1] * (scaled ? std_ : 1.f);
-    auto grad = [&](float p, float yv) {
+    auto grad = [&](float p, float yv, bool on) {
         float d, mk;
         masked_terms(p, yv, mean, std_, scaled, mask_val, d, mk);
+        if (kWeighted) mk = on ? mk : 0.f;
         const float e = kind == 0 ? (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) : d;
         return e * mk * sc;
     };
     const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
+    bool on[4] = {true, true, true, true};
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         const f32x4 p0 = ld4(pred + 4 * i), y0 = ld4(y + 4 * i);
+        if (kWeighted) clip_on4(cw, 4 * i, on);
         f32x4 g;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) g[r] = grad(p0[r], y0[r]);
+        for (int r = 0; r < 4; ++r) g[r] = grad(p0[r], y0[r], on[r]);
         st4(dpred + 4 * i, g);
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == blockDim.x - 1)
-        for (size_t e = 4 * n4; e < n; ++e) dpred[e] = grad(pred[e], y[e]);
+        for (size_t e = 4 * n4; e < n; ++e) dpred[e] = grad(pred[e], y[e], !kWeighted || cw.w[clip_of(e, cw.per)] != 0.f);
+}
+__global__ __launch_bounds__(256) void masked_loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                               size_t n, float mean, float std_, int scaled, float mask_val,
+                                                               int kind, const float* __restrict__ part, float* __restrict__ dpred) {
+    masked_loss_grad_body<false>(pred, y, n, mean, std_, scaled, mask_val, kind, part, dpred, ClipWeights{nullptr, 1});
+}
+__global__ __launch_bounds__(256) void masked_loss_w_grad_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                                 size_t n, float mean, float std_, int scaled, float mask_val, int kind,
+                                                                 const float* __restrict__ part, float* __restrict__ dpred, ClipWeights cw) {
+    masked_loss_grad_body<true>(pred, y, n, mean, std_, scaled, mask_val, kind, part, dpred, cw);
 }
 
 // p[0 .. n16) <- 0 in 16-byte pieces, then the < 16 trailing bytes (optimizer.zero_grad() on the flat bucket; a memset node of the

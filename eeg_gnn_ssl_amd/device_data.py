@@ -7,8 +7,17 @@ per cfg2 step, 233 MB of raw signals) -- the link, not the kernels, then sets th
 `EpochSampler` the epoch's permutation and a cursor, both on the device; `TrainStep.step_from` / `capture_epoch` gather each
 step's batch out of the pools (`ops.gather_clips`: one launch + the cursor's) in front of the unchanged step.
 
-One deviation from the reference: the last, shorter batch of an epoch is dropped (P mod (batch_size * world) clips, other clips
-every epoch) -- a captured graph has one batch size."""
+The epoch's short last batch.  The reference's loaders keep it (`drop_last=False`): `EpochSampler(..., drop_last=False)` does the
+same -- ceil(P / (batch_size * world)) steps, the last one on the P mod (batch_size * world) clips that remain.  A captured graph
+has one batch size, but not one count of clips that matter: the gather wraps, so the slots behind the end of the epoch hold real
+clips, and it writes which slots count (`clip_w`), the step's global count (`n_valid`) and the divisor of the rank's criterion
+(`denom = max(n_valid, 1) / world`) into device memory; the criterion kernels select the other slots out (loss term and seed
+exactly zero, hence a zero contribution to every gradient) and divide by `denom`.  Behind the summed all-reduce and its 1/world
+the gradient is sum_valid g_b / n_valid: the mean over the clips that are there, what the reference's single process computes for
+its short batch (on one rank the plain mean; the RMSE of the SSL task is the clip-weighted mean of the ranks' losses, a rank's loss
+being that of its shard as everywhere here).  A rank whose slots all lie behind the end contributes zeros and still takes part in
+the all-reduce.  The DEFAULT, `drop_last=True`, deviates from the reference: the short batch is dropped (other clips every epoch)
+and the step runs the unweighted kernels."""
 from __future__ import annotations
 
 from typing import Optional
@@ -96,9 +105,17 @@ class EpochSampler:
     `begin_epoch(e)` draws P Philox keys from (seed, e) (`ops.epoch_keys`), sorts them -- stable, once per epoch -- INTO `perm` and
     zeroes the cursor; both tensors keep their addresses, so a captured graph sees the new epoch.  Every rank of a data-parallel
     run passes the same seed: one shared permutation, rank r takes positions cursor + r*batch_size .. + batch_size of every step
-    (disjoint shards).  steps_per_epoch = P // (batch_size * world); the tail is dropped (module docstring)."""
+    (disjoint shards).  steps_per_epoch = P // (batch_size * world); the tail is dropped (module docstring).
 
-    def __init__(self, P: int, batch_size: int, seed: int, rank: Optional[int] = None, world: Optional[int] = None, device=None):
+    drop_last=False keeps the tail: steps_per_epoch = ceil(P / (batch_size * world)), and the sampler owns `clip_w` (batch_size,)
+    float32, `denom` (1,) float32 and `n_valid` (1,) int64 at fixed addresses, which every gather of a step rewrites and the
+    criterion reads (module docstring).  A constructor property: `state_dict` does not carry it.  Such a sampler keeps a HOST mirror
+    of the cursor (`take`), so that the step counts its clips without reading the device: `begin_epoch` and `load_state_dict` set
+    it; a caller that writes `cursor` itself says so with `seek`.  A step issued past the end of the epoch (cursor >= P) is the
+    caller's error; it stays finite -- every weight 0: loss 0, zero gradients -- and no kernel raises."""
+
+    def __init__(self, P: int, batch_size: int, seed: int, rank: Optional[int] = None, world: Optional[int] = None, device=None,
+                 drop_last: bool = True):
         has_pg = dist.is_available() and dist.is_initialized()
         self.rank = int(rank) if rank is not None else (dist.get_rank() if has_pg else 0)
         self.world = int(world) if world is not None else (dist.get_world_size() if has_pg else 1)
@@ -112,12 +129,20 @@ class EpochSampler:
             raise ValueError(f"EpochSampler: seed={seed} outside 0..2^63-1")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        self.steps_per_epoch = self.P // (self.batch_size * self.world)
+        self.drop_last = bool(drop_last)
+        per_step = self.batch_size * self.world
+        self.steps_per_epoch = self.P // per_step if self.drop_last else -(-self.P // per_step)
         self.perm = torch.arange(self.P, dtype=torch.int64, device=device)
         self.cursor = torch.zeros(1, dtype=torch.int64, device=device)
         self._keys = torch.empty(self.P, dtype=torch.int64, device=device)
         self._sorted = torch.empty(self.P, dtype=torch.int64, device=device)
         self.epoch = None                 # no epoch begun: perm is the identity
+        self.clip_w = self.denom = self.n_valid = None
+        self._host_cursor = 0             # drop_last=False: the host's copy of `cursor`
+        if not self.drop_last:            # a full batch until the first gather says otherwise
+            self.clip_w = torch.ones(self.batch_size, dtype=torch.float32, device=device)
+            self.denom = torch.full((1,), float(self.batch_size), dtype=torch.float32, device=device)
+            self.n_valid = torch.full((1,), per_step, dtype=torch.int64, device=device)
 
     @property
     def device(self):
@@ -128,8 +153,27 @@ class EpochSampler:
         ops.epoch_keys(self._keys, self.seed, int(epoch))
         torch.sort(self._keys, stable=True, out=(self._sorted, self.perm))
         self.cursor.zero_()
+        self._host_cursor = 0
         self.epoch = int(epoch)
         return self
+
+    def seek(self, cursor: int):
+        """put the cursor at `cursor` -- the device tensor and the host mirror of a drop_last=False sampler alike (outside any
+        captured graph).  Writing `sampler.cursor` directly leaves that mirror behind: the step then counts the wrong clips."""
+        self.cursor.fill_(int(cursor))
+        self._host_cursor = int(cursor)
+        return self
+
+    def take(self) -> int:
+        """the global number of clips that count in the step about to be issued; moves the host mirror of the cursor on by one
+        step.  No device read: batch_size * world for the default sampler, clamp(P - cursor, 0, batch_size * world) from the mirror
+        for drop_last=False."""
+        per_step = self.batch_size * self.world
+        if self.drop_last:
+            return per_step
+        n = min(max(self.P - self._host_cursor, 0), per_step)
+        self._host_cursor += per_step
+        return n
 
     def state_dict(self):
         return {"seed": self.seed, "epoch": self.epoch, "cursor": int(self.cursor.item())}
@@ -142,4 +186,4 @@ class EpochSampler:
             self.epoch = None
         else:
             self.begin_epoch(int(state["epoch"]))
-        self.cursor.fill_(int(state["cursor"]))
+        self.seek(int(state["cursor"]))

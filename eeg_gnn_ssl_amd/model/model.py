@@ -245,7 +245,9 @@ class DCRNNModel_nextTimePred(nn.Module):
         """batches_seen: the reference's host integer (model.py:336-343: the threshold and `random.random()` per decoder step
         are evaluated on the host) -- or, as an extension, a DEVICE int64[1] counter tensor: threshold and coin flips are then
         evaluated by `eeg_dcrnn_teacher_flags` on the stream from the decoder's Philox generator, and the counter advances
-        by `self.batches_seen_increment` (train_ssl.py:178 `step += batch_size`), so that the forward is graph-replayable."""
+        by `self.batches_seen_increment` (train_ssl.py:178 `step += batch_size`), so that the forward is graph-replayable.
+        The increment is an int or, itself, a DEVICE int64[1] tensor read on the stream (`EpochSampler.n_valid`: the real size of
+        an epoch's short last batch)."""
         b, t_out, n, _ = decoder_inputs.shape
         enc_in = encoder_inputs.transpose(0, 1)
         dec_in = decoder_inputs.transpose(0, 1)

@@ -114,6 +114,19 @@ def _clip_lengths(what: str, lengths: torch.Tensor, b: int, ref: torch.Tensor):
     return lengths.contiguous()
 
 
+def _clip_weights(what: str, clip_w: torch.Tensor, denom: torch.Tensor, b: int, ref: torch.Tensor):
+    """`clip_w` / `denom` of the weighted criteria (written by `gather_clips(..., clip_w=, denom=, n_valid=)`), read by the kernels ON
+    THE DEVICE: anything but a float32 (B,) tensor and one float32 on the device of the clips is refused"""
+    if not torch.is_tensor(clip_w) or clip_w.dtype != torch.float32 or tuple(clip_w.shape) != (b,) or clip_w.device != ref.device:
+        got = f"{clip_w.dtype} {tuple(clip_w.shape)} on {clip_w.device}" if torch.is_tensor(clip_w) else type(clip_w).__name__
+        raise RuntimeError(f"{what}: clip_w must be a float32 tensor of shape ({b},) on {ref.device} (one weight per clip, read on the "
+                           f"device), got {got}")
+    if not torch.is_tensor(denom) or denom.dtype != torch.float32 or denom.numel() != 1 or denom.device != ref.device:
+        got = f"{denom.dtype} {tuple(denom.shape)} on {denom.device}" if torch.is_tensor(denom) else type(denom).__name__
+        raise RuntimeError(f"{what}: denom must be one float32 on {ref.device} (the divisor of the mean, read on the device), got {got}")
+    return clip_w.contiguous(), denom.contiguous()
+
+
 def _new(shape, like: torch.Tensor, dtype=torch.float32):
     return torch.empty(shape, dtype=dtype, device=like.device)
 
@@ -999,9 +1012,10 @@ def _cls_head_backward(ctx, dlogits, _darg):
 torch.library.register_autograd(f"{NS}::cls_head", _cls_head_backward, setup_context=_cls_head_setup, lib=_libdef)
 
 
-def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, dw, db):
+def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, dw, db, clip_w=None, denom=None):
     """head forward + criterion + the head's backward for one optimisation step (eeg_dcrnn_cls_head_loss): returns
-    (loss (1,), logits (B,C), arg (B,C) int32, dlogits (B,C), dz (B,N,H)); dw (C,H) / db (C) are overwritten."""
+    (loss (1,), logits (B,C), arg (B,C) int32, dlogits (B,C), dz (B,N,H)); dw (C,H) / db (C) are overwritten.
+    clip_w / denom (the operator cls_head_loss_w): over the clips that count (eeg_dcrnn_cls_head_loss_w)."""
     lib = _lib.get_lib()
     z, w, bias = z.contiguous(), w.detach().contiguous(), bias.detach().contiguous()
     for t, nm in ((z, "head input"), (w, "fc.weight"), (bias, "fc.bias"), (dw, "fc.weight gradient"), (db, "fc.bias gradient")):
@@ -1029,9 +1043,18 @@ def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_us
     loss, logits, arg = _new((1,), z), _new((b, c), z), _new((b, c), z, torch.int32)
     dlogits, dz = _new((b, c), z), torch.empty_like(z)
     ws = _new((lib.query("eeg_dcrnn_cls_head_loss_ws_floats", b, h, c),), z)
-    lib.call("eeg_dcrnn_cls_head_loss", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
-             _p(logits), _p(arg), _p(dlogits), _p(dz), _p(dw), _p(db), _p(loss), _p(ws), _stream(z))
+    if clip_w is None:
+        lib.call("eeg_dcrnn_cls_head_loss", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
+                 _p(logits), _p(arg), _p(dlogits), _p(dz), _p(dw), _p(db), _p(loss), _p(ws), _stream(z))
+    else:
+        clip_w, denom = _clip_weights("cls_head_loss", clip_w, denom, b, z)
+        lib.call("eeg_dcrnn_cls_head_loss_w", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
+                 _p(clip_w), _p(denom), _p(logits), _p(arg), _p(dlogits), _p(dz), _p(dw), _p(db), _p(loss), _p(ws), _stream(z))
     return loss, logits, arg, dlogits, dz
+
+
+def _cls_head_loss_w_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, clip_w, denom, dw, db):
+    return _cls_head_loss_impl(z, w, bias, targets, kind, dropout_p, rng_used, dw, db, clip_w, denom)
 
 
 def _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db):
@@ -1041,6 +1064,9 @@ def _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db):
 
 _define("cls_head_loss", "(Tensor z, Tensor w, Tensor bias, Tensor targets, int kind, float dropout_p, Tensor? rng_used, Tensor(a!) dw, Tensor(b!) db) "
         "-> (Tensor, Tensor, Tensor, Tensor, Tensor)", _cls_head_loss_impl, _cls_head_loss_fake)
+_define("cls_head_loss_w", "(Tensor z, Tensor w, Tensor bias, Tensor targets, int kind, float dropout_p, Tensor? rng_used, Tensor clip_w, Tensor denom, "
+        "Tensor(a!) dw, Tensor(b!) db) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", _cls_head_loss_w_impl,
+        lambda z, w, bias, targets, kind, dropout_p, rng_used, clip_w, denom, dw, db: _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db))
 
 
 def _gather_last_impl(htop, lengths):
@@ -1350,7 +1376,7 @@ _define("corr_graph_rows_len", "(Tensor x, int top_k, Tensor lengths, int steps)
 # =============================================================================================
 # losses that seed backward, optimiser tail
 # =============================================================================================
-def _bce_logits_impl(logits, y):
+def _bce_logits_impl(logits, y, clip_w=None, denom=None):
     lib = _lib.get_lib()
     x = logits.contiguous().view(-1)
     yy = y.to(torch.float32).contiguous().view(-1)
@@ -1359,11 +1385,15 @@ def _bce_logits_impl(logits, y):
     if yy.numel() != x.numel():
         raise RuntimeError(f"bce_logits: {yy.numel()} targets for {x.numel()} logits")
     loss, dx = _new((1,), x), torch.empty_like(x)
-    lib.call("eeg_dcrnn_bce_logits", _p(x), _p(yy), x.numel(), _p(loss), _p(dx), _stream(x))
+    if clip_w is None:
+        lib.call("eeg_dcrnn_bce_logits", _p(x), _p(yy), x.numel(), _p(loss), _p(dx), _stream(x))
+    else:
+        clip_w, denom = _clip_weights("bce_logits", clip_w, denom, x.numel(), x)
+        lib.call("eeg_dcrnn_bce_logits_w", _p(x), _p(yy), x.numel(), _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
     return loss[0], dx.view(logits.shape)
 
 
-def _ce_logits_impl(logits, y):
+def _ce_logits_impl(logits, y, clip_w=None, denom=None):
     lib = _lib.get_lib()
     x = logits.contiguous()
     yy = y.to(torch.int64).contiguous()
@@ -1372,11 +1402,15 @@ def _ce_logits_impl(logits, y):
     if x.dim() != 2 or yy.numel() != x.shape[0]:
         raise RuntimeError(f"ce_logits: logits {tuple(x.shape)} need shape (B, C) and {yy.numel()} targets B entries")
     loss, dx = _new((1,), x), torch.empty_like(x)
-    lib.call("eeg_dcrnn_ce_logits", _p(x), _p(yy), x.shape[0], x.shape[1], _p(loss), _p(dx), _stream(x))
+    if clip_w is None:
+        lib.call("eeg_dcrnn_ce_logits", _p(x), _p(yy), x.shape[0], x.shape[1], _p(loss), _p(dx), _stream(x))
+    else:
+        clip_w, denom = _clip_weights("ce_logits", clip_w, denom, x.shape[0], x)
+        lib.call("eeg_dcrnn_ce_logits_w", _p(x), _p(yy), x.shape[0], x.shape[1], _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
     return loss[0], dx
 
 
-def _masked_loss_impl(pred, y, use_scaler: bool, mean: float, std: float, mask_val: float, kind: int):
+def _masked_loss_impl(pred, y, use_scaler: bool, mean: float, std: float, mask_val: float, kind: int, clip_w=None, denom=None):
     lib = _lib.get_lib()
     pr = pred.contiguous()
     t = y.to(torch.float32).contiguous()
@@ -1391,8 +1425,15 @@ def _masked_loss_impl(pred, y, use_scaler: bool, mean: float, std: float, mask_v
         raise RuntimeError(f"y_predicted {tuple(pr.shape)} and y_true {tuple(t.shape)} differ in shape")
     loss, dp = _new((1,), pr), torch.empty_like(pr)
     ws = _new((lib.query("eeg_dcrnn_masked_loss_ws_floats"),), pr)
-    lib.call("eeg_dcrnn_masked_loss", _p(pr), _p(t), pr.numel(), 1 if use_scaler else 0, float(mean), float(std),
-             float(mask_val), int(kind), _p(loss), _p(dp), _p(ws), _stream(pr))
+    if clip_w is None:
+        lib.call("eeg_dcrnn_masked_loss", _p(pr), _p(t), pr.numel(), 1 if use_scaler else 0, float(mean), float(std),
+                 float(mask_val), int(kind), _p(loss), _p(dp), _p(ws), _stream(pr))
+    else:
+        if pr.dim() < 1 or pr.shape[0] < 1:
+            raise RuntimeError(f"masked_loss: y_predicted {tuple(pr.shape)} has no leading clip dimension for clip_w")
+        clip_w, denom = _clip_weights("masked_loss", clip_w, denom, pr.shape[0], pr)
+        lib.call("eeg_dcrnn_masked_loss_w", _p(pr), _p(t), pr.numel(), int(pr.shape[0]), _p(clip_w), _p(denom), 1 if use_scaler else 0,
+                 float(mean), float(std), float(mask_val), int(kind), _p(loss), _p(dp), _p(ws), _stream(pr))
     return loss[0], dp
 
 
@@ -1401,6 +1442,11 @@ _define("bce_logits", "(Tensor logits, Tensor y) -> (Tensor loss, Tensor dlogits
 _define("ce_logits", "(Tensor logits, Tensor y) -> (Tensor loss, Tensor dlogits)", _ce_logits_impl, _loss_fake)
 _define("masked_loss", "(Tensor pred, Tensor y, bool use_scaler, float mean, float std, float mask_val, int kind) -> (Tensor loss, Tensor dpred)",
         _masked_loss_impl, _loss_fake)
+# the same criteria over the clips that count: clip_w (B,) float32 and denom (1,) float32 in device memory (`gather_clips`)
+_define("bce_logits_w", "(Tensor logits, Tensor y, Tensor clip_w, Tensor denom) -> (Tensor loss, Tensor dlogits)", _bce_logits_impl, _loss_fake)
+_define("ce_logits_w", "(Tensor logits, Tensor y, Tensor clip_w, Tensor denom) -> (Tensor loss, Tensor dlogits)", _ce_logits_impl, _loss_fake)
+_define("masked_loss_w", "(Tensor pred, Tensor y, bool use_scaler, float mean, float std, float mask_val, int kind, Tensor clip_w, Tensor denom) "
+        "-> (Tensor loss, Tensor dpred)", _masked_loss_impl, _loss_fake)
 
 
 def _loss_setup(ctx, inputs, output):
@@ -1413,7 +1459,7 @@ def _loss_backward(ctx, dloss, _dgrad):
     return (dx * dloss,) + (None,) * (ctx.n_in - 1)
 
 
-for _name in ("bce_logits", "ce_logits", "masked_loss"):
+for _name in ("bce_logits", "ce_logits", "masked_loss", "bce_logits_w", "ce_logits_w", "masked_loss_w"):
     torch.library.register_autograd(f"{NS}::{_name}", _loss_backward, setup_context=_loss_setup, lib=_libdef)
 
 
@@ -1462,6 +1508,24 @@ def _teacher_flags_impl(rng_state, samples_seen, increment: int, cl_decay_steps:
 
 _define("teacher_flags_", "(Tensor(a!) rng_state, Tensor(b!) samples_seen, int increment, float cl_decay_steps, int t_len) -> Tensor",
         _teacher_flags_impl, lambda rng_state, samples_seen, increment, cl_decay_steps, t_len: rng_state.new_empty((t_len,), dtype=torch.int32))
+
+
+def _teacher_flags_dev_impl(rng_state, samples_seen, increment, cl_decay_steps: float, t_len: int):
+    """`_teacher_flags_impl` with the increment read on the device: `increment` is one int64 on the device of the counter"""
+    lib = _lib.get_lib()
+    _check_rng(lib, rng_state, "rng_state")
+    _check(lib, samples_seen, "samples_seen", torch.int64)
+    if increment.dtype != torch.int64 or increment.numel() != 1 or increment.device != samples_seen.device:
+        raise RuntimeError(f"teacher_flags: increment must be an int or one int64 on {samples_seen.device} (read on the device), got "
+                           f"{increment.dtype} {tuple(increment.shape)} on {increment.device}")
+    flags = _new((t_len,), rng_state, torch.int32)
+    lib.call("eeg_dcrnn_teacher_flags_dev", _p(rng_state), _p(samples_seen), _p(increment.contiguous()), float(cl_decay_steps), int(t_len),
+             _p(flags), _stream(rng_state))
+    return flags
+
+
+_define("teacher_flags_dev_", "(Tensor(a!) rng_state, Tensor(b!) samples_seen, Tensor increment, float cl_decay_steps, int t_len) -> Tensor",
+        _teacher_flags_dev_impl, lambda rng_state, samples_seen, increment, cl_decay_steps, t_len: rng_state.new_empty((t_len,), dtype=torch.int32))
 
 
 def _augment_draw_impl(rng_state, batch: int, swap_perm, plain_supports, reflected_supports):
@@ -1542,9 +1606,11 @@ def _gather_pair(lib, pool, out, name, dtypes, wide, dev):
     return pool.shape[0], row
 
 
-def _gather_clips_impl(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, rank: int, world: int) -> None:
+def _gather_clips_impl(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, rank: int, world: int,
+                       clip_w=None, denom=None, n_valid=None) -> None:
     """x_out[b] <- x_pool[src_b] (and the second wide tensor, the labels, the lengths), src_b = clamp(perm[(cursor + rank*B + b) mod
-    len(perm)], 0, P-1); cursor += B*world on the stream"""
+    len(perm)], 0, P-1); cursor += B*world on the stream.  clip_w / denom / n_valid (the operator gather_clips_tail): the validity
+    of the slots, written in front of the cursor's advance (eeg_dcrnn_gather_clips_tail)."""
     lib = _lib.get_lib()
     _check(lib, perm, "perm", torch.int64)
     _check(lib, cursor, "cursor", torch.int64)
@@ -1564,12 +1630,24 @@ def _gather_clips_impl(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_
         raise RuntimeError(f"gather_clips: rank={rank} of world={world}")
     if b * world > perm.numel():
         raise RuntimeError(f"gather_clips: batch_size*world = {b * world} clips per step exceed the {perm.numel()} entries of perm")
-    lib.call("eeg_dcrnn_gather_clips", _p(x_pool), _p(x_out), x_row, _p(y_pool), _p(y_out), y_row, _p(label_pool), _p(label_out), int(l_row),
-             _p(len_pool), _p(len_out), _p(perm), perm.numel(), int(p), _p(cursor), int(b), int(rank), int(world), _stream(perm))
+    if clip_w is None:
+        lib.call("eeg_dcrnn_gather_clips", _p(x_pool), _p(x_out), x_row, _p(y_pool), _p(y_out), y_row, _p(label_pool), _p(label_out), int(l_row),
+                 _p(len_pool), _p(len_out), _p(perm), perm.numel(), int(p), _p(cursor), int(b), int(rank), int(world), _stream(perm))
+        return
+    for t, name, dtype, shape in ((clip_w, "clip_w", torch.float32, (b,)), (denom, "denom", torch.float32, (1,)), (n_valid, "n_valid", torch.int64, (1,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"gather_clips: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev} (written on the device), "
+                               f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    lib.call("eeg_dcrnn_gather_clips_tail", _p(x_pool), _p(x_out), x_row, _p(y_pool), _p(y_out), y_row, _p(label_pool), _p(label_out), int(l_row),
+             _p(len_pool), _p(len_out), _p(perm), perm.numel(), int(p), _p(cursor), int(b), int(rank), int(world), _p(clip_w), _p(denom),
+             _p(n_valid), _stream(perm))
 
 
 _define("gather_clips", "(Tensor x_pool, Tensor(a!) x_out, Tensor? y_pool, Tensor(b!)? y_out, Tensor? label_pool, Tensor(c!)? label_out, "
         "Tensor? len_pool, Tensor(d!)? len_out, Tensor perm, Tensor(e!) cursor, int rank, int world) -> ()", _gather_clips_impl, lambda *a: None)
+_define("gather_clips_tail", "(Tensor x_pool, Tensor(a!) x_out, Tensor? y_pool, Tensor(b!)? y_out, Tensor? label_pool, Tensor(c!)? label_out, "
+        "Tensor? len_pool, Tensor(d!)? len_out, Tensor perm, Tensor(e!) cursor, int rank, int world, Tensor(f!) clip_w, Tensor(g!) denom, "
+        "Tensor(h!) n_valid) -> ()", _gather_clips_impl, lambda *a: None)
 
 
 # =============================================================================================
@@ -1904,18 +1982,36 @@ def cls_head(z, w, bias, dropout_p=0.0, rng_state=None, return_rng_used=False):
     return (logits, used) if return_rng_used else logits
 
 
-def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.0, rng_state=None):
+def _weights_together(what, clip_w, denom, ref):
+    """the pair of the weighted criteria: both or none, and on the device of the clips (the dispatcher picks the implementation by
+    the devices of ALL tensor arguments: a stray one is refused here, by name; dtype and shape are the operator's to refuse)"""
+    if (clip_w is None) != (denom is None):
+        raise RuntimeError(f"{what}: clip_w and denom come together (one of them is None)")
+    if clip_w is not None:
+        _clip_weights(what, clip_w, denom, clip_w.numel() if torch.is_tensor(clip_w) and clip_w.dim() == 1 else -1, ref)
+
+
+def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.0, rng_state=None, clip_w=None, denom=None):
     """The tail of a supervised optimisation step behind the encoder (model.py:267-270 + train.py:203-206,266-272) in two launches:
     dropout -> relu -> fc -> max over nodes, the criterion (task "detection": BCE-with-logits, "classification": cross-entropy) and
     their backward.  z (B,N,H) = the top layer's state at len-1, DETACHED from autograd: the gradients of fc go straight into
     `fc_weight.grad` / `fc_bias.grad` (written in place inside `with GradSink`, else accumulated), and the caller seeds the encoder's
-    backward with the returned dz (`last.backward(dz)`).  Returns (loss (), logits (B,C), dz (B,N,H))."""
+    backward with the returned dz (`last.backward(dz)`).  Returns (loss (), logits (B,C), dz (B,N,H)).
+    clip_w (B,) float32 / denom (1,) float32, both on the device and given together (`gather_clips(..., clip_w=, denom=, n_valid=)`,
+    an epoch's short last batch): the mean runs over the clips with clip_w != 0 and divides by denom; the others get dz = 0 and add
+    nothing to the loss and to the gradients of fc, whatever their label holds.  logits are returned for every clip."""
+    _weights_together("cls_head_loss", clip_w, denom, z)
     used = rng_take(rng_state, z.numel() // 4) if dropout_p > 0 else None
     sunk = [GradSink.take(q) for q in (fc_weight, fc_bias)]
     dw = sunk[0] if sunk[0] is not None else torch.empty_like(fc_weight)
     db = sunk[1] if sunk[1] is not None else torch.empty_like(fc_bias)
-    loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,
-                                                                    0 if task == "detection" else 1, float(dropout_p), used, dw, db)
+    kind = 0 if task == "detection" else 1
+    if clip_w is None:
+        loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,
+                                                                        kind, float(dropout_p), used, dw, db)
+    else:
+        loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss_w(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,
+                                                                          kind, float(dropout_p), used, clip_w, denom, dw, db)
     for q, buf, sk in ((fc_weight, dw, sunk[0]), (fc_bias, db, sunk[1])):
         if sk is None and q.requires_grad:
             q.grad = buf if q.grad is None else q.grad + buf
@@ -1939,22 +2035,36 @@ def gather_last(htop: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
     return torch.ops.eeg_dcrnn.gather_last(htop, lengths)
 
 
-def masked_regression_loss(y_predicted, y_true, mean=None, std=None, loss_fn="mae", mask_val=0.0):
+def masked_regression_loss(y_predicted, y_true, mean=None, std=None, loss_fn="mae", mask_val=0.0, clip_w=None, denom=None):
     """utils.compute_regression_loss (utils.py:431-495).  Only the exact string 'mae' selects the MAE
-    (utils.py:489-495); anything else is the masked RMSE."""
+    (utils.py:489-495); anything else is the masked RMSE.
+    clip_w (B,) / denom (1,) (float32 on the device, together; B = the leading dimension): the loss L over the elements of the clips
+    with clip_w != 0 only, times the rank's factor sum(clip_w) / denom -- on one rank with denom = the number of such clips, L itself."""
+    _weights_together("masked_regression_loss", clip_w, denom, y_predicted)
     scaled = mean is not None
-    return torch.ops.eeg_dcrnn.masked_loss(y_predicted, y_true, scaled, float(mean) if scaled else 0.0,
-                                           float(std) if scaled else 1.0, float(mask_val), 0 if loss_fn == "mae" else 1)[0]
+    args = (y_predicted, y_true, scaled, float(mean) if scaled else 0.0, float(std) if scaled else 1.0, float(mask_val), 0 if loss_fn == "mae" else 1)
+    if clip_w is None:
+        return torch.ops.eeg_dcrnn.masked_loss(*args)[0]
+    return torch.ops.eeg_dcrnn.masked_loss_w(*args, clip_w, denom)[0]
 
 
-def bce_with_logits(logits, y):
-    """nn.BCEWithLogitsLoss() (mean): value and dlogits from one HIP launch (train.py:203-204)."""
-    return torch.ops.eeg_dcrnn.bce_logits(logits, y)[0]
+def bce_with_logits(logits, y, clip_w=None, denom=None):
+    """nn.BCEWithLogitsLoss() (mean): value and dlogits from one HIP launch (train.py:203-204).
+    clip_w (B,) / denom (1,) (float32 on the device, together): sum over the clips with clip_w != 0, divided by denom."""
+    _weights_together("bce_with_logits", clip_w, denom, logits)
+    if clip_w is None:
+        return torch.ops.eeg_dcrnn.bce_logits(logits, y)[0]
+    return torch.ops.eeg_dcrnn.bce_logits_w(logits, y, clip_w, denom)[0]
 
 
-def cross_entropy(logits, y):
-    """nn.CrossEntropyLoss() (mean) on (B,C) logits and int64 class targets (train.py:205-206)."""
-    return torch.ops.eeg_dcrnn.ce_logits(logits, y)[0]
+def cross_entropy(logits, y, clip_w=None, denom=None):
+    """nn.CrossEntropyLoss() (mean) on (B,C) logits and int64 class targets (train.py:205-206).
+    clip_w (B,) / denom (1,) (float32 on the device, together): sum over the clips with clip_w != 0, divided by denom; the label of
+    a clip that does not count is not looked at."""
+    _weights_together("cross_entropy", clip_w, denom, logits)
+    if clip_w is None:
+        return torch.ops.eeg_dcrnn.ce_logits(logits, y)[0]
+    return torch.ops.eeg_dcrnn.ce_logits_w(logits, y, clip_w, denom)[0]
 
 
 def decoder_is_persistent(t_len, batch, n, h, dout, m, n_layers) -> bool:
@@ -1966,7 +2076,11 @@ def decoder_is_persistent(t_len, batch, n, h, dout, m, n_layers) -> bool:
 
 def teacher_flags(rng_state, samples_seen, increment, cl_decay_steps, t_len):
     """Scheduled-sampling flags of one decoder forward drawn ON THE DEVICE (model.py:194-200, utils.py:385-390): int32[t_len],
-    flag t = u_t < k / (k + exp(samples_seen / k)); advances the generator and adds `increment` to samples_seen on the stream."""
+    flag t = u_t < k / (k + exp(samples_seen / k)); advances the generator and adds `increment` to samples_seen on the stream.
+    increment: an int, or one int64 ON THE DEVICE that is read on the stream (`n_valid` of `gather_clips`: the real size of an
+    epoch's short last batch inside a replayed graph)."""
+    if torch.is_tensor(increment):
+        return torch.ops.eeg_dcrnn.teacher_flags_dev_(rng_state, samples_seen, increment, float(cl_decay_steps), int(t_len))
     return torch.ops.eeg_dcrnn.teacher_flags_(rng_state, samples_seen, int(increment), float(cl_decay_steps), int(t_len))
 
 
@@ -2010,9 +2124,21 @@ def epoch_keys(keys: torch.Tensor, seed: int, epoch: int) -> torch.Tensor:
 
 
 def gather_clips(x_pool, x_out, perm, cursor, rank: int = 0, world: int = 1, y_pool=None, y_out=None, label_pool=None, label_out=None,
-                 len_pool=None, len_out=None):
+                 len_pool=None, len_out=None, clip_w=None, denom=None, n_valid=None):
     """One step's batch out of the device-resident pools (the DataLoader's collate): slot b of the batch tensors takes clip
     clamp(perm[(cursor + rank*B + b) mod len(perm)], 0, P-1) of every pool given -- x (wide), y (a second wide tensor: the SSL
     target), a float / int64 label and an int64 length per clip -- and `cursor` (int64[1], on the device) advances by B*world on the
-    stream.  Two launches, no allocation, capturable."""
-    torch.ops.eeg_dcrnn.gather_clips(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank), int(world))
+    stream.  Two launches, no allocation, capturable.
+    clip_w (B,) float32, denom (1,) float32, n_valid (1,) int64, on the device and given together: an epoch that keeps its short
+    last batch.  The same copy -- the slots behind the end of the epoch hold real clips through the wrap -- and, written in front of
+    the cursor's advance: clip_w[b] = 1 if 0 <= cursor + rank*B + b < len(perm) else 0, n_valid = clamp(len(perm) - cursor, 0,
+    B*world) (all ranks), denom = max(n_valid, 1) / world -- the operands of the weighted criteria (`cls_head_loss`, `bce_with_logits`,
+    `cross_entropy`, `masked_regression_loss`) and of `teacher_flags`.  A full batch: clip_w = 1, denom = B."""
+    tail = [t is not None for t in (clip_w, denom, n_valid)]
+    if not any(tail):
+        torch.ops.eeg_dcrnn.gather_clips(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank), int(world))
+        return
+    if not all(tail):
+        raise RuntimeError("gather_clips: clip_w, denom and n_valid come together (one of them is None)")
+    torch.ops.eeg_dcrnn.gather_clips_tail(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank),
+                                          int(world), clip_w, denom, n_valid)

@@ -230,20 +230,28 @@ class TrainStep:
         sc = None if self.scaler_mean is None else utils.StandardScaler(self.scaler_mean, self.scaler_std)
         return utils.compute_regression_loss(y_true=y, y_predicted=out, standard_scaler=sc, loss_fn="MAE")
 
-    def loss_and_grad(self, out, y):
-        """(loss, d loss / d out) of the task's criterion from the fused HIP loss kernels (same values as `self.loss`)"""
+    def loss_and_grad(self, out, y, clip_w=None, denom=None):
+        """(loss, d loss / d out) of the task's criterion from the fused HIP loss kernels (same values as `self.loss`).
+        clip_w / denom (device tensors of a drop_last=False sampler): over the clips that count, divided by denom"""
+        E = torch.ops.eeg_dcrnn
+        weights = () if clip_w is None else (clip_w, denom)
         if self.task == "detection":
-            return torch.ops.eeg_dcrnn.bce_logits(out.view(-1), y)
+            return (E.bce_logits_w if weights else E.bce_logits)(out.view(-1), y, *weights)
         if self.task == "classification":
-            return torch.ops.eeg_dcrnn.ce_logits(out, y)
+            return (E.ce_logits_w if weights else E.ce_logits)(out, y, *weights)
         scaled = self.scaler_mean is not None
         # train_ssl.py:165-170: loss_fn "MAE" != "mae" selects the masked RMSE (kind 1), Q9
-        return torch.ops.eeg_dcrnn.masked_loss(out, y, scaled, float(self.scaler_mean) if scaled else 0.0,
-                                               float(self.scaler_std) if scaled else 1.0, 0.0, 1)
+        return (E.masked_loss_w if weights else E.masked_loss)(out, y, scaled, float(self.scaler_mean) if scaled else 0.0,
+                                                               float(self.scaler_std) if scaled else 1.0, 0.0, 1, *weights)
 
-    def forward_backward(self, x, y, seq_lengths, supports):
+    def forward_backward(self, x, y, seq_lengths, supports, sampler=None):
         """supports=None: build the per-clip correlation graph and its dual random-walk supports from
-        the clips on the device (the DataLoader-side `_get_indiv_graphs` of the reference)."""
+        the clips on the device (the DataLoader-side `_get_indiv_graphs` of the reference).
+        sampler: the `EpochSampler` whose gather filled x / y (`step_from` / `capture_epoch` pass theirs).  One that keeps the
+        epoch's short last batch (drop_last=False) hands its device-resident `clip_w` / `denom` to the criterion and, for ssl, its
+        `n_valid` to the curriculum counter; everything in front of the criterion sees the B real clips of the batch tensors."""
+        tail = sampler is not None and not sampler.drop_last
+        clip_w, denom = (sampler.clip_w, sampler.denom) if tail else (None, None)
         self.fp.zero_grad()
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
@@ -274,7 +282,7 @@ class TrainStep:
             supports = ops.collapse_shared_supports(supports)
         if self.task == "ssl":
             if self._use_device_curriculum(y.shape[1], y.shape[0]):
-                self.model.batches_seen_increment = x.shape[0] * self.world
+                self.model.batches_seen_increment = sampler.n_valid if tail else x.shape[0] * self.world
                 out = self.model(x, y, supports, batches_seen=self.samples_seen_dev)
             else:
                 out = self.model(x, y, supports, batches_seen=self.samples_seen)    # train_ssl.py:163
@@ -285,7 +293,7 @@ class TrainStep:
             drop_p = m._drop_p()
             with self.fp.sink:
                 loss, self.last_logits, dz = ops.cls_head_loss(last, m.fc.weight, m.fc.bias, y, self.task, drop_p,
-                                                               m._rng_state(last.device) if drop_p > 0 else None)
+                                                               m._rng_state(last.device) if drop_p > 0 else None, clip_w=clip_w, denom=denom)
                 last.backward(dz)
             return loss.detach()
         else:
@@ -293,7 +301,7 @@ class TrainStep:
         # The loss kernels return value AND gradient (d loss / d out) from one pass: backward is seeded with that gradient
         # directly -- `loss.backward()` would first fill a ones tensor and multiply the saved gradient by it (two framework
         # kernels per step for a factor of exactly 1).  `self.loss(out, y).backward()` remains the equivalent public path.
-        loss, seed = self.loss_and_grad(out.detach(), y)
+        loss, seed = self.loss_and_grad(out.detach(), y, clip_w, denom)
         with self.fp.sink:                       # backward operators write into the flat gradient bucket
             out.backward(seed.view_as(out))
         return loss.detach()
@@ -417,7 +425,7 @@ class TrainStep:
             self._advance(warmup + 1, (warmup + 1) * x.shape[0] * self.world)
         elif keep is not None:
             self.restore(keep, counters_only=True)        # the warm-up draws advanced the device-side sample counter
-        self._graphs[slot] = (graph, loss, (x, y, seq_lengths, supports), include_update)
+        self._graphs[slot] = (graph, loss, (x, y, seq_lengths, supports), include_update, None)
         return graph
 
     def snapshot(self):
@@ -439,9 +447,10 @@ class TrainStep:
 
     def replay_step(self, slot: int = 0):
         """One optimisation step on the captured tensors of `slot`: graph replay + all-reduce + clip/Adam."""
-        graph, loss, inputs, whole = self._graphs[slot]
+        graph, loss, inputs, whole, sampler = self._graphs[slot]
         graph.replay()
-        self._advance(0, inputs[0].shape[0] * self.world)
+        # (a sampler that keeps the short last batch counts the clips that were there, from its host mirror of the cursor)
+        self._advance(0, inputs[0].shape[0] * self.world if sampler is None else sampler.take())
         if whole:
             self._advance(1)
         else:
@@ -513,14 +522,23 @@ class TrainStep:
         ops.gather_clips(dataset.x, x, sampler.perm, sampler.cursor, sampler.rank, sampler.world,
                          y_pool=dataset.y if wide else None, y_out=y if wide else None,
                          label_pool=None if wide else dataset.y, label_out=None if wide else y,
-                         len_pool=dataset.seq_lengths if gathered else None, len_out=lens if gathered else None)
+                         len_pool=dataset.seq_lengths if gathered else None, len_out=lens if gathered else None,
+                         clip_w=sampler.clip_w, denom=sampler.denom, n_valid=sampler.n_valid)     # (None, None, None: drop_last)
 
     def step_from(self, dataset, sampler, supports=None):
         """One eager step on the sampler's next batch of the dataset: gather into the batch tensors kept for it, then `step`.
-        supports: None (correlation graphs built on the device) or the shared graph."""
+        supports: None (correlation graphs built on the device) or the shared graph.  With a drop_last=False sampler the last step of
+        the epoch trains on the clips that remain, normalised by their number (device_data.py); a step issued past the end of the
+        epoch is the caller's error and applies a zero gradient."""
         batch = self._epoch_batch(dataset, sampler)
         self._gather_batch(dataset, sampler, batch)
-        return self.step(batch[0], batch[1], batch[2], supports)
+        if sampler.drop_last:
+            return self.step(batch[0], batch[1], batch[2], supports)
+        # the epoch's short last batch is kept: the criterion runs over the clips that count, and so does `samples_seen`
+        loss = self.forward_backward(batch[0], batch[1], batch[2], supports, sampler=sampler)
+        self._advance(0, sampler.take())
+        self.reduce_and_update()
+        return loss
 
     def capture_epoch(self, dataset, sampler, supports=None, warmup: int = 2, slot: int = 0, include_update: bool = False):
         """`capture` with the gather as the first nodes of the graph body, all on the one capture stream: every `replay_step(slot)`
@@ -534,11 +552,11 @@ class TrainStep:
             raise RuntimeError("TrainStep.capture_epoch: this decoder shape is outside the persistent decoder kernels, so curriculum "
                                "learning draws its teacher-forcing flags on the host every step; use step_from() (eager launches)")
         keep = self.snapshot() if on_device and not include_update else None
-        cursor0 = sampler.cursor.clone()
+        cursor0, host0 = sampler.cursor.clone(), sampler._host_cursor     # (host0: the host mirror a drop_last=False sampler keeps)
 
         def body():
             self._gather_batch(dataset, sampler, batch)
-            loss = self.forward_backward(x, y, lens, supports)
+            loss = self.forward_backward(x, y, lens, supports, sampler=sampler)
             if include_update:
                 self.reduce_and_update(count=False)
             return loss
@@ -554,11 +572,15 @@ class TrainStep:
             loss = body()
         graph.replay()                                    # the untimed upload replay of `capture`
         sampler.cursor.copy_(cursor0)
+        seen = (warmup + 1) * x.shape[0] * self.world             # the clips the warm-up launches and the upload replay counted
+        if not sampler.drop_last:
+            seen = sum(sampler.take() for _ in range(warmup + 1))
+            sampler._host_cursor = host0
         if include_update:
-            self._advance(warmup + 1, (warmup + 1) * x.shape[0] * self.world)
+            self._advance(warmup + 1, seen)
         elif keep is not None:
             self.restore(keep, counters_only=True)
-        self._graphs[slot] = (graph, loss, (x, y, lens, supports), include_update)
+        self._graphs[slot] = (graph, loss, (x, y, lens, supports), include_update, None if sampler.drop_last else sampler)
         return graph
 
     def begin_epoch(self, epoch: int, num_epochs: int, sampler=None, eta_min: float = 0.0):

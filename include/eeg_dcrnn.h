@@ -332,6 +332,12 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
 int eeg_dcrnn_teacher_flags(uint64_t* rng_state, int64_t* samples_seen, int64_t increment, double cl_decay_steps, int T,
                             int32_t* flags, void* stream);
 
+/* eeg_dcrnn_teacher_flags with the increment in device memory: increment[0] (DEVICE int64) is read on the stream -- n_valid of
+ * eeg_dcrnn_gather_clips_tail, the real global size of an epoch's short last batch -- so `step += batch_size` stays exact inside a
+ * replayed graph. */
+int eeg_dcrnn_teacher_flags_dev(uint64_t* rng_state, int64_t* samples_seen, const int64_t* increment, double cl_decay_steps, int T,
+                                int32_t* flags, void* stream);
+
 /* Data augmentation drawn on the device (data/dataloader_detection.py:233-256 `_random_reflect`, `_random_scale`, applied per
  * sample at :384-389 in the DataLoader workers).  rng_used = the {seed, offset} pair eeg_dcrnn_rng_take handed out for B
  * counters; clip b uses counter offset + b: word 0's top bit = the reflection coin, word 1 / 2^32 = u, scale = 0.8 + 0.4 u.
@@ -367,6 +373,20 @@ int eeg_dcrnn_gather_clips(const float* x_pool, float* x_out, size_t x_row_bytes
                            const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
                            const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, void* stream);
 
+/* eeg_dcrnn_gather_clips_tail: the gather of an epoch that keeps its short last batch (the reference's DataLoader default,
+ * drop_last=False).  The copy, the wrap, the clamp, the two launches and the cursor's advance by B*world are those of
+ * eeg_dcrnn_gather_clips: the slots behind the end of the epoch hold real clips.  Three DEVICE outputs, written by the gather launch
+ * (in front of the cursor's advance), say which slots count; with pos_b = cursor[0] + rank*B + b, the cursor as it stands:
+ *     clip_w[b]  (float[B])  = 1 if 0 <= pos_b < n_perm, else 0
+ *     n_valid[0] (int64[1])  = clamp(n_perm - cursor[0], 0, B*world): the clips of the step over ALL ranks
+ *     denom[0]   (float[1])  = max(n_valid, 1) / world: the divisor of this rank's criterion (the _w entry points below) -- behind
+ *                              the summed all-reduce and its 1/world, sum_valid g_b / denom is the mean over the n_valid clips.
+ * A full batch gives clip_w = 1 and denom = B exactly. */
+int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_bytes, const float* y_pool, float* y_out, size_t y_row_bytes,
+                                const void* label_pool, void* label_out, int label_bytes, const int64_t* len_pool, int64_t* len_out,
+                                const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, float* clip_w,
+                                float* denom, int64_t* n_valid, void* stream);
+
 /* utils.last_relevant_pytorch (utils.py:346-357): last[b] = Htop[lengths[b]-1, b]. Htop (T,B,NH). */
 int eeg_dcrnn_gather_last(const float* Htop, const int64_t* lengths, int T, int B, int NH,
                           float* last, void* stream);
@@ -396,6 +416,15 @@ size_t eeg_dcrnn_cls_head_loss_ws_floats(int B, int H, int C);
 int eeg_dcrnn_cls_head_loss(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N,
                             int H, int C, float dropout_p, const uint64_t* rng_used, float* logits, int32_t* arg,
                             float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream);
+/* eeg_dcrnn_cls_head_loss over the clips that count: clip_w (DEVICE float[B]) and denom (DEVICE float[1]) as written by
+ * eeg_dcrnn_gather_clips_tail.  The mean divides by denom[0] instead of B; a clip with clip_w[b] == 0 is selected out (not
+ * multiplied): dlogits = 0 and dz = 0 for it, nothing from it in dW, dbias and loss -- a cross-entropy label outside 0..C-1 there
+ * does not make the loss NaN (on a clip that counts it does) -- while logits and arg are written for every clip.  Same launches and
+ * order of sums: clip_w = 1 and denom = B give the results of eeg_dcrnn_cls_head_loss bit for bit. */
+int eeg_dcrnn_cls_head_loss_w(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N,
+                              int H, int C, float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom,
+                              float* logits, int32_t* arg, float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws,
+                              void* stream);
 /* mask[e] = keep(e) / (1 - p) for e < n: the factors the fused kernels apply for the {seed, offset} pair in rng_used (a forward
  * call's output), materialised -- the parity tests hand them to the oracle. */
 int eeg_dcrnn_dropout_mask(const uint64_t* rng_used, size_t n, float dropout_p, float* mask, void* stream);
@@ -413,6 +442,17 @@ int eeg_dcrnn_ce_logits(const float* logits, const int64_t* y, int B, int C, flo
 size_t eeg_dcrnn_masked_loss_ws_floats(void);
 int eeg_dcrnn_masked_loss(const float* pred, const float* y, size_t n, int use_scaler, float mean, float std_,
                           float mask_val, int kind, float* loss, float* dpred, float* ws, void* stream);
+/* The three criteria over the clips that count (clip_w DEVICE float[B], denom DEVICE float[1]: eeg_dcrnn_gather_clips_tail).
+ * bce / ce: as eeg_dcrnn_cls_head_loss_w -- selection, mean over denom[0].  masked_loss_w: pred / y are B clips of n / B elements
+ * each (n % B == 0), the mask is (y != mask_val) && clip_w[clip] != 0, L = the masked MAE / RMSE over it, and the rank's factor
+ * f = (sum_b clip_w[b]) / denom[0] goes on both outputs: loss[0] = f * L, dpred = f * dL/dpred (no element left: 0 and 0).
+ * With clip_w = 1 and denom = B all three equal their unweighted entry points bit for bit. */
+int eeg_dcrnn_bce_logits_w(const float* logits, const float* y, int B, const float* clip_w, const float* denom, float* loss,
+                           float* dlogits, void* stream);
+int eeg_dcrnn_ce_logits_w(const float* logits, const int64_t* y, int B, int C, const float* clip_w, const float* denom, float* loss,
+                          float* dlogits, void* stream);
+int eeg_dcrnn_masked_loss_w(const float* pred, const float* y, size_t n, int B, const float* clip_w, const float* denom, int use_scaler,
+                            float mean, float std_, float mask_val, int kind, float* loss, float* dpred, float* ws, void* stream);
 /* clip_grad_norm_(max_norm) + torch.optim.Adam(lr, betas, eps, weight_decay = coupled L2) step
  * `step` (1-based) over flat fp32 buffers of n elements (train.py:222-223,273-275).  grads are
  * first multiplied by grad_scale (1/world_size after a summed all-reduce).  ws: 64 floats scratch;

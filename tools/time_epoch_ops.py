@@ -10,6 +10,11 @@
         from the pool (`capture_epoch`; `begin_epoch` -- keys, sort, cursor -- once per 16 steps inside the timed loop);
         with a fresh pinned host batch per step: the step captured on two input sets, the host-to-device copy of batch k+1 on a side
         stream into the set the next replay reads while batch k computes (the method of bench.py's streamed-input pass).
+  (c) the same captured step from a pool whose size is NO multiple of the batch (--pool minus 100 clips): the default sampler
+        (drop_last=True: the unweighted criterion, the short batch dropped) against `EpochSampler(..., drop_last=False)` (the
+        validity gather and the weighted criterion in every step, the epoch one step longer) -- and, with --lib PATH, the default
+        sampler on the other build, the yardstick: the parent has no other step.  `begin_epoch` once per epoch inside the timed
+        loop, as in (b).
 Every figure: warm, `--rounds` rounds alternating between the candidates, each round ~0.1 s per candidate (steps: 40 steps); median
 and spread (min..max) over the rounds.
 usage: python tools/time_epoch_ops.py [--lib PATH] [--rounds 7] [--seed 11] [--out profiles/epoch_time_ops.json]"""
@@ -221,6 +226,47 @@ if other is not None:
     step["resident_median_within_other_libs_range"] = bool(o[1] <= a[0] <= o[2])          # the criterion: plain min..max of the other
     step["resident_median_within_other_libs_range_widened_by_own_spread"] = bool(o[1] - (a[2] - a[1]) <= a[0] <= o[2] + (a[2] - a[1]))
 result["captured_cfg2_step"] = step
+
+# ---- (c) the epoch's short last batch: drop_last=True against drop_last=False ------------------------------------------------------
+POOL_ODD = POOL - 100
+assert POOL_ODD % B != 0 and POOL_ODD >= B
+ds_odd = DeviceDataset(pool_x[:POOL_ODD], ds.y[:POOL_ODD].contiguous())
+
+
+def epoch_stepper(drop_last, lib=None):
+    wrap = (lambda f: f) if lib is None else (lambda f: with_lib(lib, f))
+    st, sm = wrap(stepper)(), EpochSampler(POOL_ODD, B, opt.seed, 0, 1, device=dev, drop_last=drop_last)
+
+    def prepare():
+        st.begin_epoch(0, 1000, sampler=sm)
+        keep = st.snapshot()
+        st.capture_epoch(ds_odd, sm, supports, include_update=True)
+        st.restore(keep)
+    wrap(prepare)()
+    calls = {"k": 0}
+
+    def run():
+        if calls["k"] % sm.steps_per_epoch == 0:
+            st.begin_epoch((calls["k"] // sm.steps_per_epoch) % 1000, 1000)
+        calls["k"] += 1
+        return st.replay_step(0)
+    return wrap(run), sm
+
+
+cands, samplers = {}, {}
+for name, drop_last, lib in (("drop_last_true", True, None), ("drop_last_false", False, None), ("drop_last_true_other_lib", True, other)):
+    if name.endswith("other_lib") and other is None:
+        continue
+    cands[name], samplers[name] = epoch_stepper(drop_last, lib)
+res = alternate(cands, opt.rounds, reps=40)
+tail = {"pool_clips": POOL_ODD, "steps_per_epoch": {k: v.steps_per_epoch for k, v in samplers.items()}, "ms": stats(res)}
+if other is not None:
+    o = res["drop_last_true_other_lib"]
+    tail["other_lib_spread_ms"] = o[2] - o[1]
+    for k in ("drop_last_true", "drop_last_false"):
+        tail[f"{k}_minus_other_lib_ms"] = res[k][0] - o[0]
+        tail[f"{k}_slower_than_other_lib_by_more_than_its_spread"] = bool(res[k][0] - o[0] > o[2] - o[1])
+result["short_last_batch_cfg2_step"] = tail
 torch.cuda.synchronize()
 text = json.dumps(result, indent=1)
 print(text)
