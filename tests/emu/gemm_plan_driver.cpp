@@ -1,5 +1,6 @@
-// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h and csrc/spec_launch.h for the calls read from stdin, one line
-// each (see tests/test_gemm_plans.py, tests/test_spec_plans.py).  Host code only: the headers must compile without kernel bodies.
+// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h, csrc/spec_launch.h and csrc/seq_launch.h for the calls read from
+// stdin, one line each (see tests/test_gemm_plans.py, tests/test_spec_plans.py, tests/test_seq_kernels.py).  Host code only: the first
+// two headers must compile without kernel bodies; seq_launch.h brings kernels_seq.h along, which is host code under platform_emu.h.
 //   nn   nseg F R nct_total ldc O batch_major quad_pack bf3_nct num_cus KNOBS  ->  kind t1 t2 t3 gx gy block lds error
 //   tn   nseg F R O batch_major offer_quad num_cus KNOBS                       ->  kind t1 t2 t3 nsplit rps gx gy block lds remap error
 //   pair M H R num_cus KNOBS   (the two h-part problems of a cell)             ->  1 / 0: one paired launch or not
@@ -12,12 +13,18 @@
 //   snn  K Sp G nct num_cus SKNOBS        ->  launch
 //   stn  Fin H Sp G num_cus SKNOBS        ->  launch (fused) or x-part launch ; pair launch, then spg_x rps_x spg_h rps_h px pg pc
 //   sdx  Fin N T B num_cus SKNOBS         ->  launch (fused) or grouped NN launch ; mix launch, then needs_dxh
+// The recurrent family: every field of SeqCall in its order, dev knobs and the probe flag included (has_* asks the predicates of
+// kernels_seq.h the plans are built on):
+//   sfwd H M N T B plane_stride spectral Sp SpE one_wave no_spec stream probe   ->  kind probe nks block grid lds error
+//   sbwd (the same fields)                                                      ->  kind probe nks block grid lds error
+//   shas H M N                                          ->  nks two_wave spec probe stream h_supported m_supported dev_build
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "gemm_launch.h"
 #include "spec_launch.h"
+#include "seq_launch.h"
 using namespace eeg;
 
 static bool knobs(GemmKnobs& k) {
@@ -108,11 +115,32 @@ static bool spec_line(const char* op, char* out) {
     return true;
 }
 
+// one recurrent-family line; false: not such an op
+static bool seq_line(const char* op, char* out) {
+    if (!strcmp(op, "shas")) {
+        int H, M, N;
+        if (scanf("%d %d %d", &H, &M, &N) != 3) exit(2);
+        const int nks = seq_nks(N);
+        sprintf(out, "%d %d %d %d %d %d %d %d", nks, seq_has_two_wave(H, M, nks) ? 1 : 0, seq_has_spec(H, M, nks) ? 1 : 0, seq_has_probe(H, M, nks) ? 1 : 0,
+                seq_has_stream(H, M) ? 1 : 0, seq_h_supported(H) ? 1 : 0, seq_m_supported(M) ? 1 : 0, kDevBuild ? 1 : 0);
+        return true;
+    }
+    if (strcmp(op, "sfwd") && strcmp(op, "sbwd")) return false;
+    SeqCall c{};
+    int spectral, probe;
+    if (scanf("%d %d %d %d %d %zu %d %d %d %d %d %d %d", &c.H, &c.M, &c.N, &c.T, &c.B, &c.plane_stride, &spectral, &c.Sp, &c.SpE, &c.knob_one_wave,
+              &c.knob_no_spec, &c.knob_stream, &probe) != 13) exit(2);
+    c.spectral = spectral != 0; c.probe = probe != 0;
+    const SeqPlan p = op[1] == 'f' ? seq_fwd_plan(c) : seq_bwd_plan(c);
+    sprintf(out, "%d %d %d %d %d %zu %d", (int)p.kind, p.probe ? 1 : 0, p.nks, p.block, p.grid, p.lds, p.error);
+    return true;
+}
+
 int main() {
     char op[8], out[512];
     while (scanf("%7s", op) == 1) {
         int bm, quad;
-        if (spec_line(op, out)) {
+        if (spec_line(op, out) || seq_line(op, out)) {
         } else if (!strcmp(op, "nn")) {
             NnCall c{};
             if (scanf("%d %d %d %d %d %d %d %d %d %d", &c.nseg, &c.F, &c.R, &c.nct_total, &c.ldc, &c.O, &bm, &quad, &c.bf3_nct, &c.num_cus) != 10 || !knobs(c.knobs)) return 2;

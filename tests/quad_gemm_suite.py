@@ -115,15 +115,16 @@ ROLES = ("gemm_nn_xw", "gemm_nn_dx", "gemm_tn_x", "gemm_tn_h", "gemm_tn_hg", "ge
 
 
 def hops(case):
-    return (2 if case["filt"] == "dual_random_walk" else 1) * case["k"] + 1
+    return (2 if case["filt"] == "dual_random_walk" else 1) * case["k"] + 1      # (laplacian, random_walk: one support)
 
 
 # ---- what a layer plans: the calls of csrc/api.cpp restated, answered by the plan driver ------------------------------------------
-def build_plan_driver(out_dir):
-    """tests/emu/gemm_plan_driver.cpp compiled as tests/test_gemm_plans.py does (host code only) -> path of the executable"""
+def build_plan_driver(out_dir, dev=True):
+    """tests/emu/gemm_plan_driver.cpp compiled as tests/test_gemm_plans.py does (host code only) -> path of the executable.  dev=False:
+    without -DEEG_DEV, as the product library sees the headers (no probe instantiations)"""
     exe = os.path.join(str(out_dir), "gemm_plan_driver")
-    subprocess.check_call([CLANG if os.path.exists(CLANG) else "clang++", "-x", "c++", "-std=c++17", "-O1", "-g", "-DEEG_PLATFORM_HEADER=\"platform_emu.h\"",
-                           "-DEEG_DEV", "-I", os.path.join(HERE, "emu"), "-I", CSRC, "-Wno-unused-function", "-Wno-unknown-attributes",
+    subprocess.check_call([CLANG if os.path.exists(CLANG) else "clang++", "-x", "c++", "-std=c++17", "-O1", "-g", "-DEEG_PLATFORM_HEADER=\"platform_emu.h\""] +
+                          (["-DEEG_DEV"] if dev else []) + ["-I", os.path.join(HERE, "emu"), "-I", CSRC, "-Wno-unused-function", "-Wno-unknown-attributes",
                            os.path.join(HERE, "emu", "gemm_plan_driver.cpp"), "-o", exe])
     return exe
 
@@ -218,11 +219,27 @@ def emu_dims(case):
 
 
 # ---- operands, the float64 reference --------------------------------------------------------------------------------------------
+def make_supports(case, b, g):
+    """per-clip random directed graphs (the quad table, and every case that does not say otherwise); case["sup"] = "shared": ONE such
+    graph in its 2-D form (p_batched = 0 on the general path), "symmetric": the scaled Laplacian of one random undirected graph in its
+    2-D form, which the spectral form accepts (tests/seq_kernel_suite.py)"""
+    kind = case.get("sup", "per_clip")
+    if kind == "per_clip":
+        return ps.random_supports(case["n"], b, case["filt"], g)
+    if kind == "shared":
+        return [s[0].clone() for s in ps.random_supports(case["n"], 1, case["filt"], g)]
+    assert kind == "symmetric" and case["filt"] == "laplacian", case
+    a = torch.rand(case["n"], case["n"], generator=g)
+    a = (0.5 * (a + a.t())).numpy()
+    a[range(case["n"]), range(case["n"])] = 1.0
+    return orc.compute_supports(a, "laplacian")
+
+
 def make_operands(case, t, b, seed):
     g = torch.Generator().manual_seed(seed)
     n, h, fin, m = case["n"], case["h"], case["fin"], hops(case)
     kdim = (fin + h) * m
-    op = dict(sup=ps.random_supports(n, b, case["filt"], g),
+    op = dict(sup=make_supports(case, b, g),
               xb=torch.randn(b, t, n, fin, generator=g),                                   # batch-major storage; the layer sees (T,B,N,Fin)
               h0=0.5 * torch.randn(b, n * h, generator=g) if case["h0"] else None,
               wg=torch.randn(kdim, 2 * h, generator=g) / math.sqrt(kdim), bg=0.1 * torch.randn(2 * h, generator=g),
@@ -231,6 +248,8 @@ def make_operands(case, t, b, seed):
               lengths=torch.randint(1, t + 1, (b,), generator=g) if case["lengths"] else None)
     if op["lengths"] is not None:
         op["lengths"][0] = t                                                              # (one clip of full length)
+        if case.get("len1"):
+            op["lengths"][b - 1] = 1                                                      # (and one that ends after its first step)
         op["w"] = op["w"] * (torch.arange(t).view(t, 1, 1) < op["lengths"].view(1, b, 1))
     return op
 
@@ -294,7 +313,11 @@ def run_layer(case, op, w, wsel, device):
     t, b = w.shape[:2]
     sup = [s.to(device) for s in op["sup"]]
     p, p_batched = ops.hop_polys(sup, case["k"], b)
-    assert p_batched == 1                                                                 # per-clip graphs: the general path
+    assert p_batched == (1 if case.get("sup", "per_clip") == "per_clip" else 0)           # per-clip graphs: the general path
+    basis = None
+    if case.get("sup") == "symmetric":                                                    # the layer is handed the eigenbasis: the spectral form where it applies
+        basis = ops.shared_spectral_basis(sup, case["k"])
+        assert basis is not None, "the scaled Laplacian of an undirected graph is symmetric"
     if case["bm"]:
         dims = _lib.LayerDims(t, b, n, h, case["fin"], m, 0, 1)
         assert _lib.get_lib().query("eeg_dcrnn_batch_major_ok", ctypes.byref(dims)) == 2
@@ -308,13 +331,26 @@ def run_layer(case, op, w, wsel, device):
         x = xb.detach().requires_grad_(True)
         q = {k: v.detach().requires_grad_(True) for k, v in par.items()}
         h0d = h0.detach().requires_grad_(True) if h0 is not None else None
-        hseq, hsel = ops.dcgru_layer(x.transpose(0, 1) if case["bm"] else x, h0d, p, p_batched, q["wg"], q["bg"], q["wc"], q["bc"],
-                                     n, h, m, case["act"], lengths)
+        if basis is None:
+            hseq, hsel = ops.dcgru_layer(x.transpose(0, 1) if case["bm"] else x, h0d, p, p_batched, q["wg"], q["bg"], q["wc"], q["bc"],
+                                         n, h, m, case["act"], lengths)
+        else:
+            out = ops.dcgru_layer_ex(x, 0, h0d, p, p_batched, q["wg"], q["bg"], q["wc"], q["bc"], n, h, m, case["act"], lengths, basis=basis)
+            hseq, hsel = out.hseq, out.hsel
         _loss(hseq, hsel if lengths is not None else None, wd, wseld).backward()
         grads = dict(dX=x.grad.transpose(0, 1) if case["bm"] else x.grad, dWg=q["wg"].grad, dbg=q["bg"].grad, dWc=q["wc"].grad, dbc=q["bc"].grad)
         if h0d is not None:
             grads["dh0"] = h0d.grad
         return hseq.detach(), grads
+
+    def forward_only():
+        """the same layer under torch.no_grad(): nothing is saved for a backward (Rs == nullptr in the recurrent kernel)"""
+        with torch.no_grad():
+            if basis is None:
+                return ops.dcgru_layer(xb.transpose(0, 1) if case["bm"] else xb, h0, p, p_batched, par["wg"], par["bg"], par["wc"], par["bc"],
+                                       n, h, m, case["act"], lengths)[0]
+            return ops.dcgru_layer_ex(xb, 0, h0, p, p_batched, par["wg"], par["bg"], par["wc"], par["bc"], n, h, m, case["act"], lengths, basis=basis).hseq
+    run.forward_only = forward_only
     return run
 
 

@@ -7,6 +7,7 @@ import pytest
 import cases
 import parity_suite as ps
 import quad_gemm_suite as qg
+import seq_kernel_suite as sk
 import spec_plan_suite as sp
 
 
@@ -140,8 +141,9 @@ def test_single_wave_forward_kernel_at_default_width(emulator, adj3d, golden):
     by the cycle probe and for every other width / hop count) must give the same results at that shape."""
     emulator.call("eeg_dcrnn_set_tuning", 12, 1)
     try:
-        ps.check_cell_case("lap_default", golden, adj3d, "cpu")
-        ps.check_cell_case("lap_l1_default", golden, adj3d, "cpu")
+        for tag in ("lap_default", "lap_l1_default"):
+            ran = ps.kernels_run(lambda: ps.check_cell_case(tag, golden, adj3d, "cpu"))
+            assert set(ran["seq_fwd"]) == {sk.fwd1(64, 3, 5)}, ran["seq_fwd"]       # the forced kernel is the one that ran
     finally:
         emulator.call("eeg_dcrnn_set_tuning", 12, 0)
 
@@ -153,9 +155,34 @@ def test_streamed_weight_bptt_kernel(emulator, adj3d, filt, k, lengths, act):
     beyond 1.5 clips per CU at M >= 4) forced on: whole model vs the oracle."""
     emulator.call("eeg_dcrnn_set_tuning", 3, 1)
     try:
-        ps.check_vs_oracle_random("cpu", filt, 8, 64, 2, 3, 3, 4, adj3d, seed=5, lengths=lengths, act=act, k=k)
+        ran = ps.kernels_run(lambda: ps.check_vs_oracle_random("cpu", filt, 8, 64, 2, 3, 3, 4, adj3d, seed=5, lengths=lengths, act=act, k=k))
+        assert set(ran["seq_bwd"]) == {sk.stream((2 if filt == "dual_random_walk" else 1) * k + 1)}, ran["seq_bwd"]      # the forced kernel ran, in both layers
     finally:
         emulator.call("eeg_dcrnn_set_tuning", 3, 0)
+
+
+@pytest.mark.parametrize("name", list(sk.EMU_CASES))
+def test_seq_kernel_case_table(emulator, name):
+    """The small cases of tests/seq_kernel_suite.py (one layer per reachable instance of the recurrent kernels; on the MI355X:
+    tests/test_seq_kernels.py, all of them) -- at least one per kernel template and per hidden size.  Same float64 reference, same
+    tolerances, the same proof by the recorder that the named kernels took seq_fwd and seq_bwd, the same bit-equal forward without
+    saving.  (The walk cases stay on the MI355X: the smallest of them, 257 clips of 21 nodes at 16 units, takes 18 s here.)"""
+    sk.check_case(name, "cpu")
+
+
+@pytest.mark.parametrize("name", list(sk.KNOB_CASES))
+def test_seq_kernel_instances_only_dev_knobs_reach(emulator, name):
+    """The one-wave kernels at 64 units, M <= 3, N <= 20 (a product build: only beyond the 2 GB a descriptor reaches) under knobs 12 / 13,
+    and the streamed BPTT kernel at M = 1, 2, 3 (a product build: never) and M = 5 at a small clip count under knob 3: the cases of the
+    table that the two-wave kernels take by default, with the same checks"""
+    base, knobs, expect = sk.KNOB_CASES[name]
+    for key, value in knobs.items():
+        emulator.call("eeg_dcrnn_set_tuning", key, value)
+    try:
+        sk.check_case(base, "cpu", expect=expect)
+    finally:
+        for key in knobs:
+            emulator.call("eeg_dcrnn_set_tuning", key, 0)
 
 
 def test_spectral_weight_gradients_fused_and_as_three_grouped_launches(emulator, adj3d):
