@@ -13,6 +13,7 @@
 #include "../../include/eeg_dcrnn_prof.h"
 #include "kernels_decoder.h"
 #include "kernels_diffuse.h"
+#include "kernels_eval.h"
 #include "kernels_data.h"
 #include "kernels_feat.h"
 #include "kernels_gemm.h"
@@ -1173,6 +1174,74 @@ int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_
         return fail("gather_clips_tail: clip_w / denom / n_valid must be aligned to their element size");
     return gather_clips_launch(x_pool, x_out, x_row_bytes, y_pool, y_out, y_row_bytes, label_pool, label_out, label_bytes, len_pool, len_out, perm,
                                n_perm, P, cursor, B, rank, world, clip_w, denom, n_valid, stream);
+}
+
+/* ---- the evaluation pass: per-clip scores, scores of the pool ------------------------------------ */
+static_assert(EEG_EVAL_MAX_CLIPS == kEvalMaxClips && EEG_EVAL_RECORD_HEAD == kEvalRecordHead, "include/eeg_dcrnn.h and kernels_eval.h disagree");
+int eeg_dcrnn_eval_scores(const float* logits, const void* label_pool, int label_bytes, const float* clip_w, const int64_t* cursor, int B, int C,
+                          int rank, int world, int64_t P, float* probs, float* losses, void* stream) {
+    if (logits == nullptr || label_pool == nullptr || clip_w == nullptr || cursor == nullptr) return fail("eval_scores: null logits / label_pool / clip_w / cursor");
+    if (probs == nullptr || losses == nullptr) return fail("eval_scores: null probs / losses");
+    if (B < 1 || C < 1) return fail("eval_scores: empty batch (B=%d, C=%d)", B, C);
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("eval_scores: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (world < 1 || rank < 0 || rank >= world) return fail("eval_scores: rank=%d of world=%d", rank, world);
+    if (label_bytes != (C == 1 ? 4 : 8)) return fail("eval_scores: label_bytes=%d (float32 labels for C = 1, int64 classes for C > 1; C=%d)", label_bytes, C);
+    if ((((uintptr_t)logits | (uintptr_t)clip_w | (uintptr_t)probs | (uintptr_t)losses) & 3) != 0 ||
+        (((uintptr_t)cursor | (C == 1 ? 0 : (uintptr_t)label_pool)) & 7) != 0 || ((uintptr_t)label_pool & 3) != 0)
+        return fail("eval_scores: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("eval_scores", eval_scores_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, S_(stream), logits, label_pool, clip_w,
+                 reinterpret_cast<const long long*>(cursor), (long long)B * world, (long long)rank * B, (long long)P, B, C, probs, losses);
+    return check_launch("eval_scores");
+}
+static int eval_npad(int64_t P) {
+    int n = 1;
+    while (n < P) n <<= 1;
+    return n;
+}
+size_t eeg_dcrnn_eval_metrics_ws_bytes(int64_t P, int C) {
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS || C < 1) return 0;
+    return C == 1 ? sizeof(unsigned) * (size_t)eval_npad(P) + sizeof(int) * ((size_t)eval_npad(P) + 1) : 0;
+}
+int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_bytes, const float* losses, int64_t P, int C, int search,
+                           double thresh, void* ws, int64_t* record, void* stream) {
+    if (probs == nullptr || labels == nullptr || losses == nullptr || record == nullptr) return fail("eval_metrics: null probs / labels / losses / record");
+    if (C < 1 || C > 1024) return fail("eval_metrics: C=%d classes unsupported (1..1024)", C);
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("eval_metrics: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (label_bytes != (C == 1 ? 4 : 8)) return fail("eval_metrics: label_bytes=%d (float32 labels for C = 1, int64 classes for C > 1; C=%d)", label_bytes, C);
+    if ((((uintptr_t)probs | (uintptr_t)losses | (uintptr_t)labels | (uintptr_t)ws) & 3) != 0 || ((uintptr_t)record & 7) != 0 ||
+        (C > 1 && ((uintptr_t)labels & 7) != 0))
+        return fail("eval_metrics: pointers must be aligned to their element size");
+    hipStream_t st = S_(stream);
+    long long* rec = reinterpret_cast<long long*>(record);
+    if (C > 1) {
+        EEG_LAUNCH_P("eval_metrics", eval_confusion_kernel, dim3(1), dim3(kEvalScanThreads), kEvalScanThreads * sizeof(long long), st, probs,
+                     static_cast<const long long*>(labels), losses, (int)P, C, rec);
+        return check_launch("eval_confusion");
+    }
+    if (ws == nullptr) return fail("eval_metrics: null workspace (eeg_dcrnn_eval_metrics_ws_bytes)");
+    if (!(thresh == thresh)) return fail("eval_metrics: the threshold is NaN");
+    const int npad = eval_npad(P), tile = kEvalSortTile;
+    unsigned* keys = static_cast<unsigned*>(ws);
+    int* neg_before = reinterpret_cast<int*>(keys + npad);
+    const float* lab = static_cast<const float*>(labels);
+    EEG_LAUNCH_P("eval_metrics", eval_keys_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, probs, lab, (int)P, npad, keys);
+    if (check_launch("eval_keys")) return 1;
+    const int ntile = npad > tile ? npad / tile : 1;
+    const size_t tile_lds = (size_t)tile * sizeof(unsigned);
+    EEG_LAUNCH_P("eval_metrics", eval_sort_tile_kernel, dim3(ntile), dim3(kEvalSortThreads), tile_lds, st, keys, npad, 2, npad < tile ? npad : tile);
+    if (check_launch("eval_sort_tile")) return 1;
+    const int step_grid = ceil_div(npad / 2, kEvalSortThreads * kEvalStepPairs);
+    for (int k = 2 * tile; k <= npad && k > 0; k <<= 1) {
+        for (int j = k >> 1; j >= tile; j >>= 1) {
+            EEG_LAUNCH_P("eval_metrics", eval_sort_step_kernel, dim3(step_grid), dim3(kEvalSortThreads), 0, st, keys, npad, j, k);
+            if (check_launch("eval_sort_step")) return 1;
+        }
+        EEG_LAUNCH_P("eval_metrics", eval_sort_tile_kernel, dim3(ntile), dim3(kEvalSortThreads), tile_lds, st, keys, npad, k, k);
+        if (check_launch("eval_sort_tile")) return 1;
+    }
+    EEG_LAUNCH_P("eval_metrics", eval_scan_kernel, dim3(1), dim3(kEvalScanThreads), 4 * kEvalScanThreads * sizeof(long long), st, keys, probs, lab,
+                 losses, (int)P, search ? 1 : 0, thresh, neg_before, rec);
+    return check_launch("eval_scan");
 }
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */

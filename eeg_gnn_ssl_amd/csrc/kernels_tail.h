@@ -7,6 +7,23 @@
 
 namespace eeg {
 
+// The per-clip terms of the two criteria, shared by the training kernels below and by the evaluation pass (kernels_eval.h:
+// eval_scores_kernel), so that a clip's evaluation loss is the training criterion of that clip as a batch of one, bit for bit.
+__device__ __forceinline__ float bce_logits_term(float v, float t) { return fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v))); }
+// log-sum-exp of one row of C logits
+__device__ __forceinline__ float ce_row_lse(const float* __restrict__ r, int C) {
+    float mx = r[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
+    return mx + logf(se);
+}
+// a label outside 0..C-1 (torch: a device-side assert that ends the process) makes the LOSS NaN instead of reading logits out of bounds
+__device__ __forceinline__ float ce_logits_term(const float* __restrict__ r, int C, long long tl, float lse) {
+    const bool t_ok = tl >= 0 && tl < (long long)C;
+    return lse - (t_ok ? r[(int)tl] : __builtin_nanf(""));
+}
+
 // nn.BCEWithLogitsLoss() (mean) on logits (B,), targets y (B,): loss[0], dlogits = (sigmoid(x)-y)/B.
 // single workgroup (B is a batch size), fixed-order tree reduction.
 __global__ void bce_logits_kernel(const float* __restrict__ x, const float* __restrict__ y, int B,
@@ -15,7 +32,7 @@ __global__ void bce_logits_kernel(const float* __restrict__ x, const float* __re
     float acc = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
         const float v = x[i], t = y[i];
-        acc += fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
+        acc += bce_logits_term(v, t);
         dx[i] = (1.f / (1.f + expf(-v)) - t) / (float)B;
     }
     sm[threadIdx.x] = acc;
@@ -34,17 +51,11 @@ __global__ void ce_logits_kernel(const float* __restrict__ x, const long long* _
     float acc = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
         const float* r = x + (size_t)i * C;
-        float mx = r[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
-        const float lse = mx + logf(se);
-        // a label outside 0..C-1 (torch: a device-side assert that ends the process) makes the LOSS NaN instead of reading logits out
-        // of bounds; the gradient of that clip is the softmax alone
+        const float lse = ce_row_lse(r, C);
+        // a label outside 0..C-1: the loss is NaN (ce_logits_term); the gradient of that clip is the softmax alone
         const long long tl = y[i];
-        const bool t_ok = tl >= 0 && tl < (long long)C;
-        const int t = t_ok ? (int)tl : -1;
-        acc += lse - (t_ok ? r[t] : __builtin_nanf(""));
+        const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
+        acc += ce_logits_term(r, C, tl, lse);
         for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (expf(r[c] - lse) - (c == t ? 1.f : 0.f)) / (float)B;
     }
     sm[threadIdx.x] = acc;
@@ -68,7 +79,7 @@ __global__ void bce_logits_w_kernel(const float* __restrict__ x, const float* __
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
         if (clip_w[i] == 0.f) { dx[i] = 0.f; continue; }
         const float v = x[i], t = y[i];
-        acc += fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
+        acc += bce_logits_term(v, t);
         dx[i] = (1.f / (1.f + expf(-v)) - t) / div;
     }
     sm[threadIdx.x] = acc;
@@ -90,15 +101,10 @@ __global__ void ce_logits_w_kernel(const float* __restrict__ x, const long long*
             continue;
         }
         const float* r = x + (size_t)i * C;
-        float mx = r[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
-        const float lse = mx + logf(se);
+        const float lse = ce_row_lse(r, C);
         const long long tl = y[i];                                  // (a label outside 0..C-1 on a clip that counts: NaN, as ce_logits_kernel)
-        const bool t_ok = tl >= 0 && tl < (long long)C;
-        const int t = t_ok ? (int)tl : -1;
-        acc += lse - (t_ok ? r[t] : __builtin_nanf(""));
+        const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
+        acc += ce_logits_term(r, C, tl, lse);
         for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (expf(r[c] - lse) - (c == t ? 1.f : 0.f)) / div;
     }
     sm[threadIdx.x] = acc;

@@ -1,0 +1,182 @@
+"""The reference's evaluation pass (train.py:289-326,332-431: after every epoch, for checkpoint selection and early stopping) on the
+device, for the detection and classification tasks.
+
+`evaluate` / `predict` (train_step.py) run the model on whatever batches they are handed and finish on the host (`.cpu()` + sklearn):
+they have no data chain -- a raw or time-domain pool cannot be evaluated -- and no lengths for the correlation graph.  A
+`DeviceEvaluator` hangs off the `TrainStep`, which owns both: a pass walks a `DeviceDataset` IN ORDER through an evaluator-owned
+`EpochSampler` (identity permutation, short last batch kept), runs the step's data chain without augmentation, the `save=False`
+forward and the head, and writes every clip's probability and criterion term into fixed buffers (`ops.eval_scores`).  The body of a
+step is captured once as one HIP graph and replayed; the graph reads the parameters in place, so it stays valid while training
+updates them.  Behind the last step `ops.eval_metrics` reduces the buffers to one small integer record (the project's own sort, AUROC
+numerator, max-F1 threshold, confusion counts) which the host reads in a single copy and finishes in float64.
+
+`evaluate`, `predict` and `evaluate_ssl` are unchanged and remain the yardstick; SSL evaluation stays with `evaluate_ssl`."""
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Optional
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import ops
+from .device_data import EpochSampler
+
+# words of the record (include/eeg_dcrnn.h: eeg_dcrnn_eval_metrics)
+_N, _POS, _NEG, _NUM, _THRESH, _TP, _FP_, _FN, _TN, _BAD_LABELS, _BAD_PROBS, _LOSS, _SEARCHED, _FOUND = range(14)
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else 0.0       # (a class without predictions / support scores 0: sklearn's zero_division default)
+
+
+def scores_from_record(record, task: str, best_thresh: float = 0.5):
+    """The reference's score dictionary (the keys and order of `evaluate`) from the int64 record of `ops.eval_metrics`, in float64 on the
+    host.  Non-zero flag counters (labels outside the task's classes, probabilities outside [0, 1] or NaN) raise ValueError."""
+    rec = np.asarray(record.cpu() if torch.is_tensor(record) else record, dtype=np.int64)
+    n = int(rec[_N])
+    if rec[_BAD_LABELS] or rec[_BAD_PROBS]:
+        raise ValueError(f"eval_metrics: {int(rec[_BAD_LABELS])} labels outside the task's classes and {int(rec[_BAD_PROBS])} probabilities "
+                         f"outside [0, 1] (or NaN) among {n} clips")
+    loss = float(rec[_LOSS:_LOSS + 1].view(np.float64)[0]) / n
+    if task == "detection":
+        n_pos, n_neg = int(rec[_POS]), int(rec[_NEG])
+        tp, fp, fn, tn = (int(rec[i]) for i in (_TP, _FP_, _FN, _TN))
+        if rec[_SEARCHED]:
+            if not rec[_FOUND]:
+                raise ValueError("eval_metrics: the threshold search has no candidate (no positive clip: F1 is undefined everywhere, "
+                                 "as in utils.thresh_max_f1)")
+            best_thresh = float(rec[_THRESH:_THRESH + 1].view(np.float64)[0])
+        if n_pos == 0 or n_neg == 0:
+            # one class only: whatever utils.eval_dict does on such labels (sklearn's AUROC is undefined there), from the same counts
+            from . import utils
+            y = np.array([1] * n_pos + [0] * n_neg)
+            y_pred = np.array([1] * tp + [0] * fn + [1] * fp + [0] * tn)
+            scores, _, _ = utils.eval_dict(y_pred=y_pred, y=y, y_prob=y_pred.astype(np.float64), average="binary")
+        else:
+            scores = {"acc": (tp + tn) / n, "F1": _ratio(2 * tp, 2 * tp + fp + fn), "precision": _ratio(tp, tp + fp),
+                      "recall": _ratio(tp, tp + fn), "auroc": int(rec[_NUM]) / (2.0 * n_pos * n_neg)}
+    else:
+        c = int(round((rec.size - ops.EVAL_RECORD_HEAD) ** 0.5))
+        cm = rec[ops.EVAL_RECORD_HEAD:].reshape(c, c)                # row = label, column = prediction
+        support, predicted, hit = cm.sum(axis=1), cm.sum(axis=0), np.diag(cm)
+        w = support / float(support.sum())
+        scores = {"acc": float(hit.sum()) / n,
+                  "F1": float(sum(w[k] * _ratio(2 * hit[k], support[k] + predicted[k]) for k in range(c))),
+                  "precision": float(sum(w[k] * _ratio(hit[k], predicted[k]) for k in range(c))),
+                  "recall": float(sum(w[k] * _ratio(hit[k], support[k]) for k in range(c)))}
+    res = [("loss", loss), ("acc", scores["acc"]), ("F1", scores["F1"]), ("recall", scores["recall"]), ("precision", scores["precision"]),
+           ("best_thresh", best_thresh)]
+    if "auroc" in scores:
+        res.append(("auroc", scores["auroc"]))
+    return OrderedDict(res)
+
+
+class DeviceEvaluator:
+    """`TrainStep.evaluator(dataset, batch_size, supports=None)`: evaluation passes of the step's model over `dataset` on the device.
+
+    supports: None (correlation graphs built on the device -- of the unpadded clip when the step has `padding_val` and the dataset a
+    length pool) or the shared graph: the rule of `TrainStep.step_from`.  A pass is ceil(P / (batch_size * world)) steps over the pool
+    in order; rank r takes the slots cursor + r * batch_size .. of every step, and `probs` / `losses` go through one summed
+    all-reduce behind the last step (disjoint slots, zeros elsewhere).  After `run`:
+        probs   (P,) float32 (detection) / (P, C) (classification), pool order, on the device
+        losses  (P,) float32, the per-clip criterion terms
+        record  the integer record of the pass (`ops.eval_metrics`), on the host
+    The buffers keep their addresses; the next `run` overwrites them.  P <= ops.EVAL_MAX_CLIPS (2^20)."""
+
+    def __init__(self, step, dataset, batch_size: int, supports=None, rank: Optional[int] = None, world: Optional[int] = None):
+        if step.task == "ssl":
+            raise ValueError("DeviceEvaluator: task='ssl' has no per-clip scores; its evaluation pass is train_step.evaluate_ssl")
+        dev = step.fp.flat.device
+        if dataset.device != dev:
+            raise ValueError(f"DeviceEvaluator: dataset on {dataset.device}, model on {dev}: one device")
+        if len(dataset) > ops.EVAL_MAX_CLIPS:
+            raise ValueError(f"DeviceEvaluator: the pool holds P={len(dataset)} clips, one pass takes at most {ops.EVAL_MAX_CLIPS} "
+                             f"(ops.EVAL_MAX_CLIPS); evaluate it in parts")
+        want = torch.float32 if step.task == "detection" else torch.int64
+        if dataset.y_is_target or dataset.y.dtype != want:
+            raise ValueError(f"DeviceEvaluator(task={step.task!r}): y of the dataset must be the labels (P,) as {want}, got {dataset.y.dtype} "
+                             f"{tuple(dataset.y.shape)}")
+        if step.padding_val is not None and dataset.seq_lengths is None:
+            raise ValueError("DeviceEvaluator: TrainStep(padding_val=...) evaluates variable-length clips: the dataset needs a seq_lengths "
+                             "pool (DeviceDataset(x, y, seq_lengths=...))")
+        self.classes = int(step.model.fc.weight.shape[0])
+        if (step.task == "detection") != (self.classes == 1):
+            raise ValueError(f"DeviceEvaluator(task={step.task!r}): the model's head has {self.classes} outputs")
+        self.step, self.dataset, self.supports = step, dataset, supports
+        # the pass's own sampler: never begun (perm = identity), never attached to the step
+        self.sampler = EpochSampler(len(dataset), batch_size, seed=0, rank=rank, world=world, device=dev, drop_last=False)
+        p, b, c = len(dataset), int(batch_size), self.classes
+        self._scores = torch.zeros(p * c + p, dtype=torch.float32, device=dev)      # probs | losses: one zero_, one all-reduce
+        self.probs = self._scores[:p * c].view((p,) if c == 1 else (p, c))
+        self.losses = self._scores[p * c:]
+        self._ws, self._record = ops.eval_metrics_buffers(p, c, dev)
+        self.record = None
+        self._x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=torch.float32, device=dev)
+        self._y = torch.empty((b,), dtype=dataset.y.dtype, device=dev)
+        if dataset.seq_lengths is not None:
+            self._lens, self._gather_lens = torch.empty(b, dtype=torch.int64, device=dev), True
+        else:
+            self._lens, self._gather_lens = dataset.full_lengths(b, step.raw_window, "DeviceEvaluator"), False
+        self._graph = None
+
+    def _body(self):
+        """one step of the pass: gather -> data chain without augmentation -> save=False forward -> head (p = 0) -> scores"""
+        st, ds, s, m = self.step, self.dataset, self.sampler, self.step.model
+        ops.gather_clips(ds.x, self._x, s.perm, s.cursor, s.rank, s.world, label_pool=ds.y, label_out=self._y,
+                         len_pool=ds.seq_lengths if self._gather_lens else None, len_out=self._lens if self._gather_lens else None,
+                         clip_w=s.clip_w, denom=s.denom, n_valid=s.n_valid)
+        x, _, supports = st._data_chain(self._x, self._y, self._lens, self.supports)
+        last = m.encode_last(x, self._lens, supports)
+        logits = ops.cls_head(last, m.fc.weight, m.fc.bias, 0.0, None)
+        ops.eval_scores(logits.view(self._x.shape[0], self.classes), ds.y, s.clip_w, s.cursor, self.probs, self.losses, s.rank, s.world)
+
+    def _capture(self, warmup: int = 2):
+        """the body as one HIP graph (the model is in eval mode here); the warm-up launches and the upload replay run real steps
+        whose scores `run` zeroes again"""
+        if self._scores.device.type != "cuda":
+            raise RuntimeError("DeviceEvaluator.run(capture=True) needs HIP graphs: the pools are on " + str(self._scores.device) +
+                               "; pass capture=False")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._body()
+        graph.replay()
+        self._graph = graph
+        return graph
+
+    @torch.no_grad()
+    def run(self, is_test: bool = False, eval_set: str = "dev", best_thresh: float = 0.5, capture: bool = True):
+        """One pass -> the OrderedDict of `evaluate` (loss, acc, F1, recall, precision, best_thresh[, auroc]).  detection: the
+        predictions are prob > best_thresh; on the dev set of a test run (is_test, eval_set == "dev") the threshold is searched on the
+        device (max F1, `utils.thresh_max_f1`).  capture: replay the step's body as one HIP graph (captured at the first such call)
+        instead of issuing it eagerly.  Leaves the model's mode, the step's counters, optimiser state, generators and sampler alone."""
+        st, s, model = self.step, self.sampler, self.step.model
+        multi = s.world > 1
+        if multi and not (dist.is_available() and dist.is_initialized() and dist.get_world_size() == s.world):
+            raise RuntimeError(f"DeviceEvaluator: world={s.world} needs a process group of that size for the all-reduce of the scores")
+        was_training = model.training
+        model.eval()
+        try:
+            graph = (self._graph or self._capture()) if capture else None
+            ops.zero_(self._scores)
+            s.seek(0)
+            for _ in range(s.steps_per_epoch):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._body()
+            if multi:
+                dist.all_reduce(self._scores, op=dist.ReduceOp.SUM)
+            search = st.task == "detection" and eval_set == "dev" and bool(is_test)
+            ops.eval_metrics(self.probs, self.dataset.y, self.losses, search, best_thresh, self._ws, self._record)
+            self.record = self._record.cpu()                         # the pass's one device-to-host copy
+        finally:
+            model.train(was_training)
+        return scores_from_record(self.record, st.task, best_thresh)

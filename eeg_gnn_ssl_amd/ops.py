@@ -12,7 +12,7 @@ Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
-    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips.
+    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, eval_scores, eval_metrics.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1449,6 +1449,82 @@ _define("masked_loss_w", "(Tensor pred, Tensor y, bool use_scaler, float mean, f
         "-> (Tensor loss, Tensor dpred)", _masked_loss_impl, _loss_fake)
 
 
+# ---- the evaluation pass on the device (train.py:332-431; evaluation.py: DeviceEvaluator) ----------------------------------------
+EVAL_MAX_CLIPS = 1 << 20      # EEG_EVAL_MAX_CLIPS: the largest pool of one pass
+EVAL_RECORD_HEAD = 16         # EEG_EVAL_RECORD_HEAD: int64 words in front of the classification confusion matrix
+
+
+def _eval_tensor(what, name, t, dtype, shape, dev):
+    """the operands of the evaluation operators are read / written ON THE DEVICE as they are: no conversion, anything else is refused"""
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {got}")
+
+
+def _eval_classes(what, probs):
+    if not torch.is_tensor(probs) or probs.dim() not in (1, 2) or probs.shape[0] < 1 or (probs.dim() == 2 and probs.shape[1] < 2):
+        got = f"{tuple(probs.shape)}" if torch.is_tensor(probs) else type(probs).__name__
+        raise RuntimeError(f"{what}: probs must be (P,) (detection) or (P, C) with C >= 2 (classification), got {got}")
+    p, c = int(probs.shape[0]), (1 if probs.dim() == 1 else int(probs.shape[1]))
+    if p > EVAL_MAX_CLIPS:
+        raise RuntimeError(f"{what}: P={p} clips exceed the limit of one pass, {EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    return p, c
+
+
+def _eval_scores_impl(logits, label_pool, clip_w, cursor, rank: int, world: int, probs, losses) -> None:
+    lib = _lib.get_lib()
+    p, c = _eval_classes("eval_scores", probs)
+    _check(lib, probs, "probs")
+    dev = probs.device
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.shape[1] != c or logits.shape[0] < 1:
+        raise RuntimeError(f"eval_scores: logits must be (B, {c}) for probs {tuple(probs.shape)}, got "
+                           f"{tuple(logits.shape) if torch.is_tensor(logits) else type(logits).__name__}")
+    b = int(logits.shape[0])
+    _eval_tensor("eval_scores", "logits", logits, torch.float32, (b, c), dev)
+    _eval_tensor("eval_scores", "losses", losses, torch.float32, (p,), dev)
+    _eval_tensor("eval_scores", "label_pool", label_pool, torch.float32 if c == 1 else torch.int64, (p,), dev)
+    _eval_tensor("eval_scores", "clip_w", clip_w, torch.float32, (b,), dev)
+    _eval_tensor("eval_scores", "cursor", cursor, torch.int64, (1,), dev)
+    if world < 1 or not 0 <= rank < world:
+        raise RuntimeError(f"eval_scores: rank={rank} of world={world}")
+    lib.call("eeg_dcrnn_eval_scores", _p(logits), _p(label_pool), 4 if c == 1 else 8, _p(clip_w), _p(cursor), b, c, int(rank), int(world), p,
+             _p(probs), _p(losses), _stream(probs))
+
+
+def eval_metrics_buffers(num_clips: int, num_classes: int, device):
+    """(ws, record) of `eval_metrics` for a pool of `num_clips` clips: int32 scratch of eeg_dcrnn_eval_metrics_ws_bytes and the int64
+    record (EVAL_RECORD_HEAD words, + C*C for classification); allocated once by the caller (`DeviceEvaluator`)"""
+    if not 1 <= int(num_clips) <= EVAL_MAX_CLIPS:
+        raise RuntimeError(f"eval_metrics: P={num_clips} clips outside 1..{EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    c = int(num_classes)
+    nbytes = int(_lib.get_lib().query("eeg_dcrnn_eval_metrics_ws_bytes", int(num_clips), c))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)
+    return ws, torch.zeros(EVAL_RECORD_HEAD + (c * c if c > 1 else 0), dtype=torch.int64, device=device)
+
+
+def _eval_metrics_impl(probs, labels, losses, search: bool, thresh: float, ws, record) -> None:
+    lib = _lib.get_lib()
+    p, c = _eval_classes("eval_metrics", probs)
+    _check(lib, probs, "probs")
+    dev = probs.device
+    _eval_tensor("eval_metrics", "labels", labels, torch.float32 if c == 1 else torch.int64, (p,), dev)
+    _eval_tensor("eval_metrics", "losses", losses, torch.float32, (p,), dev)
+    need = (int(lib.query("eeg_dcrnn_eval_metrics_ws_bytes", p, c)) + 3) // 4
+    if not torch.is_tensor(ws) or ws.dtype != torch.int32 or ws.dim() != 1 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise RuntimeError(f"eval_metrics: ws must be a contiguous int32 vector of at least {need} entries on {dev} (ops.eval_metrics_buffers)")
+    _eval_tensor("eval_metrics", "record", record, torch.int64, (EVAL_RECORD_HEAD + (c * c if c > 1 else 0),), dev)
+    if thresh != thresh:
+        raise RuntimeError("eval_metrics: thresh is NaN")
+    lib.call("eeg_dcrnn_eval_metrics", _p(probs), _p(labels), 4 if c == 1 else 8, _p(losses), p, c, 1 if search else 0, float(thresh),
+             _p(ws) if ws.numel() else None, _p(record), _stream(probs))
+
+
+_define("eval_scores", "(Tensor logits, Tensor label_pool, Tensor clip_w, Tensor cursor, int rank, int world, Tensor(a!) probs, "
+        "Tensor(b!) losses) -> ()", _eval_scores_impl, lambda *a: None)
+_define("eval_metrics", "(Tensor probs, Tensor labels, Tensor losses, bool search, float thresh, Tensor(a!) ws, Tensor(b!) record) -> ()",
+        _eval_metrics_impl, lambda *a: None)
+
+
 def _loss_setup(ctx, inputs, output):
     ctx.save_for_backward(output[1])
     ctx.n_in = len(inputs)
@@ -2142,3 +2218,24 @@ def gather_clips(x_pool, x_out, perm, cursor, rank: int = 0, world: int = 1, y_p
         raise RuntimeError("gather_clips: clip_w, denom and n_valid come together (one of them is None)")
     torch.ops.eeg_dcrnn.gather_clips_tail(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank),
                                           int(world), clip_w, denom, n_valid)
+
+
+def eval_scores(logits, label_pool, clip_w, cursor, probs, losses, rank: int = 0, world: int = 1):
+    """Per-clip scores of one step of an evaluation pass over a pool in order, behind `gather_clips(..., clip_w=, denom=, n_valid=)`
+    (which has advanced `cursor`): slot b of logits (B, C) is pool position cursor - B*world + rank*B + b; a slot with clip_w != 0
+    and a position in [0, P) writes probs[pos] (sigmoid, C = 1 / the softmax row) and losses[pos] (the BCE-with-logits /
+    cross-entropy term of that clip, label read from label_pool[pos]: float32 (P,) for C = 1, int64 (P,) else).  Nothing is ever
+    written outside probs (P,) / (P, C) and losses (P,).  One launch, no allocation, capturable."""
+    torch.ops.eeg_dcrnn.eval_scores(logits, label_pool, clip_w, cursor, int(rank), int(world), probs, losses)
+
+
+def eval_metrics(probs, labels, losses, search: bool = False, thresh: float = 0.5, ws=None, record=None):
+    """The scores of a pool from its per-clip scores, on the device, as one int64 record (include/eeg_dcrnn.h: eeg_dcrnn_eval_metrics;
+    `evaluation.scores_from_record` turns it into the reference's score dictionary): detection (probs (P,), labels float32) -- the
+    clips sorted by the project's own bitonic sort, AUROC numerator, the max-F1 threshold of `utils.thresh_max_f1` (search=True) or
+    `thresh`, the confusion counts of prob > threshold; classification (probs (P, C), labels int64) -- the C x C confusion matrix of
+    the first arg-max.  ws / record: `eval_metrics_buffers` (allocated here when not given).  Returns record; no host sync."""
+    if ws is None or record is None:
+        ws, record = eval_metrics_buffers(probs.shape[0], 1 if probs.dim() == 1 else probs.shape[1], probs.device)
+    torch.ops.eeg_dcrnn.eval_metrics(probs, labels, losses, bool(search), float(thresh), ws, record)
+    return record

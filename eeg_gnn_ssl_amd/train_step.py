@@ -256,30 +256,7 @@ class TrainStep:
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
             supports, perm, log_scale = self._draw_augmentation(x.shape[0], supports)
-        # variable-length clips: the data side stops at the clip's own length (None: every step, the calls below as they always were)
-        lens, pad = None, 0.0
-        if self.padding_val is not None and seq_lengths is not None:
-            lens, pad = seq_lengths.to(device=x.device, dtype=torch.int64), self.padding_val
-        if not self.use_fft:
-            x, y, supports = self._time_domain_inputs(x, y, supports, perm, log_scale, lens, pad)
-        elif self.task == "ssl" and (self.raw_window is not None or perm is not None):
-            # the SSL sample is a pair: the target takes the clip's draws and the scaler like the input (dataloader_ssl.py:317-341)
-            x, y, supports = self._ssl_pair(x, y, supports, perm, log_scale)
-        elif self.raw_window is not None:            # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
-            feat_raw, x = ops.fft_features(x, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm, log_scale=log_scale,
-                                           lengths=lens, padding_val=pad)
-            if supports is None:
-                supports = ops.correlation_supports(feat_raw, top_k=3, lengths=lens)   # (feat_raw: un-reflected, un-scaled, un-standardised)
-        elif perm is not None:
-            plain = x
-            idx = perm.to(torch.int64)[:, None, :, None].expand(-1, x.shape[1], -1, x.shape[3])
-            x = x.gather(2, idx) + (log_scale / self.feature_std)[:, None, None, None]
-            if supports is None:
-                supports = ops.correlation_supports(plain, top_k=3, lengths=lens)
-        if supports is None:
-            supports = ops.correlation_supports(x, top_k=3, lengths=lens)
-        elif self.shared_graph:
-            supports = ops.collapse_shared_supports(supports)
+        x, y, supports = self._data_chain(x, y, seq_lengths, supports, perm, log_scale)
         if self.task == "ssl":
             if self._use_device_curriculum(y.shape[1], y.shape[0]):
                 self.model.batches_seen_increment = sampler.n_valid if tail else x.shape[0] * self.world
@@ -305,6 +282,37 @@ class TrainStep:
         with self.fp.sink:                       # backward operators write into the flat gradient bucket
             out.backward(seed.view_as(out))
         return loss.detach()
+
+    def _data_chain(self, x, y, seq_lengths, supports, perm=None, log_scale=None):
+        """the data side of a step in front of the model: raw signals -> log|FFT| or windows -> z-score, the padding of variable-length
+        clips, the correlation graph of the un-augmented, un-standardised clip (supports=None) or the shared graph in its 2-D form
+        -> (model input, target, supports).  perm / log_scale: this step's augmentation draws; None (a step without augmentation,
+        and the evaluation pass of `DeviceEvaluator`): no draw is applied and none is taken."""
+        # variable-length clips: the data side stops at the clip's own length (None: every step, the calls below as they always were)
+        lens, pad = None, 0.0
+        if self.padding_val is not None and seq_lengths is not None:
+            lens, pad = seq_lengths.to(device=x.device, dtype=torch.int64), self.padding_val
+        if not self.use_fft:
+            x, y, supports = self._time_domain_inputs(x, y, supports, perm, log_scale, lens, pad)
+        elif self.task == "ssl" and (self.raw_window is not None or perm is not None):
+            # the SSL sample is a pair: the target takes the clip's draws and the scaler like the input (dataloader_ssl.py:317-341)
+            x, y, supports = self._ssl_pair(x, y, supports, perm, log_scale)
+        elif self.raw_window is not None:            # raw signals in: featurise on the device (x becomes the standardised log|FFT|)
+            feat_raw, x = ops.fft_features(x, window=self.raw_window, mean=self.raw_mean, std=self.raw_std, perm=perm, log_scale=log_scale,
+                                           lengths=lens, padding_val=pad)
+            if supports is None:
+                supports = ops.correlation_supports(feat_raw, top_k=3, lengths=lens)   # (feat_raw: un-reflected, un-scaled, un-standardised)
+        elif perm is not None:
+            plain = x
+            idx = perm.to(torch.int64)[:, None, :, None].expand(-1, x.shape[1], -1, x.shape[3])
+            x = x.gather(2, idx) + (log_scale / self.feature_std)[:, None, None, None]
+            if supports is None:
+                supports = ops.correlation_supports(plain, top_k=3, lengths=lens)
+        if supports is None:
+            supports = ops.correlation_supports(x, top_k=3, lengths=lens)
+        elif self.shared_graph:
+            supports = ops.collapse_shared_supports(supports)
+        return x, y, supports
 
     def _ssl_target_steps(self, y) -> int:
         """decoder steps of an SSL target: feature steps, or whole windows of a raw target (refused otherwise)"""
@@ -592,6 +600,12 @@ class TrainStep:
             raise RuntimeError("TrainStep.begin_epoch: no sampler attached (pass sampler=, or call step_from / capture_epoch first)")
         self.sampler.begin_epoch(epoch)
         return self.set_epoch(epoch, num_epochs, eta_min)
+
+    def evaluator(self, dataset, batch_size: int, supports=None, rank: Optional[int] = None, world: Optional[int] = None):
+        """the evaluation pass of this step's model and data chain over a device-resident pool, on the device
+        (`evaluation.DeviceEvaluator`): `ev = step.evaluator(dev_ds, B); res = ev.run(is_test=False, eval_set="dev")`"""
+        from .evaluation import DeviceEvaluator
+        return DeviceEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world)
 
     # -- checkpointing (utils.CheckpointSaver / load_model_checkpoint use these like an optimizer's) -------
     def state_dict(self):

@@ -387,6 +387,37 @@ int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_
                                 const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, float* clip_w,
                                 float* denom, int64_t* n_valid, void* stream);
 
+/* The evaluation pass (train.py:332-431) on the device.
+ *
+ * eeg_dcrnn_eval_scores: one launch behind the head of every step of a pass over a pool of P clips in order (perm = identity,
+ * eeg_dcrnn_gather_clips_tail in front, which has ALREADY advanced the cursor): slot b of logits (B, C) is pool position
+ * pos = cursor[0] - B*world + rank*B + b.  A slot writes only if clip_w[b] != 0 AND 0 <= pos < P; whatever the cursor holds,
+ * nothing is written outside probs (P, C) and losses (P).  The label is read from label_pool at pos (label_bytes 4: float32
+ * {0, 1}, C = 1; 8: int64 classes, C > 1).  Written per slot: C = 1: probs[pos] = sigmoid, losses[pos] = the BCE-with-logits term;
+ * C > 1: probs[pos, :] = the float32 softmax row, losses[pos] = the cross-entropy term -- the terms of eeg_dcrnn_bce_logits /
+ * eeg_dcrnn_ce_logits on that clip as a batch of one, bit for bit (a class outside 0..C-1: NaN).
+ *
+ * eeg_dcrnn_eval_metrics: the scores of the pool from probs / labels / losses as ONE record of int64 words in device memory
+ * (EEG_EVAL_RECORD_HEAD words, for C > 1 followed by the C x C confusion matrix, row = label, column = prediction); float64 values
+ * travel as their bit patterns.  No allocation, no host synchronisation; integer arithmetic and one float64 sum in a fixed
+ * order: the record reproduces bit for bit.  P <= EEG_EVAL_MAX_CLIPS.  ws: eeg_dcrnn_eval_metrics_ws_bytes(P, C) bytes (0 for
+ * C > 1: ws may be null).  Words (both tasks): 0 n, 9 labels outside {0,1} / 0..C-1, 10 probabilities outside [0,1] or NaN (C > 1:
+ * rows holding one), 11 bits of sum(losses).  C = 1 (labels float32): the clips are sorted by (prob, label) (bitonic network, LDS
+ * tiles + global steps) and scanned once: 1 n_pos, 2 n_neg, 3 the AUROC numerator sum_v pos(v) * (2 * neg_below(v) + neg(v)) over
+ * the distinct values v (AUROC = num / (2 n_pos n_neg)), 4 bits of the threshold used, 5..8 tp, fp, fn, tn of the predictions
+ * (double)prob > threshold, 12 search, 13 whether the search found a candidate, 14 / 15 its tp and the bits of its F1.  search != 0:
+ * the threshold is the distinct value v whose predictions prob >= v have the largest F1 among those with tp > 0 -- F1 as
+ * utils.thresh_max_f1 computes it in float64 from the integer counts, operation for operation, so that candidates whose F1 tie as
+ * rationals resolve as they do there -- ties to the lowest v; without a candidate, and with search == 0, it is `thresh`.  C > 1
+ * (labels int64): the prediction is the first arg-max of the row. */
+#define EEG_EVAL_MAX_CLIPS (1 << 20)
+#define EEG_EVAL_RECORD_HEAD 16
+int eeg_dcrnn_eval_scores(const float* logits, const void* label_pool, int label_bytes, const float* clip_w, const int64_t* cursor, int B, int C,
+                          int rank, int world, int64_t P, float* probs, float* losses, void* stream);
+size_t eeg_dcrnn_eval_metrics_ws_bytes(int64_t P, int C);
+int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_bytes, const float* losses, int64_t P, int C, int search,
+                           double thresh, void* ws, int64_t* record, void* stream);
+
 /* utils.last_relevant_pytorch (utils.py:346-357): last[b] = Htop[lengths[b]-1, b]. Htop (T,B,NH). */
 int eeg_dcrnn_gather_last(const float* Htop, const int64_t* lengths, int T, int B, int NH,
                           float* last, void* stream);
