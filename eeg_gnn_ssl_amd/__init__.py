@@ -6,10 +6,10 @@ gfx950 behind a C ABI (include/eeg_dcrnn.h).
 """
 from . import ops, utils                                  # noqa: F401
 from .device_data import DeviceDataset, EpochSampler             # noqa: F401
-from .evaluation import DeviceEvaluator                         # noqa: F401
+from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
 from .model.cell import DCGRUCell, DiffusionGraphConv     # noqa: F401
 from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,   # noqa: F401
                           DCRNNModel_nextTimePred)
 
 __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
-           "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "DeviceEvaluator", "ops", "utils"]
+           "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "DeviceEvaluator", "DeviceSSLEvaluator", "ops", "utils"]

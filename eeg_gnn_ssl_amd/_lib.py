@@ -112,6 +112,10 @@ _SIGNATURES = {
     "eeg_dcrnn_eval_scores": (c_int, [_FP, _FP, c_int, _FP, _FP, c_int, c_int, c_int, c_int, c_int64, _FP, _FP, c_void_p]),
     "eeg_dcrnn_eval_metrics_ws_bytes": (c_size_t, [c_int64, c_int]),
     "eeg_dcrnn_eval_metrics": (c_int, [_FP, _FP, c_int, _FP, c_int64, c_int, c_int, ctypes.c_double, _FP, _FP, c_void_p]),
+    # the SSL evaluation pass: per-clip masked-MAE sums behind the decoder, then the pass's float64 record
+    "eeg_dcrnn_ssl_eval_scores": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_float, c_float, _FP, _FP,
+                                          c_void_p]),
+    "eeg_dcrnn_ssl_eval_metrics": (c_int, [_FP, c_int64, c_int64, _FP, c_void_p]),
     "eeg_dcrnn_pack_cells": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32),
                              c_int, c_int, POINTER(c_void_p), _FP, c_int, POINTER(c_void_p), c_void_p]),
     "eeg_dcrnn_cls_head_loss_ws_floats": (c_size_t, [c_int, c_int, c_int]),

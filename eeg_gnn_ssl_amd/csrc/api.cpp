@@ -1244,6 +1244,39 @@ int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_byt
     return check_launch("eval_scan");
 }
 
+/* ---- the SSL evaluation pass: per-clip masked MAE, the pass's record ------------------------------ */
+static_assert(EEG_SSL_EVAL_MAX_CLIP_ELEMS == kSslEvalMaxClipElems && EEG_SSL_EVAL_RECORD_WORDS == kSslEvalRecordWords,
+              "include/eeg_dcrnn.h and kernels_eval.h disagree");
+int eeg_dcrnn_ssl_eval_scores(const float* pred, const float* target, const float* clip_w, const int64_t* cursor, int B, int64_t clip_elems, int D,
+                              int rank, int world, int64_t P, int scaled, float mean, float std_, float mask_val, double* scores, float* keep,
+                              void* stream) {
+    if (pred == nullptr || target == nullptr || clip_w == nullptr || cursor == nullptr) return fail("ssl_eval_scores: null pred / target / clip_w / cursor");
+    if (scores == nullptr) return fail("ssl_eval_scores: null scores");
+    if (B < 1) return fail("ssl_eval_scores: empty batch (B=%d)", B);
+    if (D < 1 || D % 4 != 0) return fail("ssl_eval_scores: D=%d: the clips are read in 16-byte pieces, D must be a multiple of 4", D);
+    if (clip_elems < D || clip_elems % D != 0) return fail("ssl_eval_scores: a clip of %lld elements is no whole number of rows of D=%d", (long long)clip_elems, D);
+    if (clip_elems >= EEG_SSL_EVAL_MAX_CLIP_ELEMS)
+        return fail("ssl_eval_scores: a clip of %lld elements unsupported (below %d)", (long long)clip_elems, EEG_SSL_EVAL_MAX_CLIP_ELEMS);
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("ssl_eval_scores: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (world < 1 || rank < 0 || rank >= world) return fail("ssl_eval_scores: rank=%d of world=%d", rank, world);
+    if ((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)keep) & 15) != 0) return fail("ssl_eval_scores: pred, target and keep must be 16-byte aligned");
+    if (((uintptr_t)clip_w & 3) != 0 || (((uintptr_t)cursor | (uintptr_t)scores) & 7) != 0)
+        return fail("ssl_eval_scores: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("ssl_eval_scores", ssl_eval_scores_kernel, dim3(B), dim3(kSslEvalThreads), kSslEvalThreads * sizeof(double), S_(stream), pred, target,
+                 clip_w, reinterpret_cast<const long long*>(cursor), (long long)B * world, (long long)rank * B, (long long)P, (int)(clip_elems / 4), mean,
+                 std_, scaled ? 1 : 0, mask_val, scores, keep);
+    return check_launch("ssl_eval_scores");
+}
+int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, double* record, void* stream) {
+    if (scores == nullptr || record == nullptr) return fail("ssl_eval_metrics: null scores / record");
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("ssl_eval_metrics: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (G < 1) return fail("ssl_eval_metrics: groups of G=%lld clips", (long long)G);
+    if ((((uintptr_t)scores | (uintptr_t)record) & 7) != 0) return fail("ssl_eval_metrics: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("ssl_eval_metrics", ssl_eval_metrics_kernel, dim3(1), dim3(kSslEvalThreads), kSslEvalThreads * sizeof(double), S_(stream), scores, (int)P,
+                 (int)(G < P ? G : P), record);
+    return check_launch("ssl_eval_metrics");
+}
+
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
 static int corr_nsplit(int B, int T) {
     int ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);         // dev knob 7: target number of workgroups

@@ -280,4 +280,129 @@ __global__ __launch_bounds__(kEvalScanThreads) void eval_confusion_kernel(const 
     rec[kRecN] = P; rec[kRecBadLabels] = bad_l; rec[kRecBadProbs] = bad_p; rec[kRecLossSumBits] = eval_d2ll(loss_sum);
 }
 
+// ---- ssl: per-clip masked MAE ------------------------------------------------------------------------------------------------------
+// The SSL evaluation pass of train_ssl.py:232-280 on the device.  ssl_eval_scores_kernel is the twin of eval_scores_kernel behind the
+// decoder of every step: ONE workgroup per batch slot, the slot -> pool position arithmetic and its bound as above (unsigned; a slot
+// writes only if clip_w[b] != 0 AND 0 <= pos < P).  The clip's per4 16-byte pieces of pred and target are read once: thread t takes
+// the pieces t, t + 256, ..; per element the terms of masked_terms (two roundings of the inverse transform, float32 d, mask = ys !=
+// mask_val); the thread adds the float32 |d| of its masked-in elements in float64, in piece order, then a fixed LDS tree over the
+// thread index.  Nothing in that order depends on B, the slot, the rank or the launch: a clip's sum has the same bits wherever it
+// sits.  A masked-in element whose d is not finite is counted in bad and left out of the sum.  scores is (3, P) float64: abs_sum |
+// count | bad.  keep (nullable, (P, per4 * 4)): the slot's pred is copied to keep[pos] by the threads that read it.
+constexpr int kSslEvalThreads = 256;
+constexpr long long kSslEvalMaxClipElems = 1ll << 24;   // EEG_SSL_EVAL_MAX_CLIP_ELEMS: count and bad of a clip stay exact in an int per thread
+constexpr int kSslEvalRecordWords = 8;                  // EEG_SSL_EVAL_RECORD_WORDS
+enum SslEvalRec { kSslRecN = 0, kSslRecBatches = 1, kSslRecLoss = 2, kSslRecPoolMae = 3, kSslRecAbsSum = 4, kSslRecCount = 5, kSslRecBad = 6,
+                  kSslRecEmptyBatches = 7 };
+
+// sum of the block's doubles, fixed order (tree over the thread index); s: blockDim.x words of LDS; every thread gets the sum
+__device__ __forceinline__ double ssl_eval_block_sum(double* s, double v) {
+    __syncthreads();
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    return s[0];
+}
+
+__global__ __launch_bounds__(kSslEvalThreads) void ssl_eval_scores_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                                          const float* __restrict__ clip_w, const long long* __restrict__ cursor,
+                                                                          long long step, long long slot0, long long P, int per4, float mean,
+                                                                          float std_, int scaled, float mask_val, double* __restrict__ scores,
+                                                                          float* __restrict__ keep) {
+    EEG_DYN_SMEM(smf);
+    double* s = reinterpret_cast<double*>(smf);                          // kSslEvalThreads words
+    const int b = blockIdx.x;
+    if (clip_w[b] == 0.f) return;                                        // (the whole workgroup leaves: no barrier is left waiting)
+    const unsigned long long pos = (unsigned long long)cursor[0] - (unsigned long long)step + (unsigned long long)slot0 + (unsigned long long)b;
+    if (pos >= (unsigned long long)P) return;
+    const size_t per = (size_t)per4 * 4;
+    const float* p = pred + (size_t)b * per;
+    const float* y = target + (size_t)b * per;
+    float* k = keep != nullptr ? keep + (size_t)pos * per : nullptr;
+    double sum = 0.0;
+    int cnt = 0, bad = 0;
+    auto term = [&](float pv, float yv) {
+        float d, mk;
+        masked_terms(pv, yv, mean, std_, scaled, mask_val, d, mk);
+        if (mk != 0.f) {
+            const float a = fabsf(d);
+            ++cnt;
+            if (a <= 3.402823466e+38f) sum += (double)a; else ++bad;     // (NaN and Inf fail the comparison)
+        }
+    };
+    int i = threadIdx.x;
+    for (; i + kSslEvalThreads < per4; i += 2 * kSslEvalThreads) {       // two 16-byte loads per operand in flight
+        const f32x4 p0 = ld4(p + 4 * (size_t)i), y0 = ld4(y + 4 * (size_t)i);
+        const f32x4 p1 = ld4(p + 4 * (size_t)(i + kSslEvalThreads)), y1 = ld4(y + 4 * (size_t)(i + kSslEvalThreads));
+        if (k != nullptr) { st4(k + 4 * (size_t)i, p0); st4(k + 4 * (size_t)(i + kSslEvalThreads), p1); }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) term(p0[r], y0[r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) term(p1[r], y1[r]);
+    }
+    if (i < per4) {
+        const f32x4 p0 = ld4(p + 4 * (size_t)i), y0 = ld4(y + 4 * (size_t)i);
+        if (k != nullptr) st4(k + 4 * (size_t)i, p0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) term(p0[r], y0[r]);
+    }
+    sum = ssl_eval_block_sum(s, sum);
+    const double c = ssl_eval_block_sum(s, (double)cnt), bd = ssl_eval_block_sum(s, (double)bad);   // (integers below 2^24: exact)
+    if (threadIdx.x != 0) return;
+    scores[pos] = sum;
+    scores[(size_t)P + pos] = c;
+    scores[2 * (size_t)P + pos] = bd;
+}
+
+// The pass's record from the (3, P) scores, ONE block, float64, fixed order.  loss is the reference's AverageMeter value over the
+// consecutive groups g = [g*G, min((g+1)*G, P)) (the batches of a single process at batch size G): sum_g n_g * L_g / P with
+// L_g = S_g / C_g, 0 where C_g == 0 (masked_mae_loss turns that 0/0 into 0 and the meter still counts the batch).  G < blockDim:
+// thread t sums the groups t, t + blockDim, .. element by element, then the tree; else the block sums one group after the other
+// (strided partial sums + the tree) and thread 0 adds n_g * L_g in group order.  Both orders depend on (P, G) alone.
+__global__ __launch_bounds__(kSslEvalThreads) void ssl_eval_metrics_kernel(const double* __restrict__ scores, int P, int G, double* __restrict__ rec) {
+    EEG_DYN_SMEM(smf);
+    double* s = reinterpret_cast<double*>(smf);                          // kSslEvalThreads words
+    const double* abs_sum = scores;
+    const double* count = scores + P;
+    const double* bad = scores + 2 * (size_t)P;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    double ta = 0.0, tc = 0.0, tb = 0.0;
+    for (int i = tid; i < P; i += nt) { ta += abs_sum[i]; tc += count[i]; tb += bad[i]; }
+    ta = ssl_eval_block_sum(s, ta);
+    tc = ssl_eval_block_sum(s, tc);
+    tb = ssl_eval_block_sum(s, tb);
+    const int ngroups = (P + G - 1) / G;                                 // (G <= P: the host clamps it)
+    double acc = 0.0, empty = 0.0;
+    auto add_group = [&](double sg, double cg, int n) {
+        acc += (double)n * (cg > 0.0 ? sg / cg : 0.0);
+        empty += cg > 0.0 ? 0.0 : 1.0;
+    };
+    if (G < nt) {
+        for (int g = tid; g < ngroups; g += nt) {
+            const int lo = g * G, hi = lo + G < P ? lo + G : P;
+            double sg = 0.0, cg = 0.0;
+            for (int i = lo; i < hi; ++i) { sg += abs_sum[i]; cg += count[i]; }
+            add_group(sg, cg, hi - lo);
+        }
+        acc = ssl_eval_block_sum(s, acc);
+        empty = ssl_eval_block_sum(s, empty);
+    } else {
+        for (int g = 0; g < ngroups; ++g) {
+            const int lo = g * G, hi = lo + G < P ? lo + G : P;
+            double sg = 0.0, cg = 0.0;
+            for (int i = lo + tid; i < hi; i += nt) { sg += abs_sum[i]; cg += count[i]; }
+            sg = ssl_eval_block_sum(s, sg);
+            cg = ssl_eval_block_sum(s, cg);
+            if (tid == 0) add_group(sg, cg, hi - lo);
+        }
+    }
+    if (tid != 0) return;
+    rec[kSslRecN] = (double)P; rec[kSslRecBatches] = (double)ngroups; rec[kSslRecLoss] = acc / (double)P;
+    rec[kSslRecPoolMae] = tc > 0.0 ? ta / tc : 0.0;
+    rec[kSslRecAbsSum] = ta; rec[kSslRecCount] = tc; rec[kSslRecBad] = tb; rec[kSslRecEmptyBatches] = empty;
+}
+
 }  // namespace eeg

@@ -10,7 +10,11 @@ step is captured once as one HIP graph and replayed; the graph reads the paramet
 updates them.  Behind the last step `ops.eval_metrics` reduces the buffers to one small integer record (the project's own sort, AUROC
 numerator, max-F1 threshold, confusion counts) which the host reads in a single copy and finishes in float64.
 
-`evaluate`, `predict` and `evaluate_ssl` are unchanged and remain the yardstick; SSL evaluation stays with `evaluate_ssl`."""
+A `DeviceSSLEvaluator` (`TrainStep.ssl_evaluator`) is the same pass for self-supervised pre-training (train_ssl.py:232-280): the pair
+chain of the step on the input and target pools, the decoder without teacher forcing, and per clip the float64 masked-MAE sum and
+count (`ops.ssl_eval_scores`); `ops.ssl_eval_metrics` reduces them to the loss the reference selects its checkpoint by.
+
+`evaluate`, `predict` and `evaluate_ssl` are unchanged and remain the yardstick."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -73,7 +77,42 @@ def scores_from_record(record, task: str, best_thresh: float = 0.5):
     return OrderedDict(res)
 
 
-class DeviceEvaluator:
+class _CapturedPass:
+    """what the evaluators share: the body of a step as one HIP graph"""
+
+    def _capture(self, warmup: int = 2):
+        """the body as one HIP graph (the model is in eval mode here); the warm-up launches and the upload replay run real steps
+        whose scores `run` zeroes again"""
+        if self._scores.device.type != "cuda":
+            raise RuntimeError(type(self).__name__ + ".run(capture=True) needs HIP graphs: the pools are on " + str(self._scores.device) +
+                               "; pass capture=False")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._body()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._body()
+        graph.replay()
+        self._graph = graph
+        return graph
+
+    def _replay(self, capture: bool):
+        """zero the scores, put the sampler at the start of the pool and issue the steps of one pass"""
+        s = self.sampler
+        graph = (self._graph or self._capture()) if capture else None
+        ops.zero_(self._scores)
+        s.seek(0)
+        for _ in range(s.steps_per_epoch):
+            if graph is not None:
+                graph.replay()
+            else:
+                self._body()
+
+
+class DeviceEvaluator(_CapturedPass):
     """`TrainStep.evaluator(dataset, batch_size, supports=None)`: evaluation passes of the step's model over `dataset` on the device.
 
     supports: None (correlation graphs built on the device -- of the unpadded clip when the step has `padding_val` and the dataset a
@@ -132,25 +171,6 @@ class DeviceEvaluator:
         logits = ops.cls_head(last, m.fc.weight, m.fc.bias, 0.0, None)
         ops.eval_scores(logits.view(self._x.shape[0], self.classes), ds.y, s.clip_w, s.cursor, self.probs, self.losses, s.rank, s.world)
 
-    def _capture(self, warmup: int = 2):
-        """the body as one HIP graph (the model is in eval mode here); the warm-up launches and the upload replay run real steps
-        whose scores `run` zeroes again"""
-        if self._scores.device.type != "cuda":
-            raise RuntimeError("DeviceEvaluator.run(capture=True) needs HIP graphs: the pools are on " + str(self._scores.device) +
-                               "; pass capture=False")
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._body()
-        graph.replay()
-        self._graph = graph
-        return graph
-
     @torch.no_grad()
     def run(self, is_test: bool = False, eval_set: str = "dev", best_thresh: float = 0.5, capture: bool = True):
         """One pass -> the OrderedDict of `evaluate` (loss, acc, F1, recall, precision, best_thresh[, auroc]).  detection: the
@@ -164,14 +184,7 @@ class DeviceEvaluator:
         was_training = model.training
         model.eval()
         try:
-            graph = (self._graph or self._capture()) if capture else None
-            ops.zero_(self._scores)
-            s.seek(0)
-            for _ in range(s.steps_per_epoch):
-                if graph is not None:
-                    graph.replay()
-                else:
-                    self._body()
+            self._replay(capture)
             if multi:
                 dist.all_reduce(self._scores, op=dist.ReduceOp.SUM)
             search = st.task == "detection" and eval_set == "dev" and bool(is_test)
@@ -180,3 +193,105 @@ class DeviceEvaluator:
         finally:
             model.train(was_training)
         return scores_from_record(self.record, st.task, best_thresh)
+
+
+class DeviceSSLEvaluator(_CapturedPass):
+    """`TrainStep.ssl_evaluator(dataset, batch_size, supports=None)`: the SSL evaluation pass (train_ssl.py:232-280) of the step's
+    model over `dataset` on the device -- the value `evaluate_ssl` returns, from pools `evaluate_ssl` cannot be handed.
+
+    dataset: `DeviceDataset(x, y)` with y the TARGET pool: features / windows (P, Ty, N, D), or -- `TrainStep(raw_window=W)` -- raw
+    signals (P, N, Ty*W) like x.  A step of the pass gathers B clips of both pools in order, runs the step's pair chain without
+    augmentation (`fft_features_pair` / `window_features_pair` / the features as they are; supports=None: the correlation graph of
+    the plain input clip), the model in eval mode (no dropout, no `batches_seen`: no teacher forcing) and `ops.ssl_eval_scores`
+    with the step's scaler_mean / scaler_std.  rank r takes the slots cursor + r * batch_size .. of every step; the (3, P) scores
+    go through one summed all-reduce behind the last step (disjoint slots, zeros elsewhere).
+
+    `run` returns the reference's AverageMeter loss over consecutive batches of `loss_batch` clips (default: batch_size, the
+    PER-RANK batch size: every rank of any world size returns the single-process result of that batch size).  After `run`:
+        record       the pass's record (`ops.ssl_eval_metrics`), float64, on the host; `result`: its words by name
+        clip_abs, clip_count, clip_mae   (P,) float64 in pool order, on the device (clip_mae: 0 for a fully masked clip)
+        predictions  (P, Ty, N, D) with keep_predictions: THIS rank's slots, zeros elsewhere (not reduced), standardised like
+                     the predictions `evaluate_ssl(return_predictions=True)` returns for the rank's shard
+    The buffers keep their addresses; the next `run` overwrites them.  Limits: P <= ops.EVAL_MAX_CLIPS, a clip below
+    ops.SSL_EVAL_MAX_CLIP_ELEMS elements, output_dim a multiple of 4 (16-byte pieces)."""
+
+    def __init__(self, step, dataset, batch_size: int, supports=None, rank: Optional[int] = None, world: Optional[int] = None,
+                 keep_predictions: bool = False, loss_batch: Optional[int] = None):
+        if step.task != "ssl":
+            raise ValueError(f"DeviceSSLEvaluator: task={step.task!r} has labels and scores per clip; its evaluation pass is TrainStep.evaluator")
+        if not dataset.y_is_target:
+            raise ValueError(f"DeviceSSLEvaluator: y of the dataset is a label pool {tuple(dataset.y.shape)}; the pass needs the TARGET pool, "
+                             f"DeviceDataset(x, y) with y the clips to predict (P, Ty, N, D) or raw (P, N, Ty*raw_window)")
+        dev = step.fp.flat.device
+        if dataset.device != dev:
+            raise ValueError(f"DeviceSSLEvaluator: dataset on {dataset.device}, model on {dev}: one device")
+        p, b, m = len(dataset), int(batch_size), step.model
+        if p > ops.EVAL_MAX_CLIPS:
+            raise ValueError(f"DeviceSSLEvaluator: the pool holds P={p} clips, one pass takes at most {ops.EVAL_MAX_CLIPS} "
+                             f"(ops.EVAL_MAX_CLIPS); evaluate it in parts")
+        y = dataset.y
+        if step.raw_window is not None:
+            w = int(step.raw_window)
+            if dataset.x.dim() != 3 or y.dim() != 3 or y.shape[1] != dataset.x.shape[1] or y.shape[2] == 0 or y.shape[2] % w != 0:
+                raise ValueError(f"DeviceSSLEvaluator: TrainStep(raw_window={w}) evaluates RAW pools: x (P, N, T*{w}) and the target "
+                                 f"(P, N, Ty*{w}) -- whole windows of the same nodes -- got x {tuple(dataset.x.shape)}, y {tuple(y.shape)}")
+            steps = y.shape[2] // w
+        else:
+            if dataset.x.dim() != 4 or y.dim() != 4:
+                raise ValueError(f"DeviceSSLEvaluator: without raw_window the pools hold features / windows, x (P, T, N, D) and the target "
+                                 f"(P, Ty, N, D), got x {tuple(dataset.x.shape)}, y {tuple(y.shape)}; raw signals need TrainStep(raw_window=W)")
+            steps = y.shape[1]
+        if m.output_dim % 4 != 0:
+            raise ValueError(f"DeviceSSLEvaluator: the model's output_dim={m.output_dim} is no multiple of 4 (ops.ssl_eval_scores reads "
+                             f"16-byte pieces); evaluate with train_step.evaluate_ssl")
+        if loss_batch is not None and int(loss_batch) < 1:
+            raise ValueError(f"DeviceSSLEvaluator: loss_batch={loss_batch} (the batch size of the reference's loss, >= 1)")
+        self.step, self.dataset, self.supports = step, dataset, supports
+        # the pass's own sampler: never begun (perm = identity), never attached to the step
+        self.sampler = EpochSampler(p, b, seed=0, rank=rank, world=world, device=dev, drop_last=False)
+        self.loss_batch = b if loss_batch is None else int(loss_batch)
+        self._scores, self._record, self.predictions = ops.ssl_eval_buffers(
+            p, dev, (steps, m.num_nodes, m.output_dim) if keep_predictions else None)
+        self.clip_abs, self.clip_count = self._scores[0], self._scores[1]
+        self.clip_mae, self.record, self.result = None, None, None
+        self._x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=torch.float32, device=dev)
+        self._y = torch.empty((b,) + tuple(y.shape[1:]), dtype=torch.float32, device=dev)
+        self._graph = None
+
+    def _body(self):
+        """one step of the pass: gather the pair -> pair chain without augmentation -> the model without teacher forcing -> scores"""
+        st, ds, s = self.step, self.dataset, self.sampler
+        ops.gather_clips(ds.x, self._x, s.perm, s.cursor, s.rank, s.world, y_pool=ds.y, y_out=self._y, clip_w=s.clip_w, denom=s.denom,
+                         n_valid=s.n_valid)
+        x, y, supports = st._data_chain(self._x, self._y, None, self.supports)
+        pred = st.model(x, y, supports).contiguous()                 # (the decoder's output is time-major)
+        ops.ssl_eval_scores(pred, y, s.clip_w, s.cursor, self._scores, s.rank, s.world, st.scaler_mean, st.scaler_std, 0.0, self.predictions)
+
+    @torch.no_grad()
+    def run(self, capture: bool = True) -> float:
+        """One pass -> eval_loss, the value of `evaluate_ssl` over batches of `loss_batch` clips.  capture: replay the step's body as
+        one HIP graph (captured at the first such call; it reads the parameters in place) instead of issuing it eagerly.  A
+        prediction that is NaN or infinite where the target is masked in raises ValueError (the reference turns such a batch's loss
+        into 0).  Leaves the model's mode, the step's counters, optimiser state, generators and sampler alone."""
+        st, s, model = self.step, self.sampler, self.step.model
+        multi = s.world > 1
+        if multi and not (dist.is_available() and dist.is_initialized() and dist.get_world_size() == s.world):
+            raise RuntimeError(f"DeviceSSLEvaluator: world={s.world} needs a process group of that size for the all-reduce of the scores")
+        was_training = model.training
+        model.eval()
+        try:
+            if self.predictions is not None:
+                ops.zero_(self.predictions)
+            self._replay(capture)
+            if multi:
+                dist.all_reduce(self._scores, op=dist.ReduceOp.SUM)
+            ops.ssl_eval_metrics(self._scores, self.loss_batch, self._record)
+            self.record = self._record.cpu()                         # the pass's one device-to-host copy
+        finally:
+            model.train(was_training)
+        self.result = OrderedDict(zip(ops.SSL_EVAL_RECORD, (float(v) for v in self.record)))
+        if self.result["bad"]:
+            raise ValueError(f"ssl_eval_scores: {int(self.result['bad'])} predictions are NaN or infinite where the target counts, among "
+                             f"{int(self.result['count'])} elements of {int(self.result['n'])} clips")
+        self.clip_mae = torch.where(self.clip_count > 0, self.clip_abs / self.clip_count.clamp(min=1.0), torch.zeros_like(self.clip_abs))
+        return self.result["loss"]

@@ -12,7 +12,7 @@ Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
-    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, eval_scores, eval_metrics.
+    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1525,6 +1525,80 @@ _define("eval_metrics", "(Tensor probs, Tensor labels, Tensor losses, bool searc
         _eval_metrics_impl, lambda *a: None)
 
 
+# ---- the SSL evaluation pass on the device (train_ssl.py:232-280; evaluation.py: DeviceSSLEvaluator) ------------------------------
+SSL_EVAL_MAX_CLIP_ELEMS = 1 << 24     # EEG_SSL_EVAL_MAX_CLIP_ELEMS: a clip holds fewer elements than this
+SSL_EVAL_RECORD_WORDS = 8             # EEG_SSL_EVAL_RECORD_WORDS: float64 words of the pass's record
+SSL_EVAL_RECORD = ("n", "batches", "loss", "pool_mae", "abs_sum", "count", "bad", "empty_batches")
+
+
+def _ssl_eval_pool(what, scores):
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[0] != 3 or scores.shape[1] < 1:
+        got = f"{tuple(scores.shape)}" if torch.is_tensor(scores) else type(scores).__name__
+        raise RuntimeError(f"{what}: scores must be (3, P) float64 (abs_sum | count | bad; ops.ssl_eval_buffers), got {got}")
+    p = int(scores.shape[1])
+    if p > EVAL_MAX_CLIPS:
+        raise RuntimeError(f"{what}: P={p} clips exceed the limit of one pass, {EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    return p
+
+
+def _ssl_eval_scores_impl(pred, target, clip_w, cursor, rank: int, world: int, use_scaler: bool, mean: float, std: float, mask_val: float,
+                          scores, keep=None) -> None:
+    lib = _lib.get_lib()
+    p = _ssl_eval_pool("ssl_eval_scores", scores)
+    _check(lib, scores, "scores", torch.float64)
+    dev = scores.device
+    if not torch.is_tensor(pred) or pred.dim() != 4 or pred.shape[0] < 1 or pred.numel() == 0:
+        raise RuntimeError(f"ssl_eval_scores: pred must be (B, Ty, N, D), got {tuple(pred.shape) if torch.is_tensor(pred) else type(pred).__name__}")
+    if not torch.is_tensor(target) or tuple(target.shape) != tuple(pred.shape):
+        raise RuntimeError(f"ssl_eval_scores: pred {tuple(pred.shape)} and target "
+                           f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__} differ in shape")
+    b, d = int(pred.shape[0]), int(pred.shape[3])
+    per = pred[0].numel()
+    if d % 4 != 0:
+        raise RuntimeError(f"ssl_eval_scores: D={d}: the clips are read in 16-byte pieces, D must be a multiple of 4")
+    if per >= SSL_EVAL_MAX_CLIP_ELEMS:
+        raise RuntimeError(f"ssl_eval_scores: a clip of {per} elements; at most {SSL_EVAL_MAX_CLIP_ELEMS - 1} (EEG_SSL_EVAL_MAX_CLIP_ELEMS)")
+    _eval_tensor("ssl_eval_scores", "pred", pred, torch.float32, pred.shape, dev)
+    _eval_tensor("ssl_eval_scores", "target", target, torch.float32, pred.shape, dev)
+    _eval_tensor("ssl_eval_scores", "clip_w", clip_w, torch.float32, (b,), dev)
+    _eval_tensor("ssl_eval_scores", "cursor", cursor, torch.int64, (1,), dev)
+    if keep is not None:
+        _eval_tensor("ssl_eval_scores", "keep", keep, torch.float32, (p,) + tuple(pred.shape[1:]), dev)
+    for name, t in (("pred", pred), ("target", target), ("keep", keep)):
+        if t is not None and t.data_ptr() % 16:
+            raise RuntimeError(f"ssl_eval_scores: {name} is not 16-byte aligned (a view with an odd element offset): pass a tensor of its own")
+    if world < 1 or not 0 <= rank < world:
+        raise RuntimeError(f"ssl_eval_scores: rank={rank} of world={world}")
+    lib.call("eeg_dcrnn_ssl_eval_scores", _p(pred), _p(target), _p(clip_w), _p(cursor), b, per, d, int(rank), int(world), p, 1 if use_scaler else 0,
+             float(mean), float(std), float(mask_val), _p(scores), _p(keep), _stream(scores))
+
+
+def ssl_eval_buffers(num_clips: int, device, clip_shape=None):
+    """(scores, record, keep) of an SSL evaluation pass over `num_clips` clips: the (3, P) float64 per-clip buffer (abs_sum | count |
+    bad, zeroed), the float64 record of SSL_EVAL_RECORD_WORDS words and -- with clip_shape = (Ty, N, D) -- the (P, Ty, N, D) buffer of
+    the kept predictions (else None); allocated once by the caller (`DeviceSSLEvaluator`)"""
+    if not 1 <= int(num_clips) <= EVAL_MAX_CLIPS:
+        raise RuntimeError(f"ssl_eval_buffers: P={num_clips} clips outside 1..{EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    keep = None if clip_shape is None else torch.zeros((int(num_clips),) + tuple(int(v) for v in clip_shape), dtype=torch.float32, device=device)
+    return (torch.zeros(3, int(num_clips), dtype=torch.float64, device=device),
+            torch.zeros(SSL_EVAL_RECORD_WORDS, dtype=torch.float64, device=device), keep)
+
+
+def _ssl_eval_metrics_impl(scores, group: int, record) -> None:
+    lib = _lib.get_lib()
+    p = _ssl_eval_pool("ssl_eval_metrics", scores)
+    _check(lib, scores, "scores", torch.float64)
+    _eval_tensor("ssl_eval_metrics", "record", record, torch.float64, (SSL_EVAL_RECORD_WORDS,), scores.device)
+    if group < 1:
+        raise RuntimeError(f"ssl_eval_metrics: groups of {group} clips (the batch size of the loss, >= 1)")
+    lib.call("eeg_dcrnn_ssl_eval_metrics", _p(scores), p, int(group), _p(record), _stream(scores))
+
+
+_define("ssl_eval_scores", "(Tensor pred, Tensor target, Tensor clip_w, Tensor cursor, int rank, int world, bool use_scaler, float mean, float std, "
+        "float mask_val, Tensor(a!) scores, Tensor(b!)? keep) -> ()", _ssl_eval_scores_impl, lambda *a: None)
+_define("ssl_eval_metrics", "(Tensor scores, int group, Tensor(a!) record) -> ()", _ssl_eval_metrics_impl, lambda *a: None)
+
+
 def _loss_setup(ctx, inputs, output):
     ctx.save_for_backward(output[1])
     ctx.n_in = len(inputs)
@@ -2238,4 +2312,28 @@ def eval_metrics(probs, labels, losses, search: bool = False, thresh: float = 0.
     if ws is None or record is None:
         ws, record = eval_metrics_buffers(probs.shape[0], 1 if probs.dim() == 1 else probs.shape[1], probs.device)
     torch.ops.eeg_dcrnn.eval_metrics(probs, labels, losses, bool(search), float(thresh), ws, record)
+    return record
+
+
+def ssl_eval_scores(pred, target, clip_w, cursor, scores, rank: int = 0, world: int = 1, mean=None, std=None, mask_val: float = 0.0, keep=None):
+    """Per-clip masked-MAE sums of one step of an SSL evaluation pass over a pool in order, behind `gather_clips(..., clip_w=, denom=,
+    n_valid=)` (which has advanced `cursor`): slot b of pred / target (B, Ty, N, D) is pool position cursor - B*world + rank*B + b; a
+    slot with clip_w != 0 and a position in [0, P) writes scores[:, pos] = (float64 sum of the float32 |d| over its masked-in
+    elements, their number, the number of those whose d is not finite -- left out of the sum), with d and the mask as in
+    `masked_regression_loss(..., mean, std, "mae", mask_val)`.  A clip's sum does not depend on B, the slot or the rank, bit for bit.
+    keep (P, Ty, N, D): the slot's pred is copied to keep[pos].  Nothing is ever written outside scores (3, P) and keep.  One launch,
+    no allocation, capturable."""
+    scaled = mean is not None
+    torch.ops.eeg_dcrnn.ssl_eval_scores(pred, target, clip_w, cursor, int(rank), int(world), scaled, float(mean) if scaled else 0.0,
+                                        float(std) if scaled else 1.0, float(mask_val), scores, keep)
+
+
+def ssl_eval_metrics(scores, group: int, record=None):
+    """The record of an SSL evaluation pass from its (3, P) scores, on the device, as SSL_EVAL_RECORD_WORDS float64 words named by
+    SSL_EVAL_RECORD: n, batches = ceil(P / group), loss = the reference's AverageMeter over consecutive batches of `group` clips (a
+    batch with nothing masked in counts 0 with its weight), pool_mae = sum abs_sum / sum count (independent of group), the totals of
+    abs_sum, count and bad, empty_batches.  record: `ssl_eval_buffers` (allocated here when not given).  Returns record; no host sync."""
+    if record is None:
+        record = torch.zeros(SSL_EVAL_RECORD_WORDS, dtype=torch.float64, device=scores.device)
+    torch.ops.eeg_dcrnn.ssl_eval_metrics(scores, int(group), record)
     return record

@@ -607,6 +607,14 @@ class TrainStep:
         from .evaluation import DeviceEvaluator
         return DeviceEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world)
 
+    def ssl_evaluator(self, dataset, batch_size: int, supports=None, rank: Optional[int] = None, world: Optional[int] = None,
+                      keep_predictions: bool = False, loss_batch: Optional[int] = None):
+        """the SSL evaluation pass (train_ssl.py:232-280) of this step's model and pair chain over device-resident input and target
+        pools, on the device (`evaluation.DeviceSSLEvaluator`): `ev = step.ssl_evaluator(dev_ds, B); eval_loss = ev.run()`"""
+        from .evaluation import DeviceSSLEvaluator
+        return DeviceSSLEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world, keep_predictions=keep_predictions,
+                                  loss_batch=loss_batch)
+
     # -- checkpointing (utils.CheckpointSaver / load_model_checkpoint use these like an optimizer's) -------
     def state_dict(self):
         """with a sampler attached also its (seed, epoch, cursor): a resumed run continues mid-epoch on the same clips"""

@@ -418,6 +418,31 @@ size_t eeg_dcrnn_eval_metrics_ws_bytes(int64_t P, int C);
 int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_bytes, const float* losses, int64_t P, int C, int search,
                            double thresh, void* ws, int64_t* record, void* stream);
 
+/* The SSL evaluation pass (train_ssl.py:232-280) on the device.
+ *
+ * eeg_dcrnn_ssl_eval_scores: one launch behind the decoder of every step of a pass over a pool of P clips in order, the twin of
+ * eeg_dcrnn_eval_scores (same slot arithmetic, unsigned: pos = cursor[0] - B*world + rank*B + b; a slot writes only if
+ * clip_w[b] != 0 AND 0 <= pos < P; nothing is ever written outside scores and keep).  pred / target: (B, clip_elems) float32, the
+ * batch as the loss sees it (standardised), 16-byte aligned, clip_elems a multiple of D, D a multiple of 4,
+ * clip_elems < EEG_SSL_EVAL_MAX_CLIP_ELEMS.  Per element the terms of eeg_dcrnn_masked_loss: scaled != 0: ps = p*std + mean,
+ * ys = y*std + mean (two roundings each), d = ps - ys in float32, masked in iff ys != mask_val.  scores is (3, P) float64:
+ * scores[0][pos] = the float64 sum of the float32 |d| over the clip's masked-in elements with a finite d, scores[1][pos] = the
+ * number of masked-in elements, scores[2][pos] = the number of masked-in elements whose d is NaN or infinite.  One workgroup per
+ * slot, a fixed assignment of 16-byte pieces to threads and a fixed tree: a clip's sum has the same bits whatever B, slot, rank.
+ * keep: null, or (P, clip_elems) float32, 16-byte aligned: the slot's pred is copied to keep[pos].
+ *
+ * eeg_dcrnn_ssl_eval_metrics: the pass's record from scores, EEG_SSL_EVAL_RECORD_WORDS float64 words in device memory, one block,
+ * fixed order: 0 n = P, 1 batches = ceil(P / G), 2 loss = sum_g n_g * L_g / P over the consecutive groups g = [g*G, min((g+1)*G, P))
+ * with L_g = S_g / C_g (0 where C_g == 0): the reference's AverageMeter over batches of G clips, 3 pool_mae = sum abs_sum / sum
+ * count (0 if nothing is masked in), 4 / 5 / 6 the totals of abs_sum, count and bad, 7 the groups with C_g == 0.  G >= 1; a G
+ * above P is one group.  No allocation, no host synchronisation. */
+#define EEG_SSL_EVAL_MAX_CLIP_ELEMS (1 << 24)
+#define EEG_SSL_EVAL_RECORD_WORDS 8
+int eeg_dcrnn_ssl_eval_scores(const float* pred, const float* target, const float* clip_w, const int64_t* cursor, int B, int64_t clip_elems, int D,
+                              int rank, int world, int64_t P, int scaled, float mean, float std, float mask_val, double* scores, float* keep,
+                              void* stream);
+int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, double* record, void* stream);
+
 /* utils.last_relevant_pytorch (utils.py:346-357): last[b] = Htop[lengths[b]-1, b]. Htop (T,B,NH). */
 int eeg_dcrnn_gather_last(const float* Htop, const int64_t* lengths, int T, int B, int NH,
                           float* last, void* stream);
