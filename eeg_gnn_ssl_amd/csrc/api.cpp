@@ -578,6 +578,11 @@ int check_decoder_dims(const eeg_decoder_dims* d) {
     if (check_dims(d->N, d->H, d->Dout, d->M)) return 1;
     return check_dims(d->N, d->H, d->H, d->M);
 }
+// The persistent decoder kernels: the caller asks dec_plan (dec_launch.h) with these dims and knobs (compile-time zeros in the product
+// build) whether they take the decoder, and the launchers of dec_inst.cpp / decb_inst.cpp execute the plan.
+DecCall dec_call(const eeg_decoder_dims* d) {
+    return DecCall{d->T, d->B, d->N, d->H, d->Dout, d->M, d->L, g_tune[EEG_TUNE_DEC_FWD_PER_STEP], g_tune[EEG_TUNE_DEC_BWD_PER_STEP]};
+}
 int copy_floats(float* dst, const float* src, size_t n, hipStream_t st) {
     return platform_copy_floats(dst, src, n, st) ? 0 : fail("device copy failed");
 }
@@ -1425,20 +1430,9 @@ size_t eeg_dcrnn_decoder_saved_floats(const eeg_decoder_dims* d) { return dec_di
 size_t eeg_dcrnn_decoder_fwd_ws_floats(const eeg_decoder_dims* d) { return dec_dims_positive(d) ? (size_t)d->B * d->N * 3 * d->H : 0; }
 size_t eeg_dcrnn_decoder_bwd_ws_floats(const eeg_decoder_dims* d) { return dec_dims_positive(d) ? dec_layout(d).bwd_total : 0; }
 
-// the persistent decoder kernels (kernels_decoder.h) cover this shape: forward and backward always pair up over the shared `saved`
-// layout (64 units, <= 20 nodes, <= 4 layers, horizon <= 64, Dout <= 256 with Dout/4 divisible by 4 or 5 = the weight-group
-// sizes of the backward's projection transpose, both LDS budgets: past 128 outputs those decide -- M = 5 with two layers fits up
-// to 200 outputs, M = 5 with three layers and M = 7 do not: table in DESIGN.md 4.4)
-static bool dec_persistent_ok(const eeg_decoder_dims* d) {
-    const int q4 = d->Dout / 4;
-    return d->H == 64 && d->N <= kDecRows && d->L >= 1 && d->L <= 4 && d->T >= 1 && d->T <= 64 && d->Dout <= 256
-           && (q4 % 5 == 0 || q4 % 4 == 0) && seq_m_supported(d->M)
-           && dec_fwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes
-           && dec_bwd_lds_floats(d->M, d->L, d->Dout) * sizeof(float) <= kMaxLdsBytes;
-}
 int eeg_dcrnn_decoder_is_persistent(const eeg_decoder_dims* d) {
     if (check_decoder_dims(d)) return 0;
-    return dec_persistent_ok(d) ? 1 : 0;
+    return dec_plan(dec_call(d)).covered ? 1 : 0;
 }
 
 int eeg_dcrnn_decoder_fwd(const eeg_decoder_dims* d, const float* targets, const int32_t* teacher, const float* h0,
@@ -1467,32 +1461,28 @@ int eeg_dcrnn_decoder_fwd(const eeg_decoder_dims* d, const float* targets, const
     for (int l = 0; l < L; ++l)
         if (copy_floats(saved + y.hext[l], h0 + (size_t)l * state, state, st)) return 1;
     // ---- persistent path: ONE launch for all T steps, layers and the projection (kernels_decoder.h); where it does not
-    //      apply (hidden size, montage > 20 nodes, LDS) the per-step launches below run
-    {
-        const size_t lds = dec_fwd_lds_floats(M, L, Dout) * sizeof(float);
-        if (g_tune[EEG_TUNE_DEC_FWD_PER_STEP] == 0 && dec_persistent_ok(d)) {
-            DecFwdArgs a;
-            for (int l = 0; l < L; ++l) {
-                const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
-                a.l[l] = DecLayerPtrs{packs[l] + p.bxq, packs[l] + p.bias, packs[l] + p.bhg, packs[l] + p.bhc,
-                                      saved + y.hext[l], saved + y.rs[l], saved + y.us[l], saved + y.cs[l], saved + y.rhs[l],
-                                      saved + y.hpl[l], saved + y.rpl[l]};
-            }
-            for (int l = L; l < 4; ++l) a.l[l] = a.l[0];
-            a.P = P; a.targets = targets; a.ppack = ppack; a.pbias = pbias;
-            a.out = out; a.xin = xin; a.planes0 = saved + y.planes[0];
-            a.planes0_stride = (size_t)d->T * RB * Dout;
-            a.hplane_stride = (size_t)(d->T + 1) * state;
-            a.teacher_mask = 0;
-            a.teacher_dev = tf_dev ? reinterpret_cast<const int*>(teacher) : nullptr;
-            for (int t = 0; t < d->T && !tf_dev; ++t)
-                if (teacher != nullptr && teacher[t] != 0) a.teacher_mask |= 1ull << t;
-            a.p_batched = d->p_batched; a.T = d->T; a.B = B; a.N = N; a.Dout = Dout; a.L = L; a.act = d->act;
-            a.drop = drop; a.rng_used = used; a.hd = saved + y.hd; a.probe = seq_probe_arg(st);
-            const int rc = launch_dec_fwd_persist(M, a, lds, st);
-            if (rc == 0) return 0;
-            if (rc == 2) return fail("decoder_fwd: persistent kernel launch failed");
+    //      apply (dec_plan: hidden size, montage > 20 nodes, LDS, ...) the per-step launches below run
+    const DecPlan plan = dec_plan(dec_call(d));
+    if (plan.fwd_persistent) {
+        DecFwdArgs a;
+        for (int l = 0; l < L; ++l) {
+            const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
+            a.l[l] = DecLayerPtrs{packs[l] + p.bxq, packs[l] + p.bias, packs[l] + p.bhg, packs[l] + p.bhc,
+                                  saved + y.hext[l], saved + y.rs[l], saved + y.us[l], saved + y.cs[l], saved + y.rhs[l],
+                                  saved + y.hpl[l], saved + y.rpl[l]};
         }
+        for (int l = L; l < 4; ++l) a.l[l] = a.l[0];
+        a.P = P; a.targets = targets; a.ppack = ppack; a.pbias = pbias;
+        a.out = out; a.xin = xin; a.planes0 = saved + y.planes[0];
+        a.planes0_stride = (size_t)d->T * RB * Dout;
+        a.hplane_stride = (size_t)(d->T + 1) * state;
+        a.teacher_mask = 0;
+        a.teacher_dev = tf_dev ? reinterpret_cast<const int*>(teacher) : nullptr;
+        for (int t = 0; t < d->T && !tf_dev; ++t)
+            if (teacher != nullptr && teacher[t] != 0) a.teacher_mask |= 1ull << t;
+        a.p_batched = d->p_batched; a.T = d->T; a.B = B; a.N = N; a.Dout = Dout; a.L = L; a.act = d->act;
+        a.drop = drop; a.rng_used = used; a.hd = saved + y.hd; a.probe = seq_probe_arg(st);
+        return launch_dec_fwd_persist(plan, a, st) ? fail("decoder_fwd: persistent kernel launch failed") : 0;
     }
     if (tf_dev) return fail("decoder_fwd: teacher_on_device needs the persistent decoder kernel, which does not cover this shape "
                             "(H=%d, N=%d, L=%d, T=%d, Dout=%d, M=%d): pass the flags as a host array", H, N, L, d->T, Dout, M);
@@ -1561,35 +1551,28 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
     auto feeds_back = [&](int t) { return t + 1 < T && !(!tf_dev && teacher != nullptr && teacher[t] != 0); };
     // ---- persistent path: ONE launch walks the T steps backwards (kernels_decoder.h); it leaves dXW of every
     //      (layer, step), dOtot and dh0 -- the hoisted parameter gradients below are common to both paths
-    bool persistent = false;
-    {
-        const int q4 = Dout / 4;
-        const int dt = q4 % 5 == 0 ? 5 : (q4 % 4 == 0 ? 4 : 0);
-        const size_t lds = dec_bwd_lds_floats(M, L, Dout) * sizeof(float);
-        if (g_tune[EEG_TUNE_DEC_BWD_PER_STEP] == 0 && dec_persistent_ok(d)) {
-            DecBwdArgs a;
-            for (int l = 0; l < L; ++l) {
-                const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
-                a.l[l] = DecBwdLayerPtrs{packs[l] + p.c1, packs[l] + p.c2, saved + y.hext[l], saved + y.rs[l],
-                                         saved + y.us[l], saved + y.cs[l], ws + y.dxw[l]};
-            }
-            for (int l = L; l < 4; ++l) a.l[l] = a.l[0];
-            a.P = P; a.tpack = tpack; a.dOut = dOut; a.dOtot = dOtot; a.dh0 = dh0;
-            a.dbias0 = ws + y.dbias[0]; a.dbias1 = ws + y.dbias[L > 1 ? 1 : 0];
-            a.feeds_mask = 0;
-            a.teacher_dev = tf_dev ? reinterpret_cast<const int*>(teacher) : nullptr;
-            for (int t = 0; t < T; ++t)
-                if (feeds_back(t)) a.feeds_mask |= 1ull << t;
-            a.p_batched = d->p_batched; a.T = T; a.B = B; a.N = N; a.Dout = Dout; a.L = L; a.act = d->act;
-            a.drop = drop; a.rng_used = used; a.probe = seq_probe_arg(st);
-            const int rc = launch_dec_bwd_persist(M, dt, a, lds, st);
-            if (rc == 2) return fail("decoder_bwd: persistent kernel launch failed");
-            persistent = rc == 0;
+    const DecPlan plan = dec_plan(dec_call(d));
+    if (plan.bwd_persistent) {
+        DecBwdArgs a;
+        for (int l = 0; l < L; ++l) {
+            const CellPack p = make_cell_pack(l == 0 ? Dout : H, H, M);
+            a.l[l] = DecBwdLayerPtrs{packs[l] + p.c1, packs[l] + p.c2, saved + y.hext[l], saved + y.rs[l],
+                                     saved + y.us[l], saved + y.cs[l], ws + y.dxw[l]};
         }
+        for (int l = L; l < 4; ++l) a.l[l] = a.l[0];
+        a.P = P; a.tpack = tpack; a.dOut = dOut; a.dOtot = dOtot; a.dh0 = dh0;
+        a.dbias0 = ws + y.dbias[0]; a.dbias1 = ws + y.dbias[L > 1 ? 1 : 0];
+        a.feeds_mask = 0;
+        a.teacher_dev = tf_dev ? reinterpret_cast<const int*>(teacher) : nullptr;
+        for (int t = 0; t < T; ++t)
+            if (feeds_back(t)) a.feeds_mask |= 1ull << t;
+        a.p_batched = d->p_batched; a.T = T; a.B = B; a.N = N; a.Dout = Dout; a.L = L; a.act = d->act;
+        a.drop = drop; a.rng_used = used; a.probe = seq_probe_arg(st);
+        if (launch_dec_bwd_persist(plan, a, st)) return fail("decoder_bwd: persistent kernel launch failed");
     }
-    if (tf_dev && !persistent) return fail("decoder_bwd: teacher_on_device needs the persistent decoder kernel, which does not cover "
+    if (tf_dev && !plan.bwd_persistent) return fail("decoder_bwd: teacher_on_device needs the persistent decoder kernel, which does not cover "
                                            "this shape (H=%d, N=%d, L=%d, T=%d, Dout=%d, M=%d)", H, N, L, T, Dout, M);
-    for (int t = persistent ? -1 : T - 1; t >= 0; --t) {
+    for (int t = plan.bwd_persistent ? -1 : T - 1; t >= 0; --t) {
         // total gradient of out_t: the loss term, plus (autoregressive feedback) dx of layer 0 at step t+1, which
         // the adjoint diffusion of that step has already added into dOtot[t]
         const float* dO = feeds_back(t) ? dOtot + (size_t)t * xstep : dOut + (size_t)t * xstep;
@@ -1639,7 +1622,7 @@ int eeg_dcrnn_decoder_bwd(const eeg_decoder_dims* d, const int32_t* teacher, con
                               ws + y.dxw[l], P, saved + y.hpl[l], saved + y.rpl[l], hstride, nullptr, nullptr,
                               ws + y.partial, y.lw[l], !first_use, dWg[l], dWc[l], st)) return 1;
     }
-    if (persistent) {   // per-clip sums over steps and nodes (layers >= 1 share a cell: already added up)
+    if (plan.bwd_persistent) {   // per-clip sums over steps and nodes (layers >= 1 share a cell: already added up)
         if (colsum(ws + y.dbias[0], B, 3 * H, 2 * H, ws + y.colsum, dbg[0], dbc[0], st)) return 1;
         if (L > 1 && colsum(ws + y.dbias[1], B, 3 * H, 2 * H, ws + y.colsum, dbg[1], dbc[1], st)) return 1;
     } else {

@@ -23,6 +23,8 @@ constexpr int kMaxNodes = 32;   // node rows are padded to two 16-row MFMA tiles
 constexpr int kDecRows = 20;    // node rows of the LDS tiles of the decoder / streamed-weight kernels (montages of at most 20 nodes)
 constexpr size_t kMaxLdsBytes = 160 * 1024;   // LDS of one gfx950 CU
 constexpr int kMaxM = 8;        // hop matrices incl. identity (K<=3 with two supports -> 7)
+constexpr int kPStride = 34;                       // row stride of a hop-polynomial matrix in LDS (lds_diffuse.h): lds_stride(32)
+constexpr int kPFloats = kMaxNodes * kPStride;     // one padded 32x32 matrix
 #if defined(EEG_DEV)            // make dev / the test emulator: tuning knobs + the recurrent kernels' cycle probe
 constexpr bool kDevBuild = true;
 #else

@@ -1,44 +1,36 @@
-// Instantiations of the persistent decoder backward kernel (kernels_decoder.h), in their own translation unit.
+// Instantiations of the persistent decoder backward kernel (kernels_decoder.h), in their own translation unit: the launcher
+// executes a plan of dec_launch.h (which instance, grid, block, LDS: decided there, not here).
 #include "kernels_decoder.h"
 #include "prof.h"
-#include "seq_launch.h"
 
 namespace eeg {
 namespace {
-constexpr int kCxNarrow = cell_pack_cx_cols(64, 64) / 16;
 template <int M, int DT, int CX0>
-int launch_one(const DecBwdArgs& a, size_t lds, hipStream_t st) {
-    EEG_SET_MAX_LDS((dec_bwd_persist_kernel<64, M, DT, CX0>), lds);
-    EEG_LAUNCH_P("bwd_persist", (dec_bwd_persist_kernel<64, M, DT, CX0>), dim3(a.B < 256 ? a.B : 256), dim3(256), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+int launch_one(const DecPlan& p, const DecBwdArgs& a, hipStream_t st) {
+    EEG_SET_MAX_LDS((dec_bwd_persist_kernel<64, M, DT, CX0>), p.lds_bwd);
+    EEG_LAUNCH_P("bwd_persist", (dec_bwd_persist_kernel<64, M, DT, CX0>), dim3(p.grid), dim3(p.block), p.lds_bwd, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+// one dispatch over (M, dt, cx0); what is compiled is what dec_has_instance says, the predicate the plan covers a decoder by
 template <int M, int CX0>
-int launch_cx(int dt, const DecBwdArgs& a, size_t lds, hipStream_t st) {
-    return dt == 5 ? launch_one<M, 5, CX0>(a, lds, st) : launch_one<M, 4, CX0>(a, lds, st);
+int launch_cx(const DecPlan& p, const DecBwdArgs& a, hipStream_t st) {
+    if constexpr (dec_has_instance(M, CX0)) return p.dt == 5 ? launch_one<M, 5, CX0>(p, a, st) : launch_one<M, 4, CX0>(p, a, st);
+    return 1;
 }
 template <int M>
-int launch_m(int dt, const DecBwdArgs& a, size_t lds, hipStream_t st) { return launch_cx<M, kCxNarrow>(dt, a, lds, st); }
-// more than 128 outputs: the wide instantiations, by the column tiles of layer 0's c1 / c2 packs (16 up to 192 outputs, 20 up to 256)
-template <int M>
-int launch_w(int dt, const DecBwdArgs& a, size_t lds, hipStream_t st) {
-    if (a.Dout <= 128) return launch_m<M>(dt, a, lds, st);
-    const int cx0 = cell_pack_cx_cols(a.Dout, 64) / 16;
-    if (cx0 == 16) return launch_cx<M, 16>(dt, a, lds, st);
-    if (cx0 == 20) return launch_cx<M, 20>(dt, a, lds, st);
-    return 1;
+int launch_m(const DecPlan& p, const DecBwdArgs& a, hipStream_t st) {
+    return p.cx0 == 12 ? launch_cx<M, 12>(p, a, st) : p.cx0 == 16 ? launch_cx<M, 16>(p, a, st) : launch_cx<M, 20>(p, a, st);
 }
 }  // namespace
 
-// 0 ok, 1 unsupported M or width, 2 launch error.  dt = k-steps per weight group of the projection transpose (5 or 4;
-// (Dout/4) % dt == 0).  Wide outputs (Dout > 128) exist for M <= 5: the LDS tiles of M = 7 do not fit at any such width.
-int launch_dec_bwd_persist(int M, int dt, const DecBwdArgs& a, size_t lds, hipStream_t st) {
-    switch (M) {
-        case 1: return launch_w<1>(dt, a, lds, st);
-        case 2: return launch_w<2>(dt, a, lds, st);
-        case 3: return launch_w<3>(dt, a, lds, st);
-        case 4: return launch_w<4>(dt, a, lds, st);
-        case 5: return launch_w<5>(dt, a, lds, st);
-        case 7: return a.Dout <= 128 ? launch_m<7>(dt, a, lds, st) : 1;
+int launch_dec_bwd_persist(const DecPlan& p, const DecBwdArgs& a, hipStream_t st) {
+    switch (p.M) {
+        case 1: return launch_m<1>(p, a, st);
+        case 2: return launch_m<2>(p, a, st);
+        case 3: return launch_m<3>(p, a, st);
+        case 4: return launch_m<4>(p, a, st);
+        case 5: return launch_m<5>(p, a, st);
+        case 7: return launch_m<7>(p, a, st);
         default: return 1;
     }
 }

@@ -17,40 +17,18 @@
 //     step inputs themselves) is written in the layout of eeg_dcrnn_decoder_fwd's `saved` block, so the existing
 //     backward operator is unchanged.
 // Wave w of 4 owns column tile w of r, u, c and h (64 units).  At most 20 nodes (second node tile on v_mfma_f32_4x4x1).
+// Which decoders these kernels take, and as which instance: dec_plan (dec_launch.h), next to the operands and the LDS sizes.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "dec_launch.h"   // the operands (DecFwdArgs, DecBwdArgs), the LDS geometry, the plan that selects an instance
 #include "kernels_seq.h"
 #include "lds_diffuse.h"
 #include "nnq_order.h"
 
 namespace eeg {
 
-struct DecLayerPtrs {
-    const float *bxq, *bias, *bhg, *bhc;                      // weight packs of the layer's cell (kernels_pack.h; bxq: the x-part in quad order)
-    float *hext, *rs, *us, *cs, *rhs, *hpl, *rpl;             // saved for the backward (decoder `saved` layout)
-};
-struct DecFwdArgs {
-    DecLayerPtrs l[4];
-    const float* P;
-    const float* targets;         // (T,B,N,Dout), read where teacher_mask says so (may be NULL when the mask is 0)
-    const float *ppack, *pbias;   // projection: fragment pack (K = H, nct_o column tiles) and zero-padded bias
-    float *out, *xin, *planes0;   // (T,B,N,Dout) predictions, step inputs, and the hop planes of the step inputs (M-1 planes)
-    size_t planes0_stride;        // floats between two planes of planes0
-    size_t hplane_stride;         // floats between two planes of hpl / rpl = (T+1)*B*N*H
-    unsigned long long teacher_mask;   // bit t: step t+1 is fed targets[t] instead of out[t] (model.py:194-200)
-    const int* teacher_dev;            // nullable DEVICE int32[T]: when set, the flags are read from it at launch instead (a captured
-                                       // graph then replays with whatever eeg_dcrnn_teacher_flags drew in front of it)
-    int p_batched, T, B, N, Dout, L, act;
-    // nn.Dropout in front of the projection (model.py:191, training): the projection reads drop(h_top_t) = mask * h_top_t; the
-    // recurrence keeps h_top_t.  Element ((t*B + b)*N + n)*H + h of the (T,B,N,H) top outputs takes word e % 4 of Philox counter
-    // rng_used[1] + e / 4 under key rng_used[0] (common.h).  hd (T,B,N,H): the dropped rows, the A operand of dW_p in the backward.
-    DropCfg drop;
-    const unsigned long long* rng_used;
-    float* hd;
-    long long* probe;             // phase cycles (development builds with -DEEG_DEC_PROBE: tools/dec_probe.py), else unused
-};
 #if defined(EEG_DEV) && defined(EEG_DEC_PROBE)
 constexpr bool kDecProbe = true;
 #else
@@ -292,7 +270,6 @@ __device__ __forceinline__ void gemm_stream_quad(const float* __restrict__ tile,
 // group lg's 16-byte piece of chunk c comes from a table in LDS (nnq_col_table: tail chunks gather the leftover pieces of the
 // slots; padding chunks and missing pieces point at column 0: zero weights, any finite operand does).
 constexpr int kNnqPD = 3;
-__host__ __device__ inline int nnq_padded_chunks(int nseg, int F) { return round_up(make_nnq_order(nseg, F).nch, 4); }
 // tab[c * 4 + g], c < nnq_padded_chunks: float column of piece g of chunk c in a tile with hop slots of slotw columns
 __device__ __forceinline__ void nnq_col_table(int* tab, int nseg, int F, int slotw) {
     const NnqOrder ko = make_nnq_order(nseg, F);
@@ -393,14 +370,6 @@ __device__ __forceinline__ void gemm_stream_nnq(const float* __restrict__ tile, 
         EEG_PIN(t);
         acc[i][1][0] += rem4_reduce(t);
     }
-}
-
-// LDS floats of dec_fwd_persist_kernel<64, M>
-__host__ __device__ constexpr size_t dec_fwd_lds_floats(int M, int L, int Dout) {
-    const int H = 64, KAP = M * H, XS = lds_stride_q(M * round_up(Dout, 16));
-    return (size_t)(M - 1) * kPFloats + (size_t)L * kDecRows * KAP + (size_t)kDecRows * (XS > KAP ? XS : KAP)
-           + (size_t)kDecRows * 64       // + the dropped copy of the top state the projection reads (swizzled [rows][64])
-           + 4 * (size_t)nnq_padded_chunks(M, Dout);   // + the piece-column table of the layer-0 x-part (gemm_stream_nnq)
 }
 
 template <int H, int M>
@@ -647,39 +616,12 @@ namespace eeg {
 // previous step's output gradient.  On chip per clip: the dC / [dR|dU] tiles with their adjoint hop rows, the
 // output-gradient tiles, the recurrent gradients dh^l (lane-linear LDS slots).  It emits dXW of every (layer, step) --
 // the hoisted parameter-gradient GEMMs, the bias column sums and the projection gradients stay as they are -- the total
-// output gradients dOtot and dh0.  At most 20 nodes, 64 units, Dout <= 256 where the LDS tiles fit (dec_bwd_lds_floats).
-// Layer 0's c1 / c2 packs have CX0 column tiles: 12 up to 128 outputs, 16 up to 192, 20 up to 256 (cell_pack_cx_cols); the
+// output gradients dOtot and dh0.  At most 20 nodes, 64 units (the shapes it is handed: dec_plan of dec_launch.h).
+// Layer 0's c1 / c2 packs have CX0 column tiles (12, 16 or 20 by the output width: dec_cx0 there); the
 // layers above always 12.  Up to 128 outputs a wave owns at most two input-gradient tiles (w, w + 4) and GEMM1 / GEMM2 carry
 // them beside its hidden tile; the wide instantiations (CX0 > 12: 9..16 input-gradient tiles) add a SECOND pass over the same
 // adjoint hop rows for tiles w + 8, w + 12 (the wide tail) instead of a fourth and fifth tile in the first: five tiles of
 // weight ring and accumulators do not fit beside the rest at one wave per SIMD.
-struct DecBwdLayerPtrs {
-    const float *c1, *c2;                            // weight packs [hidden | input] (kernels_pack.h)
-    const float *hext, *rs, *us, *cs;                // saved by the forward
-    float* dxw;                                      // (T,B,N,3H) out
-};
-struct DecBwdArgs {
-    DecBwdLayerPtrs l[4];
-    const float* P;
-    const float* tpack;           // projection, transposed role: K = Dout, H/16 column tiles
-    const float* dOut;            // (T,B,N,Dout) loss gradient
-    float* dOtot;                 // (T,B,N,Dout) total gradient of out_t (loss + feedback)
-    float* dh0;                   // (L,B,N,H)
-    float *dbias0, *dbias1;       // (B,3H) per-clip bias-gradient sums [r|u|c] over steps and nodes: layer 0, layers >= 1 (one shared cell)
-    unsigned long long feeds_mask;     // bit t: out_t is the input of step t+1 (no teacher forcing there, t+1 < T)
-    const int* teacher_dev;            // nullable DEVICE int32[T] teacher-forcing flags: when set, feeds_mask is derived from it at launch
-    int p_batched, T, B, N, Dout, L, act;
-    DropCfg drop;                      // dropout in front of the projection (DecFwdArgs): d h_top = mask * (dO W_p), mask recomputed
-    const unsigned long long* rng_used;
-    long long* probe;                  // phase cycles (development builds with -DEEG_DEC_PROBE), else unused
-};
-
-__host__ __device__ constexpr size_t dec_bwd_lds_floats(int M, int L, int Dout) {
-    const int H = 64, FS = lds_stride_q(round_up(Dout, 16));
-    return (size_t)(M - 1) * kPFloats + (size_t)kDecRows * (M * H + M * 2 * H) + 2 * (size_t)kDecRows * FS
-           + (size_t)L * 4 * 2 * 256;
-}
-
 template <int H, int M, int DT, int CX0 = cell_pack_cx_cols(64, 64) / 16>
 __global__ __launch_bounds__(256, 1) void dec_bwd_persist_kernel(DecBwdArgs a) {
     unsigned long long feeds_mask = a.feeds_mask;

@@ -7,9 +7,7 @@
 
 namespace eeg {
 
-constexpr int kPStride = 34;                       // lds_stride(32)
-constexpr int kPFloats = kMaxNodes * kPStride;     // one padded 32x32 matrix
-
+// (kPStride, kPFloats: common.h, where the host-only launch plans read them too)
 // P (global): (Bp, M-1, N, N); graph g.  Pl (LDS): (M-1) x [32][kPStride], zero padded.
 __device__ __forceinline__ void lds_load_polys(float* Pl, const float* __restrict__ P, int g, int M, int N) {
     const int total = (M - 1) * kPFloats;

@@ -128,10 +128,5 @@ int launch_seq_bwd_h16(int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t
 int launch_seq_bwd_h32(int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st);
 int launch_seq_bwd_h64(int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st);
 int launch_seq_bwd_stream(int M, const SeqPlan& p, const SeqBwdArgs& a, hipStream_t st);   // SeqKind::Stream
-struct DecFwdArgs;
-struct DecBwdArgs;
-int launch_dec_fwd_persist(int M, const DecFwdArgs& a, size_t lds, hipStream_t st);
-int launch_dec_bwd_persist(int M, int dt, const DecBwdArgs& a, size_t lds, hipStream_t st);
-
 
 }  // namespace eeg

@@ -41,7 +41,7 @@ enum {
     EEG_TUNE_GRAM_WGS = 7,           /* the same, correlation-Gram launches */
     /* 8: unused (rounds 1-3: k-steps per weight group of the layer-0 input part in the persistent decoder forward) */
     EEG_TUNE_DIFFUSE_ADJ_LDS = 9,    /* 1: LDS/MFMA adjoint diffusion */
-    EEG_TUNE_DEC_BWD_PER_STEP = 10,  /* 1: per-step launches in the decoder backward instead of the persistent kernel */
+    EEG_TUNE_DEC_BWD_PER_STEP = 10,  /* 1: per-step launches in the decoder backward instead of the persistent kernel (read by the decoder plan, csrc/dec_launch.h) */
     EEG_TUNE_DEC_FWD_PER_STEP = 11,  /* 1: the same for the decoder forward */
     EEG_TUNE_SPEC_DX_PASSES = 17,    /* 1: input gradient of a spectral layer as grouped GEMM + node-mix pass instead of gemm_dxf_kernel (read by the spectral plan, csrc/spec_launch.h) */
     EEG_TUNE_DIFFUSE_ADJ_PLANES = 18, /* 1: the round-4 adjoint diffusion (hop planes one at a time) instead of the row-streaming one */

@@ -1,6 +1,7 @@
-// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h, csrc/spec_launch.h and csrc/seq_launch.h for the calls read from
-// stdin, one line each (see tests/test_gemm_plans.py, tests/test_spec_plans.py, tests/test_seq_kernels.py).  Host code only: the first
-// two headers must compile without kernel bodies; seq_launch.h brings kernels_seq.h along, which is host code under platform_emu.h.
+// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h, csrc/spec_launch.h, csrc/seq_launch.h and csrc/dec_launch.h for the
+// calls read from stdin, one line each (see tests/test_gemm_plans.py, tests/test_spec_plans.py, tests/test_seq_kernels.py,
+// tests/test_dec_plans.py).  Host code only: gemm_launch.h, spec_launch.h and dec_launch.h must compile without kernel bodies;
+// seq_launch.h brings kernels_seq.h along, which is host code under platform_emu.h.
 //   nn   nseg F R nct_total ldc O batch_major quad_pack bf3_nct num_cus KNOBS  ->  kind t1 t2 t3 gx gy block lds error
 //   tn   nseg F R O batch_major offer_quad num_cus KNOBS                       ->  kind t1 t2 t3 nsplit rps gx gy block lds remap error
 //   pair M H R num_cus KNOBS   (the two h-part problems of a cell)             ->  1 / 0: one paired launch or not
@@ -18,10 +19,14 @@
 //   sfwd H M N T B plane_stride spectral Sp SpE one_wave no_spec stream probe   ->  kind probe nks block grid lds error
 //   sbwd (the same fields)                                                      ->  kind probe nks block grid lds error
 //   shas H M N                                          ->  nks two_wave spec probe stream h_supported m_supported dev_build
+// The persistent decoder: every field of DecCall in its order; a direction that does not run persistently prints `per_step` in
+// place of its launch:
+//   dec  T B N H Dout M L knob_fwd knob_bwd   ->  covered ; fwd: kernel symbol ; grid 1 block lds ; bwd: likewise
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
+#include "dec_launch.h"
 #include "gemm_launch.h"
 #include "spec_launch.h"
 #include "seq_launch.h"
@@ -136,11 +141,27 @@ static bool seq_line(const char* op, char* out) {
     return true;
 }
 
+// one persistent-decoder line; false: not such an op
+static bool dec_line(const char* op, char* out) {
+    if (strcmp(op, "dec")) return false;
+    DecCall c{};
+    if (scanf("%d %d %d %d %d %d %d %d %d", &c.T, &c.B, &c.N, &c.H, &c.Dout, &c.M, &c.L, &c.knob_fwd_per_step, &c.knob_bwd_per_step) != 9) exit(2);
+    const DecPlan p = dec_plan(c);
+    char sym[64];
+    out += sprintf(out, "%d ; fwd: ", p.covered ? 1 : 0);
+    sprintf(sym, "dec_fwd_persist_kernel<64, %d>", p.M);
+    out += p.fwd_persistent ? launch(out, sym, p.grid, 1, p.block, p.lds_fwd) : sprintf(out, "per_step");
+    out += sprintf(out, " ; bwd: ");
+    sprintf(sym, "dec_bwd_persist_kernel<64, %d, %d, %d>", p.M, p.dt, p.cx0);
+    out += p.bwd_persistent ? launch(out, sym, p.grid, 1, p.block, p.lds_bwd) : sprintf(out, "per_step");
+    return true;
+}
+
 int main() {
     char op[8], out[512];
     while (scanf("%7s", op) == 1) {
         int bm, quad;
-        if (spec_line(op, out) || seq_line(op, out)) {
+        if (spec_line(op, out) || seq_line(op, out) || dec_line(op, out)) {
         } else if (!strcmp(op, "nn")) {
             NnCall c{};
             if (scanf("%d %d %d %d %d %d %d %d %d %d", &c.nseg, &c.F, &c.R, &c.nct_total, &c.ldc, &c.O, &bm, &quad, &c.bf3_nct, &c.num_cus) != 10 || !knobs(c.knobs)) return 2;

@@ -6,7 +6,8 @@ instance per hop count (M in {1, 2, 3, 4, 5, 7}); the backward is selected by M,
 transpose: 5 where Dout / 4 is a multiple of 5, else 4) and by CX0 (column tiles of layer 0's c1 / c2 packs: 12 up to 128 outputs, 16
 up to 192, 20 up to 256), within 64 units, 20 nodes, 4 layers, 64 steps and the LDS of a CU.  The suite restates those rules from
 the documented geometry.  Without a GPU: the restatement answers as `ops.decoder_is_persistent` (the emulator build of api.cpp)
-over the whole grid of shapes, its enumeration gives 6 forward and 32 backward instances, the case table names exactly those, the
+over the whole grid of shapes, and so does the launch plan (csrc/dec_launch.h through the plan driver), which names the instances the
+restatement names; its enumeration gives 6 forward and 32 backward instances, the case table names exactly those, the
 shape after each LDS edge is refused, and a share of the table runs on the emulator -- which proves through the event recorder
 that the named instances exist and are what a decoder of those dimensions launches.  With a GPU (`-m gpu`): every case proves
 through the recorder that the kernels it names took `dec_fwd_persist` and `dec_bwd_persist`, once each, with no per-step decoder
@@ -15,11 +16,13 @@ launch beside them; then outputs, dh0 and every parameter gradient against float
 rows at one clip more than the grid (also with a cotangent on three clips only), two rows under dropout."""
 import os
 import re
+import subprocess
 
 import pytest
 import torch
 
 import dec_kernel_suite as dk
+import quad_gemm_suite as qg
 import wide_decoder_suite as wd
 
 
@@ -64,9 +67,36 @@ def test_restated_rules_answer_as_the_library_over_the_whole_grid(emulator):
             assert ops.decoder_is_persistent(d[0], b, *d[1:]) and dk.is_persistent(*d)
 
 
+@pytest.fixture(scope="module")
+def plan_driver(tmp_path_factory):
+    return qg.build_plan_driver(tmp_path_factory.mktemp("plan_driver"))
+
+
+def test_launch_plan_answers_as_the_restated_rules_over_the_whole_grid(plan_driver):
+    """csrc/dec_launch.h through the plan driver (tests/emu/gemm_plan_driver.cpp, `dec` lines): covered where the restatement says so, as
+    the two instances the restatement names, and over the grid exactly the reachable instances"""
+    calls = "".join("dec %d 2 %d %d %d %d %d 0 0\n" % d for d in GRID)
+    out = subprocess.run([plan_driver], input=calls, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(GRID)
+    seen_f, seen_b = set(), set()
+    for (t, n, h, dout, m, layers), line in zip(GRID, out):
+        fields = line.split(" ; ")
+        assert fields[0] == ("1" if dk.is_persistent(t, n, h, dout, m, layers) else "0"), ((t, n, h, dout, m, layers), line)
+        if fields[0] == "0":
+            assert fields[1:] == ["fwd: per_step", "bwd: per_step"], line
+            continue
+        assert len(fields) == 5 and fields[2].split()[:3] == fields[4].split()[:3] == ["2", "1", "256"], line
+        got = {"dec_fwd_persist": fields[1][len("fwd: "):], "dec_bwd_persist": fields[3][len("bwd: "):]}
+        assert got == dk.symbols_of(m, dout), ((m, dout), line)
+        assert (int(fields[2].split()[3]), int(fields[4].split()[3])) == (dk.fwd_lds_bytes(m, layers, dout), dk.bwd_lds_bytes(m, layers, dout)), line
+        seen_f.add(got["dec_fwd_persist"])
+        seen_b.add(got["dec_bwd_persist"])
+    assert (seen_f, seen_b) == dk.reachable_instances()
+
+
 def test_wide_outputs_with_seven_hop_matrices_never_fit_the_lds():
-    """the backward's launch switch has no wide instance at M = 7; the LDS rule alone already refuses every such shape, so no decoder
-    passes the gate and then finds no kernel"""
+    """no wide backward instance is compiled at M = 7 (dec_has_instance, csrc/dec_launch.h, refuses the pair); the LDS rule alone already
+    refuses every such shape, so that rule changes no answer"""
     assert not [d for d in range(132, 257, 4) if dk.fwd_lds_bytes(7, 1, d) <= dk.LDS_BYTES and dk.bwd_lds_bytes(7, 1, d) <= dk.LDS_BYTES]
     assert dk.bwd_lds_bytes(7, 1, 128) == 162944 and dk.fwd_lds_bytes(4, 4, 192) == 162624      # (DESIGN.md 4.4 states the table in bytes)
     assert (dk.fwd_lds_bytes(5, 2, 200), dk.bwd_lds_bytes(5, 2, 200)) == (162112, 152192)
