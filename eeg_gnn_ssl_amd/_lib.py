@@ -102,6 +102,9 @@ _SIGNATURES = {
     # memory) out of the gather, read by the weighted criteria and the curriculum counter
     "eeg_dcrnn_gather_clips_tail": (c_int, [_FP, _FP, c_size_t, _FP, _FP, c_size_t, _FP, _FP, c_int, _FP, _FP, _FP, c_int64, c_int64, _FP, c_int, c_int,
                                             c_int, _FP, _FP, _FP, c_void_p]),
+    # clips cut out of device-resident recordings through a device clip table (csrc/kernels_records.h); clip_w / denom / n_valid NULL: plain
+    "eeg_dcrnn_gather_records": (c_int, [_FP, c_int64, _FP, c_int64, _FP, c_int64, _FP, _FP, c_int, _FP, c_int64, _FP, c_int, c_int, c_int, c_int, c_int,
+                                         c_int64, c_int64, _FP, _FP, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_cls_head_loss_w": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_int, c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                           _FP, _FP, c_void_p]),
     "eeg_dcrnn_bce_logits_w": (c_int, [_FP, _FP, c_int, _FP, _FP, _FP, _FP, c_void_p]),

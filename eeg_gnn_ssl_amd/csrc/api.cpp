@@ -15,6 +15,7 @@
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
 #include "kernels_data.h"
+#include "kernels_records.h"
 #include "kernels_feat.h"
 #include "kernels_gemm.h"
 #include "kernels_gemm_bf.h"
@@ -1179,6 +1180,64 @@ int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_
         return fail("gather_clips_tail: clip_w / denom / n_valid must be aligned to their element size");
     return gather_clips_launch(x_pool, x_out, x_row_bytes, y_pool, y_out, y_row_bytes, label_pool, label_out, label_bytes, len_pool, len_out, perm,
                                n_perm, P, cursor, B, rank, world, clip_w, denom, n_valid, stream);
+}
+
+/* ---- clips cut out of device-resident recordings through a device clip table ------------------------- */
+int eeg_dcrnn_gather_records(const float* signals, int64_t signal_floats, const int64_t* rec_table, int64_t R, const int64_t* clip_table, int64_t P,
+                             const void* label_pool, void* label_out, int label_bytes, const int64_t* perm, int64_t n_perm, int64_t* cursor, int B,
+                             int rank, int world, int N, int window, int64_t x_len, int64_t y_len, float* x_out, float* y_out, int64_t* len_out,
+                             float* clip_w, float* denom, int64_t* n_valid, void* stream) {
+    if (signals == nullptr || rec_table == nullptr || clip_table == nullptr) return fail("gather_records: null signals / rec_table / clip_table");
+    if (x_out == nullptr) return fail("gather_records: null x_out");
+    if (perm == nullptr || cursor == nullptr) return fail("gather_records: null perm / cursor");
+    if ((y_out == nullptr) != (y_len == 0)) return fail("gather_records: y_out and y_len=%lld disagree (no target: NULL, 0)", (long long)y_len);
+    if ((label_pool == nullptr) != (label_out == nullptr) || (label_pool == nullptr) != (label_bytes == 0))
+        return fail("gather_records: label_pool, label_out and label_bytes=%d disagree (no label: NULL, NULL, 0)", label_bytes);
+    if (label_bytes != 0 && label_bytes != 4 && label_bytes != 8) return fail("gather_records: label_bytes=%d unsupported (4: float, 8: int64)", label_bytes);
+    if ((clip_w == nullptr) != (denom == nullptr) || (clip_w == nullptr) != (n_valid == nullptr))
+        return fail("gather_records: clip_w, denom and n_valid come together (the plain form: all three NULL)");
+    if (B < 1 || world < 1 || rank < 0 || rank >= world) return fail("gather_records: B=%d, rank=%d, world=%d unsupported (B >= 1, 0 <= rank < world)", B, rank, world);
+    if (P < 1 || n_perm < 1 || R < 1) return fail("gather_records: P=%lld clips, n_perm=%lld entries, R=%lld recordings (all >= 1)", (long long)P, (long long)n_perm, (long long)R);
+    if ((long long)B * world > (long long)n_perm)
+        return fail("gather_records: B*world=%lld clips per step exceed the %lld entries of perm", (long long)B * world, (long long)n_perm);
+    if (N < 1) return fail("gather_records: N=%d channels (N >= 1)", N);
+    if (window < 4 || window % 4 != 0) return fail("gather_records: window=%d unsupported (a positive multiple of 4: rows of whole 16-byte pieces)", window);
+    // a channel row of a batch tensor: whole steps, inside one buffer descriptor (its byte count is 32 bits wide)
+    constexpr int64_t kMaxRow = (int64_t)1 << 28;
+    if (x_len < window || x_len % window != 0 || x_len > kMaxRow)
+        return fail("gather_records: x_len=%lld unsupported (a positive multiple of window=%d, at most %lld)", (long long)x_len, window, (long long)kMaxRow);
+    if (y_len < 0 || y_len % window != 0 || y_len > kMaxRow)
+        return fail("gather_records: y_len=%lld unsupported (a multiple of window=%d, at most %lld)", (long long)y_len, window, (long long)kMaxRow);
+    if (signal_floats < 4 || signal_floats % 4 != 0 || signal_floats >= ((int64_t)1 << 60))
+        return fail("gather_records: signal_floats=%lld unsupported (a positive multiple of 4: whole 16-byte pieces)", (long long)signal_floats);
+    if ((((uintptr_t)signals | (uintptr_t)x_out | (uintptr_t)y_out) & 15) != 0) return fail("gather_records: signals, x_out and y_out must be 16-byte aligned");
+    if ((((uintptr_t)label_pool | (uintptr_t)label_out) & (uintptr_t)(label_bytes == 8 ? 7 : 3)) != 0 ||
+        (((uintptr_t)rec_table | (uintptr_t)clip_table | (uintptr_t)len_out | (uintptr_t)perm | (uintptr_t)cursor | (uintptr_t)n_valid) & 7) != 0 ||
+        (((uintptr_t)clip_w | (uintptr_t)denom) & 3) != 0)
+        return fail("gather_records: tables / labels / lengths / perm / cursor / clip_w / denom / n_valid must be aligned to their element size");
+    const uintptr_t s0 = (uintptr_t)signals, s1 = s0 + (uintptr_t)signal_floats * 4;
+    const uintptr_t x0 = (uintptr_t)x_out, x1 = x0 + (uintptr_t)B * N * (uintptr_t)x_len * 4;
+    const uintptr_t y0 = (uintptr_t)y_out, y1 = y0 + (uintptr_t)B * N * (uintptr_t)y_len * 4;
+    if ((x0 < s1 && s0 < x1) || (y_out != nullptr && y0 < s1 && s0 < y1)) return fail("gather_records: the batch tensors must not alias the signal buffer");
+    RecordGather g{signals, (long long)signal_floats, reinterpret_cast<const long long*>(rec_table), (long long)R, reinterpret_cast<const long long*>(clip_table),
+                   x_out, y_out, (unsigned)N, (unsigned)window, (unsigned)x_len, (unsigned)y_len, 0u, 0u};
+    g.cx = (unsigned)((x_len / 4 + kAugPerBlock - 1) / kAugPerBlock);
+    g.cy = (unsigned)((y_len / 4 + kAugPerBlock - 1) / kAugPerBlock);
+    const long long blocks = (long long)N * ((long long)g.cx + g.cy);
+    if (blocks > 65535) return fail("gather_records: N=%d rows of %lld + %lld floats exceed one launch", N, (long long)x_len, (long long)y_len);
+    if (clip_w == nullptr) {
+        EEG_LAUNCH_P("gather_records", gather_records_kernel, dim3((unsigned)B, (unsigned)blocks), dim3(kAugThreads), kRecordStageBytes, S_(stream), g, label_pool,
+                     label_out, label_bytes, reinterpret_cast<long long*>(len_out), reinterpret_cast<const long long*>(perm), (long long)n_perm,
+                     (long long)P, reinterpret_cast<const long long*>(cursor), (long long)rank * B);
+    } else {
+        EEG_LAUNCH_P("gather_records", gather_records_tail_kernel, dim3((unsigned)B, (unsigned)blocks), dim3(kAugThreads), kRecordStageBytes, S_(stream), g,
+                     label_pool, label_out, label_bytes, reinterpret_cast<long long*>(len_out), reinterpret_cast<const long long*>(perm),
+                     (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor), (long long)rank * B, (long long)B * world, world,
+                     clip_w, denom, reinterpret_cast<long long*>(n_valid));
+    }
+    if (int rc = check_launch("gather_records")) return rc;
+    EEG_LAUNCH_P("gather_records_cursor", cursor_advance_kernel, dim3(1), dim3(64), 0, S_(stream), reinterpret_cast<long long*>(cursor), (long long)B * world);
+    return check_launch("gather_records_cursor");
 }
 
 /* ---- the evaluation pass: per-clip scores, scores of the pool ------------------------------------ */

@@ -36,6 +36,13 @@ __device__ __forceinline__ long long gather_source(const long long* __restrict__
     return s < 0 ? 0 : (s >= P ? P - 1 : s);
 }
 
+// the label of clip `src` into batch slot b: 4 or 8 bytes (float / int64), copied as bits; 0: no label
+__device__ __forceinline__ void gather_label(const void* __restrict__ label_pool, void* __restrict__ label_out, int label_bytes, long long src,
+                                             unsigned b) {
+    if (label_bytes == 8) static_cast<long long*>(label_out)[b] = static_cast<const long long*>(label_pool)[src];
+    else if (label_bytes == 4) static_cast<unsigned*>(label_out)[b] = static_cast<const unsigned*>(label_pool)[src];
+}
+
 // One launch per step (the body of gather_clips_kernel and gather_clips_tail_kernel): blockIdx.x = clip b of the batch, blockIdx.y = a stretch of kAugPerBlock 16-byte pieces of that clip's row of
 // the first wide tensor (blockIdx.y < w0.chunks) or of the second (the SSL target pool) -- the launch shape of
 // augment_features_kernel / window_stream_kernel: kAugUnroll pieces in flight per thread, consecutive lanes hold consecutive pieces
@@ -54,8 +61,7 @@ __device__ __forceinline__ void gather_clip_rows(const GatherWide& w0, const Gat
     const GatherWide w = second ? w1 : w0;
     const unsigned chunk = second ? blockIdx.y - w0.chunks : blockIdx.y;
     if (blockIdx.y == 0 && threadIdx.x == 0) {
-        if (label_bytes == 8) static_cast<long long*>(label_out)[b] = static_cast<const long long*>(label_pool)[src];
-        else if (label_bytes == 4) static_cast<unsigned*>(label_out)[b] = static_cast<const unsigned*>(label_pool)[src];
+        gather_label(label_pool, label_out, label_bytes, src, b);
         if (len_out != nullptr) len_out[b] = len_pool[src];
     }
     const size_t row = (size_t)w.pieces * 4;                            // floats per clip row
@@ -88,15 +94,11 @@ __global__ __launch_bounds__(kAugThreads) void gather_clips_kernel(GatherWide w0
 // writes the GLOBAL count of the step, n_valid = clamp(n_perm - cursor, 0, step) with step = B * world clips, and the divisor of
 // this rank's criterion, denom = max(n_valid, 1) / world: behind the summed all-reduce and its 1/world, sum_valid g / denom is the
 // mean over the clips that are there.  A full batch gives clip_w = 1 and denom = B exactly.  The sums run in unsigned arithmetic:
-// no cursor overflows them.  Plain stores, in front of cursor_advance_kernel on the stream.
-__global__ __launch_bounds__(kAugThreads) void gather_clips_tail_kernel(GatherWide w0, GatherWide w1, const void* __restrict__ label_pool,
-                                                                        void* __restrict__ label_out, int label_bytes,
-                                                                        const long long* __restrict__ len_pool, long long* __restrict__ len_out,
-                                                                        const long long* __restrict__ perm, long long n_perm, long long P,
-                                                                        const long long* __restrict__ cursor, long long slot0, long long step,
-                                                                        int world, float* __restrict__ clip_w, float* __restrict__ denom,
-                                                                        long long* __restrict__ n_valid) {
-    gather_clip_rows(w0, w1, label_pool, label_out, label_bytes, len_pool, len_out, perm, n_perm, P, cursor, slot0);
+// no cursor overflows them.  Plain stores, in front of cursor_advance_kernel on the stream.  (gather_tail_scalars: the tail of every
+// gather whose blockIdx.x is the batch slot -- this kernel's and gather_records_tail_kernel's.)
+__device__ __forceinline__ void gather_tail_scalars(long long n_perm, const long long* __restrict__ cursor, long long slot0, long long step,
+                                                    int world, float* __restrict__ clip_w, float* __restrict__ denom,
+                                                    long long* __restrict__ n_valid) {
     if (blockIdx.y != 0 || threadIdx.x != 0) return;
     const long long c = cursor[0];
     const unsigned long long pos = (unsigned long long)c + (unsigned long long)slot0 + blockIdx.x;
@@ -106,6 +108,16 @@ __global__ __launch_bounds__(kAugThreads) void gather_clips_tail_kernel(GatherWi
         n_valid[0] = nv;
         denom[0] = (float)(nv > 1 ? nv : 1) / (float)world;
     }
+}
+__global__ __launch_bounds__(kAugThreads) void gather_clips_tail_kernel(GatherWide w0, GatherWide w1, const void* __restrict__ label_pool,
+                                                                        void* __restrict__ label_out, int label_bytes,
+                                                                        const long long* __restrict__ len_pool, long long* __restrict__ len_out,
+                                                                        const long long* __restrict__ perm, long long n_perm, long long P,
+                                                                        const long long* __restrict__ cursor, long long slot0, long long step,
+                                                                        int world, float* __restrict__ clip_w, float* __restrict__ denom,
+                                                                        long long* __restrict__ n_valid) {
+    gather_clip_rows(w0, w1, label_pool, label_out, label_bytes, len_pool, len_out, perm, n_perm, P, cursor, slot0);
+    gather_tail_scalars(n_perm, cursor, slot0, step, world, clip_w, denom, n_valid);
 }
 
 // cursor += step (B * world clips), behind the gather on the stream and in front of the next one: one thread of one wave (the launch

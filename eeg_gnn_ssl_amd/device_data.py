@@ -17,11 +17,20 @@ the gradient is sum_valid g_b / n_valid: the mean over the clips that are there,
 its short batch (on one rank the plain mean; the RMSE of the SSL task is the clip-weighted mean of the ranks' losses, a rank's loss
 being that of its shard as everywhere here).  A rank whose slots all lie behind the end contributes zeros and still takes part in
 the all-reduce.  The DEFAULT, `drop_last=True`, deviates from the reference: the short batch is dropped (other clips every epoch)
-and the step runs the unweighted kernels."""
+and the step runs the unweighted kernels.
+
+Clips cut on the device.  The reference's loaders keep whole resampled recordings (num_channels, num_samples) and cut a clip out
+by index arithmetic at `__getitem__` time.  `RecordingDataset` does the same in HBM: the recordings lie channel-major in one
+signal buffer, a clip is a row (rec, x_start, x_samples, y_start) of an int64 table on the device, and `ops.gather_records` cuts
+the step's batch -- raw signals (B, N, Tx*W), the SSL target (B, N, Ty*W), lengths, labels -- in front of the unchanged raw chain.
+The SSL target is then no pool of its own, a classification clip needs no host padding, and overlapping or strided clips cost a
+table row each.  `clip_table_detection` / `clip_table_ssl` / `clip_table_classification` restate the three loaders' arithmetic.
+Both data sets hand their batch over through one method, `gather`."""
 from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -69,6 +78,37 @@ class DeviceDataset:
     def device(self):
         return self.x.device
 
+    # what the call sites of a step's batch read (TrainStep._epoch_batch, DeviceEvaluator, DeviceSSLEvaluator) -- of this class and of
+    # RecordingDataset alike: the shapes of one clip, whether a gather writes lengths, and the gather itself
+    @property
+    def x_shape(self):
+        return tuple(self.x.shape[1:])
+
+    @property
+    def y_shape(self):
+        return tuple(self.y.shape[1:])
+
+    @property
+    def y_dtype(self):
+        return self.y.dtype
+
+    @property
+    def has_lengths(self):
+        return self.seq_lengths is not None
+
+    def check_step(self, step, who: str):
+        """pools are taken as they are: features, windows or raw signals, whatever the step's chain expects"""
+
+    def gather(self, sampler, x_out, y_out, len_out=None):
+        """the sampler's next batch into the static batch tensors (`ops.gather_clips`; y_out: the labels or the target; len_out:
+        only with a length pool); a drop_last=False sampler also gets its clip_w / denom / n_valid written"""
+        wide = self.y_is_target
+        ops.gather_clips(self.x, x_out, sampler.perm, sampler.cursor, sampler.rank, sampler.world,
+                         y_pool=self.y if wide else None, y_out=y_out if wide else None,
+                         label_pool=None if wide else self.y, label_out=None if wide else y_out,
+                         len_pool=self.seq_lengths if len_out is not None else None, len_out=len_out,
+                         clip_w=sampler.clip_w, denom=sampler.denom, n_valid=sampler.n_valid)     # (None, None, None: drop_last)
+
     def full_lengths(self, count: int, raw_window: Optional[int] = None, who: str = "DeviceDataset"):
         """The lengths of `count` clips of a label pool WITHOUT a length pool: every clip is whole, so the constant int64 (count,) the
         model's last-step gather reads (`encoder.run(lengths=None)` returns no top state) -- T for features / windows (P, T, N, D),
@@ -97,6 +137,196 @@ class DeviceDataset:
         for i in range(0, len(self), batch_size):
             j = min(i + batch_size, len(self))
             yield self.x[i:j], self.y[i:j], None if lens is None else lens[i:j], supports
+
+
+def layout_recordings(recordings, device):
+    """whole recordings [(N, L_r) float32, ...] -> (signals, rec_table) on `device`: one flat float32 buffer, recording r
+    channel-major at rec_table[r] = (offset, stride, samples) (int64 (R, 3)) with offset and stride padded to multiples of 4 floats
+    (every channel row starts on a 16-byte piece) and the padding zero.  One upload per recording, no host copy of the whole set."""
+    if len(recordings) < 1:
+        raise ValueError("RecordingDataset: no recordings")
+    shapes = []
+    for r, rec in enumerate(recordings):
+        t = torch.as_tensor(rec)
+        if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or t.shape[1] < 1 or t.shape[0] != torch.as_tensor(recordings[0]).shape[0]:
+            raise ValueError(f"RecordingDataset: recording {r} must be float32 (N, L_r) with the N of recording 0, got {t.dtype} {tuple(t.shape)}")
+        shapes.append(tuple(t.shape))
+    n = shapes[0][0]
+    table, offset = [], 0
+    for _, samples in shapes:
+        stride = -(-samples // 4) * 4
+        table.append((offset, stride, samples))
+        offset += n * stride
+    signals = torch.zeros(offset, dtype=torch.float32, device=device)
+    for rec, (off, stride, samples) in zip(recordings, table):
+        signals[off:off + n * stride].view(n, stride)[:, :samples].copy_(torch.as_tensor(rec))
+    return signals, torch.tensor(table, dtype=torch.int64, device=device)
+
+
+class RecordingDataset:
+    """Whole recordings in device memory and a table of the P clips to cut out of them (module docstring):
+    recordings: a list of (N, L_r) float32 tensors / arrays, laid out by `layout_recordings` -- or the flat device buffer `signals` of
+        an earlier data set together with rec_table= and num_channels= (load once, build several tables);
+    clip_table: int64 (P, 4) = (rec, x_start, x_samples, y_start), numpy or tensor (`clip_table_detection` / `_ssl` /
+        `_classification`), validated HERE on the host and uploaded;
+    y: the labels (P,) (float32: detection, int64: classification), or None with y_steps > 0 (task ssl: the target is cut, too);
+    window: samples per step (TrainStep(raw_window=window)); x_steps / y_steps: steps of the input clip and of the SSL target.
+    A batch is x (B, N, x_steps*window), the whole steps of a clip's x_samples and zeros behind them, its lengths (B,) int64 -- what
+    TrainStep(padding_val=...) and the length-aware graph read -- and the labels (B,) or the target (B, N, y_steps*window)."""
+
+    has_lengths = True
+
+    def __init__(self, recordings, clip_table, y=None, *, window: int, x_steps: int, y_steps: int = 0, device=None, rec_table=None,
+                 num_channels: Optional[int] = None):
+        self.window, self.x_steps, self.y_steps = int(window), int(x_steps), int(y_steps)
+        if self.window < 4 or self.window % 4 != 0:
+            raise ValueError(f"RecordingDataset: window={window} must be a positive multiple of 4 (rows of whole 16-byte pieces)")
+        if self.x_steps < 1 or self.y_steps < 0:
+            raise ValueError(f"RecordingDataset: x_steps={x_steps} (>= 1), y_steps={y_steps} (>= 0)")
+        if torch.is_tensor(recordings) and recordings.dim() == 1:
+            if rec_table is None or num_channels is None:
+                raise ValueError("RecordingDataset: a ready signal buffer comes with rec_table= (R, 3) and num_channels=")
+            self.signals, self.N = recordings, int(num_channels)
+            self.rec_table = torch.as_tensor(rec_table, dtype=torch.int64).to(self.signals.device).contiguous()
+            if self.signals.dtype != torch.float32 or not self.signals.is_contiguous() or self.signals.numel() < 4 or self.signals.numel() % 4 != 0:
+                raise ValueError(f"RecordingDataset: signals must be a contiguous flat float32 buffer of whole 16-byte pieces, got "
+                                 f"{self.signals.dtype} {tuple(self.signals.shape)}")
+            if device is not None and torch.device(device) != self.signals.device:
+                raise ValueError(f"RecordingDataset: signals is on {self.signals.device}, device={device}")
+        else:
+            if rec_table is not None:
+                raise ValueError("RecordingDataset: rec_table= goes with a ready signal buffer, not with a list of recordings")
+            if device is None:
+                device = torch.device("cuda", torch.cuda.current_device())
+            self.signals, self.rec_table = layout_recordings(list(recordings), device)
+            self.N = int(torch.as_tensor(recordings[0]).shape[0])
+        recs = self.rec_table.cpu().numpy()
+        if recs.ndim != 2 or recs.shape[1] != 3 or recs.shape[0] < 1 or self.N < 1:
+            raise ValueError(f"RecordingDataset: rec_table must be (R, 3) = (offset, stride, samples), got {recs.shape}; num_channels={self.N}")
+        for r, (off, stride, samples) in enumerate(recs.tolist()):
+            if off < 0 or samples < 1 or stride < samples or off + (self.N - 1) * stride + samples > self.signals.numel():
+                raise ValueError(f"RecordingDataset: rec_table[{r}] = (offset={off}, stride={stride}, samples={samples}) with {self.N} channels "
+                                 f"does not lie inside the {self.signals.numel()} floats of signals (stride >= samples >= 1)")
+        table = clip_table.cpu().numpy() if torch.is_tensor(clip_table) else np.asarray(clip_table)
+        if table.ndim != 2 or table.shape[1] != 4 or table.shape[0] < 1 or table.dtype.kind not in "iu":
+            raise ValueError(f"RecordingDataset: clip_table must be an integer (P, 4) = (rec, x_start, x_samples, y_start), got {table.dtype} "
+                             f"{table.shape}")
+        table = table.astype(np.int64)
+        rec, x_start, x_samples, y_start = table.T
+        in_range = (rec >= 0) & (rec < recs.shape[0])
+        samples = recs[np.where(in_range, rec, 0), 2]
+        no_step = (x_start < 0) | (x_start > samples - self.window)          # (no sum of a table entry: none overflows)
+        bad = ~in_range | (x_samples < self.window) | no_step | ((y_start < 0) if self.y_steps > 0 else False)
+        if bad.any():                                                        # the first offending clip, by name
+            p = int(np.argmax(bad))
+            if not in_range[p]:
+                raise ValueError(f"RecordingDataset: clip {p} names recording rec={rec[p]}, there are {recs.shape[0]}")
+            if x_samples[p] < self.window:
+                raise ValueError(f"RecordingDataset: clip {p} has x_samples={x_samples[p]}, less than one step of window={self.window}")
+            if no_step[p]:
+                raise ValueError(f"RecordingDataset: clip {p} starts at x_start={x_start[p]}: no whole step of {self.window} samples lies inside "
+                                 f"recording {rec[p]} ({samples[p]} samples)")
+            raise ValueError(f"RecordingDataset: clip {p} has y_start={y_start[p]} (>= 0)")
+        dev = self.signals.device
+        self.clip_table = torch.from_numpy(table).to(dev)
+        self.y_is_target = self.y_steps > 0
+        if self.y_is_target != (y is None):
+            raise ValueError(f"RecordingDataset: y_steps={self.y_steps} and y={'None' if y is None else 'a label pool'} disagree: labels (P,) "
+                             f"with y_steps=0 (detection, classification), y=None with y_steps > 0 (ssl: the target is cut from the recording)")
+        if y is not None:
+            if not torch.is_tensor(y) or y.device != dev or not y.is_contiguous() or tuple(y.shape) != (table.shape[0],) or \
+                    y.dtype not in (torch.float32, torch.int64):
+                got = f"{y.dtype} {tuple(y.shape)} on {y.device}" if torch.is_tensor(y) else type(y).__name__
+                raise ValueError(f"RecordingDataset: y must be the contiguous labels ({table.shape[0]},) on {dev}, float32 (detection) or int64 "
+                                 f"(classification), got {got}")
+        self.y = y
+
+    def __len__(self):
+        return self.clip_table.shape[0]
+
+    @property
+    def device(self):
+        return self.signals.device
+
+    @property
+    def x_shape(self):
+        return (self.N, self.x_steps * self.window)
+
+    @property
+    def y_shape(self):
+        return (self.N, self.y_steps * self.window) if self.y_is_target else ()
+
+    @property
+    def y_dtype(self):
+        return torch.float32 if self.y_is_target else self.y.dtype
+
+    def check_step(self, step, who: str):
+        """a batch of this data set is RAW signals in steps of `window`: the step must featurise / window them with the same window,
+        and its task must match what the table cuts"""
+        if step.raw_window is None:
+            raise ValueError(f"{who}: a RecordingDataset yields raw signals (B, N, {self.x_steps}*{self.window}); the step has raw_window=None "
+                             f"-- build it as TrainStep(raw_window={self.window}, ...)")
+        if int(step.raw_window) != self.window:
+            raise ValueError(f"{who}: TrainStep(raw_window={step.raw_window}) and RecordingDataset(window={self.window}) disagree: the lengths "
+                             f"the gather writes count steps of {self.window} samples")
+        if step.task == "ssl" and not self.y_is_target:
+            raise ValueError(f"{who}: task='ssl' needs the target cut from the recordings: RecordingDataset(..., y=None, y_steps=Ty), got "
+                             f"y_steps={self.y_steps}")
+        if step.task != "ssl" and self.y_is_target:
+            raise ValueError(f"{who}: task={step.task!r} needs labels: RecordingDataset(..., y=labels, y_steps=0), got y_steps={self.y_steps}")
+
+    def gather(self, sampler, x_out, y_out, len_out=None):
+        """the sampler's next batch, cut out of the recordings into the static batch tensors (`ops.gather_records`)"""
+        wide = self.y_is_target
+        ops.gather_records(self.signals, self.rec_table, self.clip_table, x_out, sampler.perm, sampler.cursor, sampler.rank, sampler.world,
+                           window=self.window, y_out=y_out if wide else None, label_pool=None if wide else self.y,
+                           label_out=None if wide else y_out, len_out=len_out, clip_w=sampler.clip_w, denom=sampler.denom,
+                           n_valid=sampler.n_valid)
+
+    def batches(self, *args, **kwargs):
+        raise NotImplementedError("RecordingDataset.batches is not offered: there are no pre-cut pools to view.  Evaluate on the device with "
+                                  "TrainStep.evaluator(dataset, batch_size) / TrainStep.ssl_evaluator(dataset, batch_size)")
+
+
+# The three loaders' index arithmetic, on the host in numpy: one table row per clip.  freq: the resampled rate (constants.FREQUENCY).
+def _table(rec_ids, x_start, x_samples, y_start):
+    cols = np.broadcast_arrays(np.asarray(rec_ids, dtype=np.int64), np.asarray(x_start, dtype=np.int64),
+                               np.asarray(x_samples, dtype=np.int64), np.asarray(y_start, dtype=np.int64))
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+def clip_table_detection(rec_ids, clip_idx, clip_len_s, freq: int = 200):
+    """data/dataloader_detection.py, computeSliceMatrix: physical_clip_len = int(FREQUENCY * clip_len), start_window = clip_idx *
+    physical_clip_len, end_window = start_window + physical_clip_len -> (rec, start_window, physical_clip_len, 0)"""
+    clip = int(freq * clip_len_s)
+    return _table(rec_ids, np.asarray(clip_idx, dtype=np.int64) * clip, clip, 0)
+
+
+def clip_table_ssl(rec_ids, clip_idx_x, clip_idx_y, input_len_s, freq: int = 200):
+    """data/dataloader_ssl.py:52-58 for both halves, called with clip_len=self.input_len for x AND y (:303-310); the target is the
+    first output_len steps of clip clip_idx_y (:341: `y_feature[:self.output_len]`) -> (rec, clip_idx_x * L, L, clip_idx_y * L) with
+    L = int(FREQUENCY * input_len); the data set's y_steps cuts the target's length"""
+    clip = int(freq * input_len_s)
+    return _table(rec_ids, np.asarray(clip_idx_x, dtype=np.int64) * clip, clip, np.asarray(clip_idx_y, dtype=np.int64) * clip)
+
+
+def clip_table_classification(rec_ids, seizure_times, seizure_idx, clip_len_s, freq: int = 200, offset_s: int = 2):
+    """data/dataloader_classification.py:44-66.  seizure_times[k]: the (start_s, end_s) pairs of ALL seizures of clip k's recording in
+    order (getSeizureTimes), seizure_idx[k] the one the clip shows:
+        pre_seizure_end = int(FREQUENCY * seizure_times[idx - 1][1]) if idx > 0 else 0
+        start_t = max(pre_seizure_end + 1, int(FREQUENCY * (seizure_times[idx][0] - offset)))
+        end_t   = min(start_t + int(FREQUENCY * clip_len), int(FREQUENCY * seizure_times[idx][1]))
+    -> (rec, start_t, end_t - start_t, 0).  The `while` loop of :68-81 (whole 1-s steps) and the zero padding to max_seq_len behind
+    it are the gather's `keep` rule."""
+    rows = []
+    for times, idx in zip(seizure_times, seizure_idx):
+        idx = int(idx)
+        pre_seizure_end = int(freq * times[idx - 1][1]) if idx > 0 else 0
+        start_t = max(pre_seizure_end + 1, int(freq * (times[idx][0] - offset_s)))
+        end_t = min(start_t + int(freq * clip_len_s), int(freq * times[idx][1]))
+        rows.append((start_t, end_t - start_t))
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+    return _table(rec_ids, rows[:, 0], rows[:, 1], 0)
 
 
 class EpochSampler:

@@ -133,11 +133,12 @@ class DeviceEvaluator(_CapturedPass):
         if len(dataset) > ops.EVAL_MAX_CLIPS:
             raise ValueError(f"DeviceEvaluator: the pool holds P={len(dataset)} clips, one pass takes at most {ops.EVAL_MAX_CLIPS} "
                              f"(ops.EVAL_MAX_CLIPS); evaluate it in parts")
+        dataset.check_step(step, "DeviceEvaluator")
         want = torch.float32 if step.task == "detection" else torch.int64
-        if dataset.y_is_target or dataset.y.dtype != want:
-            raise ValueError(f"DeviceEvaluator(task={step.task!r}): y of the dataset must be the labels (P,) as {want}, got {dataset.y.dtype} "
-                             f"{tuple(dataset.y.shape)}")
-        if step.padding_val is not None and dataset.seq_lengths is None:
+        if dataset.y_is_target or dataset.y_dtype != want:
+            raise ValueError(f"DeviceEvaluator(task={step.task!r}): y of the dataset must be the labels (P,) as {want}, got {dataset.y_dtype} "
+                             f"{(len(dataset),) + dataset.y_shape}")
+        if step.padding_val is not None and not dataset.has_lengths:
             raise ValueError("DeviceEvaluator: TrainStep(padding_val=...) evaluates variable-length clips: the dataset needs a seq_lengths "
                              "pool (DeviceDataset(x, y, seq_lengths=...))")
         self.classes = int(step.model.fc.weight.shape[0])
@@ -152,9 +153,9 @@ class DeviceEvaluator(_CapturedPass):
         self.losses = self._scores[p * c:]
         self._ws, self._record = ops.eval_metrics_buffers(p, c, dev)
         self.record = None
-        self._x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=torch.float32, device=dev)
-        self._y = torch.empty((b,), dtype=dataset.y.dtype, device=dev)
-        if dataset.seq_lengths is not None:
+        self._x = torch.empty((b,) + dataset.x_shape, dtype=torch.float32, device=dev)
+        self._y = torch.empty((b,), dtype=dataset.y_dtype, device=dev)
+        if dataset.has_lengths:
             self._lens, self._gather_lens = torch.empty(b, dtype=torch.int64, device=dev), True
         else:
             self._lens, self._gather_lens = dataset.full_lengths(b, step.raw_window, "DeviceEvaluator"), False
@@ -163,9 +164,7 @@ class DeviceEvaluator(_CapturedPass):
     def _body(self):
         """one step of the pass: gather -> data chain without augmentation -> save=False forward -> head (p = 0) -> scores"""
         st, ds, s, m = self.step, self.dataset, self.sampler, self.step.model
-        ops.gather_clips(ds.x, self._x, s.perm, s.cursor, s.rank, s.world, label_pool=ds.y, label_out=self._y,
-                         len_pool=ds.seq_lengths if self._gather_lens else None, len_out=self._lens if self._gather_lens else None,
-                         clip_w=s.clip_w, denom=s.denom, n_valid=s.n_valid)
+        ds.gather(s, self._x, self._y, self._lens if self._gather_lens else None)
         x, _, supports = st._data_chain(self._x, self._y, self._lens, self.supports)
         last = m.encode_last(x, self._lens, supports)
         logits = ops.cls_head(last, m.fc.weight, m.fc.bias, 0.0, None)
@@ -219,8 +218,9 @@ class DeviceSSLEvaluator(_CapturedPass):
                  keep_predictions: bool = False, loss_batch: Optional[int] = None):
         if step.task != "ssl":
             raise ValueError(f"DeviceSSLEvaluator: task={step.task!r} has labels and scores per clip; its evaluation pass is TrainStep.evaluator")
+        dataset.check_step(step, "DeviceSSLEvaluator")
         if not dataset.y_is_target:
-            raise ValueError(f"DeviceSSLEvaluator: y of the dataset is a label pool {tuple(dataset.y.shape)}; the pass needs the TARGET pool, "
+            raise ValueError(f"DeviceSSLEvaluator: y of the dataset is a label pool {(len(dataset),) + dataset.y_shape}; the pass needs the TARGET pool, "
                              f"DeviceDataset(x, y) with y the clips to predict (P, Ty, N, D) or raw (P, N, Ty*raw_window)")
         dev = step.fp.flat.device
         if dataset.device != dev:
@@ -229,18 +229,18 @@ class DeviceSSLEvaluator(_CapturedPass):
         if p > ops.EVAL_MAX_CLIPS:
             raise ValueError(f"DeviceSSLEvaluator: the pool holds P={p} clips, one pass takes at most {ops.EVAL_MAX_CLIPS} "
                              f"(ops.EVAL_MAX_CLIPS); evaluate it in parts")
-        y = dataset.y
+        xs, ys = (p,) + dataset.x_shape, (p,) + dataset.y_shape       # the shapes of the pools, held or cut
         if step.raw_window is not None:
             w = int(step.raw_window)
-            if dataset.x.dim() != 3 or y.dim() != 3 or y.shape[1] != dataset.x.shape[1] or y.shape[2] == 0 or y.shape[2] % w != 0:
+            if len(xs) != 3 or len(ys) != 3 or ys[1] != xs[1] or ys[2] == 0 or ys[2] % w != 0:
                 raise ValueError(f"DeviceSSLEvaluator: TrainStep(raw_window={w}) evaluates RAW pools: x (P, N, T*{w}) and the target "
-                                 f"(P, N, Ty*{w}) -- whole windows of the same nodes -- got x {tuple(dataset.x.shape)}, y {tuple(y.shape)}")
-            steps = y.shape[2] // w
+                                 f"(P, N, Ty*{w}) -- whole windows of the same nodes -- got x {xs}, y {ys}")
+            steps = ys[2] // w
         else:
-            if dataset.x.dim() != 4 or y.dim() != 4:
+            if len(xs) != 4 or len(ys) != 4:
                 raise ValueError(f"DeviceSSLEvaluator: without raw_window the pools hold features / windows, x (P, T, N, D) and the target "
-                                 f"(P, Ty, N, D), got x {tuple(dataset.x.shape)}, y {tuple(y.shape)}; raw signals need TrainStep(raw_window=W)")
-            steps = y.shape[1]
+                                 f"(P, Ty, N, D), got x {xs}, y {ys}; raw signals need TrainStep(raw_window=W)")
+            steps = ys[1]
         if m.output_dim % 4 != 0:
             raise ValueError(f"DeviceSSLEvaluator: the model's output_dim={m.output_dim} is no multiple of 4 (ops.ssl_eval_scores reads "
                              f"16-byte pieces); evaluate with train_step.evaluate_ssl")
@@ -254,15 +254,14 @@ class DeviceSSLEvaluator(_CapturedPass):
             p, dev, (steps, m.num_nodes, m.output_dim) if keep_predictions else None)
         self.clip_abs, self.clip_count = self._scores[0], self._scores[1]
         self.clip_mae, self.record, self.result = None, None, None
-        self._x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=torch.float32, device=dev)
-        self._y = torch.empty((b,) + tuple(y.shape[1:]), dtype=torch.float32, device=dev)
+        self._x = torch.empty((b,) + dataset.x_shape, dtype=torch.float32, device=dev)
+        self._y = torch.empty((b,) + dataset.y_shape, dtype=torch.float32, device=dev)
         self._graph = None
 
     def _body(self):
         """one step of the pass: gather the pair -> pair chain without augmentation -> the model without teacher forcing -> scores"""
         st, ds, s = self.step, self.dataset, self.sampler
-        ops.gather_clips(ds.x, self._x, s.perm, s.cursor, s.rank, s.world, y_pool=ds.y, y_out=self._y, clip_w=s.clip_w, denom=s.denom,
-                         n_valid=s.n_valid)
+        ds.gather(s, self._x, self._y)
         x, y, supports = st._data_chain(self._x, self._y, None, self.supports)
         pred = st.model(x, y, supports).contiguous()                 # (the decoder's output is time-major)
         ops.ssl_eval_scores(pred, y, s.clip_w, s.cursor, self._scores, s.rank, s.world, st.scaler_mean, st.scaler_std, 0.0, self.predictions)

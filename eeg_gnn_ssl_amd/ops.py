@@ -12,7 +12,7 @@ Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
-    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics.
+    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1800,6 +1800,91 @@ _define("gather_clips_tail", "(Tensor x_pool, Tensor(a!) x_out, Tensor? y_pool, 
         "Tensor(h!) n_valid) -> ()", _gather_clips_impl, lambda *a: None)
 
 
+# ---- clips cut out of device-resident recordings (csrc/kernels_records.h) ----------------------------------------------------------
+def _gather_records_impl(signals, rec_table, clip_table, label_pool, label_out, perm, cursor, rank: int, world: int, window: int, x_out,
+                         y_out, len_out, clip_w=None, denom=None, n_valid=None) -> None:
+    """x_out[b, n, :] <- the clip clip_table[src_b] = (rec, x_start, x_samples, y_start) of channel n of recording rec, cut out of
+    `signals` through rec_table[rec] = (offset, stride, samples): whole steps of `window` samples, zeros behind them and outside the
+    recording; y_out the same from y_start; len_out[b] the whole steps; src_b and the cursor as in gather_clips
+    (eeg_dcrnn_gather_records)."""
+    lib = _lib.get_lib()
+    _check(lib, perm, "perm", torch.int64)
+    _check(lib, cursor, "cursor", torch.int64)
+    dev = perm.device
+    if perm.dim() != 1 or perm.numel() < 1 or cursor.numel() != 1 or cursor.device != dev:
+        raise RuntimeError(f"gather_records: perm must be an int64 vector and cursor one int64 on its device, got {tuple(perm.shape)} / "
+                           f"{tuple(cursor.shape)} on {cursor.device}")
+    _check(lib, signals, "signals", torch.float32)
+    _check(lib, rec_table, "rec_table", torch.int64)
+    _check(lib, clip_table, "clip_table", torch.int64)
+    _check(lib, x_out, "x_out", torch.float32)
+    given = [("signals", signals), ("rec_table", rec_table), ("clip_table", clip_table), ("x_out", x_out)]
+    if y_out is not None:
+        _check(lib, y_out, "y_out", torch.float32)
+        given.append(("y_out", y_out))
+    if len_out is not None:
+        _check(lib, len_out, "len_out", torch.int64)
+        given.append(("len_out", len_out))
+    if (label_pool is None) != (label_out is None):
+        raise RuntimeError("gather_records: label_pool and label_out come together (one of them is None)")
+    if label_pool is not None:
+        if label_pool.dtype not in (torch.float32, torch.int64):
+            raise RuntimeError(f"gather_records: label_pool must be torch.float32 or torch.int64, got {label_pool.dtype}")
+        _check(lib, label_pool, "label_pool", label_pool.dtype)
+        _check(lib, label_out, "label_out", label_pool.dtype)
+        given += [("label_pool", label_pool), ("label_out", label_out)]
+    for name, t in given:
+        if t.device != dev:
+            raise RuntimeError(f"gather_records: {name} is on {t.device}, perm on {dev}: one device")
+    if signals.dim() != 1 or signals.numel() < 4 or signals.numel() % 4 != 0:
+        raise RuntimeError(f"gather_records: signals must be a flat float32 buffer of whole 16-byte pieces, got {tuple(signals.shape)}")
+    if rec_table.dim() != 2 or rec_table.shape[0] < 1 or rec_table.shape[1] != 3:
+        raise RuntimeError(f"gather_records: rec_table must be int64 (R, 3) = (offset, stride, samples), got {tuple(rec_table.shape)}")
+    if clip_table.dim() != 2 or clip_table.shape[0] < 1 or clip_table.shape[1] != 4:
+        raise RuntimeError(f"gather_records: clip_table must be int64 (P, 4) = (rec, x_start, x_samples, y_start), got {tuple(clip_table.shape)}")
+    p = clip_table.shape[0]
+    window = int(window)
+    if window < 4 or window % 4 != 0:
+        raise RuntimeError(f"gather_records: window={window} must be a positive multiple of 4 (rows of whole 16-byte pieces)")
+    if x_out.dim() != 3 or x_out.numel() == 0 or x_out.shape[2] % window != 0:
+        raise RuntimeError(f"gather_records: x_out must be (B, N, Tx*window) with window={window}, got {tuple(x_out.shape)}")
+    b, n, x_len = x_out.shape
+    y_len = 0
+    if y_out is not None:
+        if y_out.dim() != 3 or tuple(y_out.shape[:2]) != (b, n) or y_out.shape[2] == 0 or y_out.shape[2] % window != 0:
+            raise RuntimeError(f"gather_records: y_out must be ({b}, {n}, Ty*window) with window={window}, got {tuple(y_out.shape)}")
+        y_len = y_out.shape[2]
+    if label_pool is not None and (tuple(label_pool.shape) != (p,) or tuple(label_out.shape) != (b,)):
+        raise RuntimeError(f"gather_records: label_pool {tuple(label_pool.shape)} / label_out {tuple(label_out.shape)} must be ({p},) / ({b},): "
+                           f"one value per clip of the table and of the batch")
+    if len_out is not None and tuple(len_out.shape) != (b,):
+        raise RuntimeError(f"gather_records: len_out must be int64 ({b},), got {tuple(len_out.shape)}")
+    for name, t in (("x_out", x_out), ("y_out", y_out), ("signals", signals)):
+        if t is not None and t.data_ptr() % 16 != 0:
+            raise RuntimeError(f"gather_records: {name} at address {t.data_ptr():#x} is not 16-byte aligned")
+    if world < 1 or not 0 <= rank < world:
+        raise RuntimeError(f"gather_records: rank={rank} of world={world}")
+    if b * world > perm.numel():
+        raise RuntimeError(f"gather_records: batch_size*world = {b * world} clips per step exceed the {perm.numel()} entries of perm")
+    if clip_w is not None:
+        for t, name, dtype, shape in ((clip_w, "clip_w", torch.float32, (b,)), (denom, "denom", torch.float32, (1,)), (n_valid, "n_valid", torch.int64, (1,))):
+            if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise RuntimeError(f"gather_records: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev} (written on the device), "
+                                   f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    lib.call("eeg_dcrnn_gather_records", _p(signals), signals.numel(), _p(rec_table), rec_table.shape[0], _p(clip_table), int(p), _p(label_pool),
+             _p(label_out), 0 if label_pool is None else label_pool.element_size(), _p(perm), perm.numel(), _p(cursor), int(b), int(rank),
+             int(world), int(n), window, int(x_len), int(y_len), _p(x_out), _p(y_out), _p(len_out), _p(clip_w), _p(denom), _p(n_valid),
+             _stream(perm))
+
+
+_define("gather_records", "(Tensor signals, Tensor rec_table, Tensor clip_table, Tensor? label_pool, Tensor(a!)? label_out, Tensor perm, "
+        "Tensor(b!) cursor, int rank, int world, int window, Tensor(c!) x_out, Tensor(d!)? y_out, Tensor(e!)? len_out) -> ()",
+        _gather_records_impl, lambda *a: None)
+_define("gather_records_tail", "(Tensor signals, Tensor rec_table, Tensor clip_table, Tensor? label_pool, Tensor(a!)? label_out, Tensor perm, "
+        "Tensor(b!) cursor, int rank, int world, int window, Tensor(c!) x_out, Tensor(d!)? y_out, Tensor(e!)? len_out, Tensor(f!) clip_w, "
+        "Tensor(g!) denom, Tensor(h!) n_valid) -> ()", _gather_records_impl, lambda *a: None)
+
+
 # =============================================================================================
 # Python conveniences used by model/, utils.py and train_step.py
 # =============================================================================================
@@ -2292,6 +2377,27 @@ def gather_clips(x_pool, x_out, perm, cursor, rank: int = 0, world: int = 1, y_p
         raise RuntimeError("gather_clips: clip_w, denom and n_valid come together (one of them is None)")
     torch.ops.eeg_dcrnn.gather_clips_tail(x_pool, x_out, y_pool, y_out, label_pool, label_out, len_pool, len_out, perm, cursor, int(rank),
                                           int(world), clip_w, denom, n_valid)
+
+
+def gather_records(signals, rec_table, clip_table, x_out, perm, cursor, rank: int = 0, world: int = 1, *, window: int, y_out=None,
+                   label_pool=None, label_out=None, len_out=None, clip_w=None, denom=None, n_valid=None):
+    """One step's batch CUT out of device-resident recordings (the reference loaders' slicing at __getitem__ time): slot b takes clip
+    src = clamp(perm[(cursor + rank*B + b) mod len(perm)], 0, P-1) of clip_table (P, 4) int64 = (rec, x_start, x_samples, y_start).
+    signals: flat float32 buffer; rec_table (R, 3) int64 = (offset, stride, samples), sample s of channel n of recording r at
+    offset + n*stride + s.  x_out (B, N, Tx*window): the whole steps of the x_samples from x_start on, exactly 0.0 behind them and
+    outside the recording; y_out (B, N, Ty*window), optional: the same from y_start over its whole length; len_out (B,) int64,
+    optional: the whole steps kept; label_out (B,) <- label_pool (P,).  `cursor` advances by B*world on the stream.  Two launches, no
+    allocation, capturable.  clip_w / denom / n_valid: as in `gather_clips`.  No table entry makes the kernel read outside
+    `signals` or write outside the batch tensors (`device_data.RecordingDataset` validates its table on the host all the same)."""
+    tail = [t is not None for t in (clip_w, denom, n_valid)]
+    if not any(tail):
+        torch.ops.eeg_dcrnn.gather_records(signals, rec_table, clip_table, label_pool, label_out, perm, cursor, int(rank), int(world),
+                                           int(window), x_out, y_out, len_out)
+        return
+    if not all(tail):
+        raise RuntimeError("gather_records: clip_w, denom and n_valid come together (one of them is None)")
+    torch.ops.eeg_dcrnn.gather_records_tail(signals, rec_table, clip_table, label_pool, label_out, perm, cursor, int(rank), int(world),
+                                            int(window), x_out, y_out, len_out, clip_w, denom, n_valid)
 
 
 def eval_scores(logits, label_pool, clip_w, cursor, probs, losses, rank: int = 0, world: int = 1):

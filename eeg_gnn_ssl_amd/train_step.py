@@ -505,19 +505,20 @@ class TrainStep:
             raise ValueError(f"TrainStep: dataset on {dataset.device}, sampler on {sampler.device}, model on {dev}: one device")
         if len(dataset) != sampler.P:
             raise ValueError(f"TrainStep: the dataset holds {len(dataset)} clips, the sampler permutes P={sampler.P}")
-        if self.padding_val is not None and dataset.seq_lengths is None:
+        dataset.check_step(self, "TrainStep")
+        if self.padding_val is not None and not dataset.has_lengths:
             raise ValueError("TrainStep(padding_val=...): variable-length clips need the dataset's seq_lengths pool (DeviceDataset(x, y, "
                              "seq_lengths=...)); it has none")
         if (self.task == "ssl") != dataset.y_is_target:
-            raise ValueError(f"TrainStep(task={self.task!r}): y of the dataset is {tuple(dataset.y.shape)} -- labels (P,) for the supervised "
+            raise ValueError(f"TrainStep(task={self.task!r}): y of the dataset is {(len(dataset),) + dataset.y_shape} -- labels (P,) for the supervised "
                              f"tasks, the target pool (P, ...) for ssl")
         self.attach_sampler(sampler)
         key = (id(dataset), sampler.batch_size)
         if key not in self._epoch_batches:
             b = sampler.batch_size
-            x = torch.empty((b,) + tuple(dataset.x.shape[1:]), dtype=dataset.x.dtype, device=dev)
-            y = torch.empty((b,) + tuple(dataset.y.shape[1:]), dtype=dataset.y.dtype, device=dev)
-            if dataset.seq_lengths is not None:
+            x = torch.empty((b,) + dataset.x_shape, dtype=torch.float32, device=dev)
+            y = torch.empty((b,) + dataset.y_shape, dtype=dataset.y_dtype, device=dev)
+            if dataset.has_lengths:
                 lens, gathered = torch.empty(b, dtype=torch.int64, device=dev), True
             else:                         # whole clips: the constant lengths the model's last-step gather reads (ssl: None); a raw
                 lens, gathered = dataset.full_lengths(b, self.raw_window, "TrainStep(raw_window=...)"), False      # pool needs raw_window
@@ -526,12 +527,7 @@ class TrainStep:
 
     def _gather_batch(self, dataset, sampler, batch):
         x, y, lens, gathered = batch
-        wide = dataset.y_is_target
-        ops.gather_clips(dataset.x, x, sampler.perm, sampler.cursor, sampler.rank, sampler.world,
-                         y_pool=dataset.y if wide else None, y_out=y if wide else None,
-                         label_pool=None if wide else dataset.y, label_out=None if wide else y,
-                         len_pool=dataset.seq_lengths if gathered else None, len_out=lens if gathered else None,
-                         clip_w=sampler.clip_w, denom=sampler.denom, n_valid=sampler.n_valid)     # (None, None, None: drop_last)
+        dataset.gather(sampler, x, y, lens if gathered else None)
 
     def step_from(self, dataset, sampler, supports=None):
         """One eager step on the sampler's next batch of the dataset: gather into the batch tensors kept for it, then `step`.

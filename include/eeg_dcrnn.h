@@ -387,6 +387,32 @@ int eeg_dcrnn_gather_clips_tail(const float* x_pool, float* x_out, size_t x_row_
                                 const int64_t* perm, int64_t n_perm, int64_t P, int64_t* cursor, int B, int rank, int world, float* clip_w,
                                 float* denom, int64_t* n_valid, void* stream);
 
+/* eeg_dcrnn_gather_records: the sibling of eeg_dcrnn_gather_clips / _tail for clips that are CUT out of whole recordings on the
+ * device (the index arithmetic of the reference's loaders at __getitem__ time: `signal_array[:, start:end]`, the SSL target as
+ * the head of another clip, the seizure window with its whole 1-s steps and zero padding).  All pointers DEVICE memory.
+ *   signals     float32[signal_floats], 16-byte aligned, signal_floats % 4 == 0.  Recording r is channel-major: sample s of channel n
+ *               lies at rec_table[r].offset + n * rec_table[r].stride + s.
+ *   rec_table   int64[R][3] = (offset, stride, samples), stride >= samples
+ *   clip_table  int64[P][4] = (rec, x_start, x_samples, y_start)
+ *   label_pool  (P,) elements of label_bytes = 4 / 8 bytes, copied as bits (NULL, NULL, 0: none), as in eeg_dcrnn_gather_clips
+ *   perm, n_perm, P, cursor, B, rank, world: the slot arithmetic of eeg_dcrnn_gather_clips,
+ *               src = clamp(perm[(cursor[0] + rank*B + b) mod n_perm], 0, P-1); the cursor advances by B*world behind the launch.
+ *   N channels, window (% 4 == 0), x_len = Tx * window, y_len = Ty * window floats per channel row (y_len = 0, y_out = NULL: no target)
+ * Per batch slot b, with r = clamp(rec, 0, R-1) and keep = (clamp(x_samples, 0, x_len) / window) * window (whole steps only):
+ *   x_out[b, n, i] (float[B][N][x_len]) = the sample x_start + i of channel n of recording r if i < keep and 0 <= x_start + i < samples,
+ *               else exactly 0.0f;  y_out[b, n, i] (float[B][N][y_len]) the same from y_start over all of y_len
+ *   len_out[b]  (int64[B]; NULL: not written) = keep / window
+ *   label_out[b] = label_pool[src]
+ *   clip_w, denom, n_valid: written exactly as by eeg_dcrnn_gather_clips_tail; all three NULL: the plain form.
+ * Bounds are part of the contract: whatever the two tables, perm and the cursor hold, nothing is read outside
+ * [signals, signals + signal_floats) -- a sample whose address falls outside it reads as 0.0f -- and nothing is written outside the
+ * B output rows, every element of which is written by every launch.  A start with (offset + n*stride + start) % 4 == 0 copies
+ * 16-byte pieces; any other start is read as dwords.  The outputs must not alias the signal buffer. */
+int eeg_dcrnn_gather_records(const float* signals, int64_t signal_floats, const int64_t* rec_table, int64_t R, const int64_t* clip_table, int64_t P,
+                             const void* label_pool, void* label_out, int label_bytes, const int64_t* perm, int64_t n_perm, int64_t* cursor, int B,
+                             int rank, int world, int N, int window, int64_t x_len, int64_t y_len, float* x_out, float* y_out, int64_t* len_out,
+                             float* clip_w, float* denom, int64_t* n_valid, void* stream);
+
 /* The evaluation pass (train.py:332-431) on the device.
  *
  * eeg_dcrnn_eval_scores: one launch behind the head of every step of a pass over a pool of P clips in order (perm = identity,
