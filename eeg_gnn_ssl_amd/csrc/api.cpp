@@ -12,6 +12,7 @@
 #include "../../include/eeg_dcrnn_dev.h"
 #include "../../include/eeg_dcrnn_prof.h"
 #include "kernels_decoder.h"
+#include "diffuse_launch.h"
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
 #include "kernels_data.h"
@@ -19,6 +20,7 @@
 #include "kernels_feat.h"
 #include "kernels_gemm.h"
 #include "kernels_gemm_bf.h"
+#include "corr_launch.h"
 #include "kernels_graph.h"
 #include "kernels_head.h"
 #include "kernels_pack.h"
@@ -204,92 +206,79 @@ int gemm_tn(const TnPlan& p, const TnCall& c, const SegPtrs& segs, const float* 
     return run_tn<6>(p, c, segs, a, st, tag);
 }
 
-// the streaming kernel applies (and with it the batch-major input option of eeg_dcrnn_layer_fwd)
-bool diffuse_streams(int p_batched, int S, int B, int N, int F) { return N == 19 && F / 4 <= 128 && S / (p_batched ? B : 1) >= 4; }
-
+// ---- hop diffusion ----------------------------------------------------------------------------
+// diffuse_launch.h plans a call (kernel, grid, block, LDS, column chunk); it is executed here, one launch line per kernel signature.
+DiffuseCall diffuse_call(bool adjoint, int p_batched, int S, int B, int N, int F, int M, int x_bt = 0, bool wants_copy = false) {
+    return DiffuseCall{p_batched, S, B, N, F, M, adjoint, x_bt, wants_copy, g_tune[EEG_TUNE_DIFFUSE_FWD_WGS], g_tune[EEG_TUNE_DIFFUSE_ADJ_WGS],
+                       g_tune[EEG_TUNE_DIFFUSE_ADJ_LDS], g_tune[EEG_TUNE_DIFFUSE_ADJ_PLANES]};
+}
 // x_bt: X is batch-major (B, S/B, N, F) and xcopy gets its time-major copy (streaming kernel only)
 int diffuse_fwd(const float* X, const float* P, int p_batched, int S, int B, int N, int F, int M, float* planes,
                 hipStream_t st, size_t plane_stride = 0, int x_bt = 0, float* xcopy = nullptr) {
     if (plane_stride == 0) plane_stride = (size_t)S * N * F;
-    if (M == 1 && xcopy == nullptr) return 0;         // max_diffusion_step = 0: no planes (a requested copy still runs below)
-    if (x_bt && !diffuse_streams(p_batched, S, B, N, F)) return fail("diffuse_fwd: batch-major input needs the streaming kernel");
-    // the EEG montage: streaming kernel (no LDS); launches with < 4 samples per graph (decoder steps) leave most of its
-    // lanes idle and are faster through the LDS/MFMA kernel below
-    if (diffuse_streams(p_batched, S, B, N, F)) {
-        const int F4 = F / 4, sB = p_batched ? B : 1, T = S / sB;
-        int threads = 256;                        // few samples per graph: narrower workgroups
-        while (threads > 64 && (threads / 2) / F4 >= T && (threads / 2) >= F4) threads /= 2;
-        const int SPW = threads / F4;
-        int ny = ceil_div(T, SPW);
-        // ~4 workgroups per CU in total, each walking >= 2 passes of consecutive samples: measured on MI355X (cfg2, F=100,
-        // profiles/r02_b_diffuse_sweep.txt) 64 us against 75 us with 6 single-pass workgroups per CU and 68 / 85 us with 2 / 1
-        // (fewer, longer sequential streams suit the DRAM pages better than more parallelism); prefetching the next
-        // sample's rows ahead of the stores was slower (71 us).  dev knob 5 overrides the target.
-        const int want = ceil_div(g_tune[EEG_TUNE_DIFFUSE_FWD_WGS] > 0 ? g_tune[EEG_TUNE_DIFFUSE_FWD_WGS] : 1024, sB);
-        if (ny > want) ny = want;
-        if (ny < 1) ny = 1;
-        EEG_LAUNCH_P("diffuse_fwd", diffuse_fwd_stream_kernel<19>, dim3(sB, ny), dim3(threads), 0, st, X, P, p_batched, S, B, F, M, planes, plane_stride, x_bt, xcopy);
-        return check_launch("diffuse_fwd");
+    const DiffusePlan p = diffuse_plan(diffuse_call(false, p_batched, S, B, N, F, M, x_bt, xcopy != nullptr));
+    if (p.error == kDiffuseBatchMajorNeedsStream) return fail("diffuse_fwd: batch-major input needs the streaming kernel");
+    if (p.error == kDiffuseNoFit) return fail("diffuse_fwd: N=%d M=%d does not fit the LDS tile", N, M);
+    switch (p.kind) {
+        case DiffuseKind::None: return 0;
+        case DiffuseKind::StreamFwd:
+            EEG_LAUNCH_P("diffuse_fwd", diffuse_fwd_stream_kernel<19>, dim3(p.gx, p.gy), dim3(p.block), 0, st, X, P, p_batched, S, B, F, M, planes, plane_stride, x_bt, xcopy);
+            return check_launch("diffuse_fwd");
+        default:
+            EEG_SET_MAX_LDS(diffuse_fwd_kernel, p.lds);
+            for (int c0 = 0; c0 < F; c0 += p.fc) {
+                EEG_LAUNCH_P("diffuse_fwd", diffuse_fwd_kernel, dim3(p.gx, p.gy), dim3(p.block), p.lds, st, X, P, p_batched, S, B, N, F, M, planes, plane_stride,
+                             c0, F - c0 < p.fc ? F - c0 : p.fc);
+                if (check_launch("diffuse_fwd")) return 1;
+            }
+            return 0;
     }
-    // LDS kernel: rows wider than one tile (LDS budget / prefetch registers) go in column chunks, one launch each
-    const int NR = round_up(N, 4);
-    int Fc = F;
-    auto lds_of = [&](int fc) { return ((size_t)(M - 1) * kPFloats + (size_t)NR * lds_stride(M * round_up(fc, 16))) * sizeof(float); };
-    while (Fc > 16 && (lds_of(Fc) > 96 * 1024 || N * (Fc / 4) > 256 * kDiffPrefetch)) Fc = round_up(ceil_div(Fc, 2), 16);
-    const size_t lds = lds_of(Fc);
-    if (lds > kMaxLdsBytes || N * (Fc / 4) > 256 * kDiffPrefetch) return fail("diffuse_fwd: N=%d M=%d does not fit the LDS tile", N, M);
-    EEG_SET_MAX_LDS(diffuse_fwd_kernel, lds);
-    dim3 grid;
-    if (p_batched) {
-        const int T = S / B;
-        int tg = ceil_div(2048, B);
-        if (tg > T) tg = T;
-        grid = dim3(B, tg < 1 ? 1 : tg);
-    } else {
-        grid = dim3(S < 2048 ? S : 2048, 1);
-    }
-    for (int c0 = 0; c0 < F; c0 += Fc) {
-        EEG_LAUNCH_P("diffuse_fwd", diffuse_fwd_kernel, grid, dim3(256), lds, st, X, P, p_batched, S, B, N, F, M, planes, plane_stride,
-                     c0, F - c0 < Fc ? F - c0 : Fc);
-        if (check_launch("diffuse_fwd")) return 1;
-    }
-    return 0;
 }
 int diffuse_adj(const float* Z, const float* P, int p_batched, int S, int B, int N, int F, int M, float* dX,
                 hipStream_t st, const float* add = nullptr) {
-    if (N == 19 && F / 4 <= 128 && g_tune[EEG_TUNE_DIFFUSE_ADJ_LDS] == 0 && (double)S * N * M * F < 1.7e10 && S / (p_batched ? B : 1) >= 4) {   // the EEG montage: streaming kernel (no LDS); 32-bit float4 offsets
-        const int F4 = F / 4, sB = p_batched ? B : 1, T = S / sB;
-        int threads = 256;
-        while (threads > 64 && (threads / 2) / F4 >= T && (threads / 2) >= F4) threads /= 2;
-        const int SPW = threads / F4;
-        int ny = ceil_div(T, SPW);
-        const int want = ceil_div(g_tune[EEG_TUNE_DIFFUSE_ADJ_WGS] > 0 ? g_tune[EEG_TUNE_DIFFUSE_ADJ_WGS] : 4096, sB);   // dev knob 6 (512 .. 4096 measured alike)
-        if (ny > want) ny = want;
-        if (ny < 1) ny = 1;
-        // round 5: Z walked in storage order (all hop slots of a node row together) where the hop count has an instantiation
-        if (g_tune[EEG_TUNE_DIFFUSE_ADJ_PLANES] == 0 && M == 3) {
-            EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 3>), dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, add, dX);
-        } else if (g_tune[EEG_TUNE_DIFFUSE_ADJ_PLANES] == 0 && M == 5) {
-            EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 5>), dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, add, dX);
-        } else {
-            EEG_LAUNCH_P("diffuse_adj", diffuse_adj_stream_kernel<19>, dim3(sB, ny), dim3(threads), 0, st, Z, P, p_batched, S, B, F, M, add, dX);
-        }
-        return check_launch("diffuse_adj");
+    const DiffusePlan p = diffuse_plan(diffuse_call(true, p_batched, S, B, N, F, M));
+    if (p.error == kDiffuseNoFit) return fail("diffuse_adj: N=%d M=%d does not fit the LDS tile", N, M);
+    const dim3 grid(p.gx, p.gy), block(p.block);
+    switch (p.kind) {
+        case DiffuseKind::RowsAdj:
+            if (p.mm == 3) EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 3>), grid, block, 0, st, Z, P, p_batched, S, B, F, add, dX);
+            else EEG_LAUNCH_P("diffuse_adj", (diffuse_adj_rows_kernel<19, 5>), grid, block, 0, st, Z, P, p_batched, S, B, F, add, dX);
+            return check_launch("diffuse_adj");
+        case DiffuseKind::StreamAdj:
+            EEG_LAUNCH_P("diffuse_adj", diffuse_adj_stream_kernel<19>, grid, block, 0, st, Z, P, p_batched, S, B, F, M, add, dX);
+            return check_launch("diffuse_adj");
+        default:
+            EEG_SET_MAX_LDS(diffuse_adj_kernel, p.lds);
+            for (int c0 = 0; c0 < F; c0 += p.fc) {
+                EEG_LAUNCH_P("diffuse_adj", diffuse_adj_kernel, dim3(p.gx), block, p.lds, st, Z, P, p_batched, S, B, N, F, M, add, dX,
+                             c0, F - c0 < p.fc ? F - c0 : p.fc);
+                if (check_launch("diffuse_adj")) return 1;
+            }
+            return 0;
     }
-    const int NR = round_up(N, 4);
-    int Fc = F;
-    auto lds_of = [&](int fc) { return ((size_t)(M - 1) * kPFloats + (size_t)NR * lds_stride(M * round_up(fc, 16))) * sizeof(float); };
-    while (Fc > 16 && lds_of(Fc) > 96 * 1024) Fc = round_up(ceil_div(Fc, 2), 16);
-    const size_t lds = lds_of(Fc);
-    if (lds > kMaxLdsBytes) return fail("diffuse_adj: N=%d M=%d does not fit the LDS tile", N, M);
-    EEG_SET_MAX_LDS(diffuse_adj_kernel, lds);
-    const int grid = S < 2048 ? S : 2048;
-    for (int c0 = 0; c0 < F; c0 += Fc) {
-        EEG_LAUNCH_P("diffuse_adj", diffuse_adj_kernel, dim3(grid), dim3(256), lds, st, Z, P, p_batched, S, B, N, F, M, add, dX,
-                     c0, F - c0 < Fc ? F - c0 : Fc);
-        if (check_launch("diffuse_adj")) return 1;
-    }
-    return 0;
+}
+
+// ---- per-clip correlation Gram ---------------------------------------------------------------
+// corr_launch.h plans a call; these execute it: the template switch and one launch line per kernel signature
+template <int NQ, bool REM4, bool LEN>
+void run_corr_gram(const CorrGramPlan& p, const float* X, int T, int N, int D, float* ws, const long long* len, hipStream_t st) {
+    EEG_SET_MAX_LDS((corr_gram_kernel<NQ, REM4, LEN>), p.lds);
+    EEG_LAUNCH_P(LEN ? "corr_gram_len" : "corr_gram", (corr_gram_kernel<NQ, REM4, LEN>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, X, T, N, D, ws, p.step_floats, len);
+}
+template <int NQ>
+void run_corr_gram(const CorrGramPlan& p, const float* X, int T, int N, int D, float* ws, const long long* len, hipStream_t st) {
+    if (p.len) return p.rem4 ? run_corr_gram<NQ, true, true>(p, X, T, N, D, ws, len, st) : run_corr_gram<NQ, false, true>(p, X, T, N, D, ws, len, st);
+    return p.rem4 ? run_corr_gram<NQ, true, false>(p, X, T, N, D, ws, len, st) : run_corr_gram<NQ, false, false>(p, X, T, N, D, ws, len, st);
+}
+int corr_finish(const float* ws, int B, int ns, int N, int top_k, float* adj, float* S1, float* S2, hipStream_t st) {
+    EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), corr_finish_lds_bytes(), st, ws, ns, N, top_k, adj, S1, S2);
+    return check_launch("corr_finish");
+}
+template <bool REM4, bool LEN>
+void run_corr_gram_rows(const CorrRowsPlan& p, const float* X, int N, int P, int Q, float* ws, const long long* len, hipStream_t st) {
+    EEG_SET_MAX_LDS((corr_gram_rows_kernel<REM4, LEN>), p.lds);
+    EEG_LAUNCH_P(LEN ? "corr_gram_rows_len" : "corr_gram_rows", (corr_gram_rows_kernel<REM4, LEN>), dim3(p.gx, p.gy), dim3(p.block), p.lds, st, X, N, P, Q, p.ps,
+                 (unsigned)p.clip_floats, ws, p.tile_floats, len, p.unit);
 }
 
 // The recurrent launches: the caller makes the plan (seq_launch.h) from one of these calls, lays its operands out by plan.kind,
@@ -766,7 +755,8 @@ int eeg_dcrnn_spectral_ok(const eeg_layer_dims* d, int need_dx) {
 }
 
 int eeg_dcrnn_batch_major_ok(const eeg_layer_dims* d) {
-    if (!diffuse_streams(d->p_batched, d->T * d->B, d->B, d->N, d->Fin)) return 0;
+    // the plan's own predicate, not a whole plan: a size query takes degenerate dims (Fin = 0) and plans no launch
+    if (!diffuse_streams(diffuse_call(false, d->p_batched, d->T * d->B, d->B, d->N, d->Fin, d->M))) return 0;
     // 2: the GEMMs read the batch-major input through a row map (d->x_batch_major = 1, no copy); 1: only with the
     // time-major copy Xtm.  The rule is "the LDS-DMA kernel applies to both x-part GEMMs", NOT "both x-part plans succeed with a
     // row map": the quad kernels read a row map too, also where the DMA kernels do not apply, and Python keeps other tensors for
@@ -1342,12 +1332,6 @@ int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, doubl
 }
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */
-static int corr_nsplit(int B, int T) {
-    int ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);         // dev knob 7: target number of workgroups
-    const int cap = ceil_div(T, 4);
-    if (ns > cap) ns = cap;
-    return ns < 1 ? 1 : ns;
-}
 int eeg_dcrnn_augment_draw(const uint64_t* rng_used, int B, int N, const int32_t* swap_perm, int32_t* flags, int32_t* perm,
                            float* log_scale, const float* S_plain, const float* S_reflected, int n_supports, float* S_out, void* stream) {
     if (rng_used == nullptr || swap_perm == nullptr || flags == nullptr || perm == nullptr || log_scale == nullptr)
@@ -1361,45 +1345,31 @@ int eeg_dcrnn_augment_draw(const uint64_t* rng_used, int B, int N, const int32_t
     return check_launch("augment_draw");
 }
 
-size_t eeg_dcrnn_corr_graph_ws_floats(int B, int T) { return (B >= 1 && T >= 1) ? (size_t)B * corr_nsplit(B, T) * kGramFloats : 0; }
+// corr_launch.h plans a call (instance, grid, LDS, workspace, refusals); the entry points size the workspace and launch by the same plan
+size_t eeg_dcrnn_corr_graph_ws_floats(int B, int T) { return corr_gram_plan(B, T, 1, 4, false, g_tune[EEG_TUNE_GRAM_WGS]).ws_floats; }
 static int corr_graph(const float* X, int B, int T, int N, int D, int top_k, const int64_t* lengths, float* adj, float* S1, float* S2,
                       float* ws, void* stream) {
     const long long* len = reinterpret_cast<const long long*>(lengths);
-    if (N < 1 || N > kMaxNodes) return fail("corr_graph: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
-    if (D < 4 || D % 4 != 0) return fail("corr_graph: feature dim=%d unsupported (positive multiple of 4)", D);
-    if (B < 1 || T < 1) return fail("corr_graph: empty batch/clip (B=%d, T=%d)", B, T);
+    const CorrGramPlan p = corr_gram_plan(B, T, N, D, len != nullptr, g_tune[EEG_TUNE_GRAM_WGS]);
+    if (p.error == kCorrBadNodes) return fail("corr_graph: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
+    if (p.error == kCorrBadDim) return fail("corr_graph: feature dim=%d unsupported (positive multiple of 4)", D);
+    if (p.error == kCorrEmpty) return fail("corr_graph: empty batch/clip (B=%d, T=%d)", B, T);
     if (top_k < 0 || top_k >= N) return fail("corr_graph: top_k=%d unsupported (0..%d)", top_k, N - 1);
+    if (p.error == kCorrStaging) return fail("corr_graph: N*D=%d too large for the per-wave staging buffers", N * D);
+    if (p.error == kCorrNoInstance) return fail("corr_graph: feature dim=%d unsupported (<= 128)", D);
     hipStream_t st = S_(stream);
-    const int ns = corr_nsplit(B, T);
-    const int step_floats = round_up(N * D, 256);          // one time step, in whole 1-KB wave-DMAs
-    const size_t lds = 4 * (size_t)(step_floats > kGramFloats ? step_floats : kGramFloats) * sizeof(float);
-    if (lds > 64 * 1024) return fail("corr_graph: N*D=%d too large for the per-wave staging buffers", N * D);
-    switch (ceil_div(D, 16)) {
-#define EEG_GRAM_LEN(NQ, REM4)                                                                                                \
-    do {                                                                                                                      \
-        EEG_SET_MAX_LDS((corr_gram_kernel<NQ, REM4, true>), lds);                                                             \
-        EEG_LAUNCH_P("corr_gram_len", (corr_gram_kernel<NQ, REM4, true>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len); \
-    } while (0)
-#define EEG_GRAM(NQ)                                                                                                          \
-    case NQ:                                                                                                                  \
-        if (len != nullptr) {                                                                                                 \
-            if (N <= 20) EEG_GRAM_LEN(NQ, true); else EEG_GRAM_LEN(NQ, false);                                                \
-        } else if (N <= 20) {                                                                                                        \
-            EEG_SET_MAX_LDS((corr_gram_kernel<NQ, true>), lds);                                                               \
-            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, true>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len);  \
-        } else {                                                                                                              \
-            EEG_SET_MAX_LDS((corr_gram_kernel<NQ, false>), lds);                                                              \
-            EEG_LAUNCH_P("corr_gram", (corr_gram_kernel<NQ, false>), dim3(B, ns), dim3(256), lds, st, X, T, N, D, ws, step_floats, len); \
-        }                                                                                                                     \
-        break;
-        EEG_GRAM(1) EEG_GRAM(2) EEG_GRAM(3) EEG_GRAM(4) EEG_GRAM(5) EEG_GRAM(6) EEG_GRAM(7) EEG_GRAM(8)
-#undef EEG_GRAM
-#undef EEG_GRAM_LEN
-        default: return fail("corr_graph: feature dim=%d unsupported (<= 128)", D);
+    switch (p.nq) {
+        case 1: run_corr_gram<1>(p, X, T, N, D, ws, len, st); break;
+        case 2: run_corr_gram<2>(p, X, T, N, D, ws, len, st); break;
+        case 3: run_corr_gram<3>(p, X, T, N, D, ws, len, st); break;
+        case 4: run_corr_gram<4>(p, X, T, N, D, ws, len, st); break;
+        case 5: run_corr_gram<5>(p, X, T, N, D, ws, len, st); break;
+        case 6: run_corr_gram<6>(p, X, T, N, D, ws, len, st); break;
+        case 7: run_corr_gram<7>(p, X, T, N, D, ws, len, st); break;
+        default: run_corr_gram<8>(p, X, T, N, D, ws, len, st); break;
     }
     if (check_launch("corr_gram")) return 1;
-    EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
-    return check_launch("corr_finish");
+    return corr_finish(ws, B, p.ns, N, top_k, adj, S1, S2, st);
 }
 int eeg_dcrnn_corr_graph(const float* X, int B, int T, int N, int D, int top_k, float* adj, float* S1, float* S2,
                          float* ws, void* stream) {
@@ -1412,64 +1382,28 @@ int eeg_dcrnn_corr_graph_len(const float* X, int B, int T, int N, int D, int top
     return corr_graph(X, B, T, N, D, top_k, lengths, adj, S1, S2, ws, stream);
 }
 
-// chunks of a clip's channel rows (P pieces of Q floats), and the workgroups per clip that share them
-static int corr_rows_nsplit(int B, int P, int Q) {
-    const long long chunks = (long long)P * ceil_div(Q, kRowChunk);
-    long long ns = ceil_div(g_tune[EEG_TUNE_GRAM_WGS] > 0 ? g_tune[EEG_TUNE_GRAM_WGS] : 1024, B);   // dev knob 7, as corr_nsplit
-    const long long cap = (chunks + 3) / 4;
-    if (ns > cap) ns = cap;
-    return ns < 1 ? 1 : (int)(ns > 65535 ? 65535 : ns);
-}
-size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q) {
-    return (B >= 1 && P >= 1 && Q >= 1) ? (size_t)B * corr_rows_nsplit(B, P, Q) * kGramFloats : 0;
-}
+size_t eeg_dcrnn_corr_graph_rows_ws_floats(int B, int P, int Q) { return corr_rows_plan(B, 1, P, Q, 0, false, 0, g_tune[EEG_TUNE_GRAM_WGS]).ws_floats; }
 // lengths != nullptr: `steps` = the steps of a full clip (raw rows: Q = steps * samples per step; window tensors: steps = P)
 static int corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, const int64_t* lengths, int steps,
                            float* adj, float* S1, float* S2, float* ws, void* stream) {
     const long long* len = reinterpret_cast<const long long*>(lengths);
     if (X == nullptr || ws == nullptr) return fail("corr_graph_rows: null input / workspace");
     if (S1 == nullptr || S2 == nullptr) return fail("corr_graph_rows: null output (S1=%p, S2=%p)", (void*)S1, (void*)S2);
-    if (N < 1 || N > kMaxNodes) return fail("corr_graph_rows: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
-    if (B < 1 || P < 1) return fail("corr_graph_rows: empty batch/clip (B=%d, pieces=%d)", B, P);
-    if (Q < 4 || Q % 4 != 0) return fail("corr_graph_rows: row piece of %d floats unsupported (positive multiple of 4)", Q);
+    const CorrRowsPlan p = corr_rows_plan(B, N, P, Q, piece_stride, len != nullptr, steps, g_tune[EEG_TUNE_GRAM_WGS]);
+    if (p.error == kRowsBadNodes) return fail("corr_graph_rows: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
+    if (p.error == kRowsEmpty) return fail("corr_graph_rows: empty batch/clip (B=%d, pieces=%d)", B, P);
+    if (p.error == kRowsBadPiece) return fail("corr_graph_rows: row piece of %d floats unsupported (positive multiple of 4)", Q);
     if (top_k < 0 || top_k >= N) return fail("corr_graph_rows: top_k=%d unsupported (0..%d)", top_k, N - 1);
     if (((uintptr_t)X & 15) != 0) return fail("corr_graph_rows: clips must be 16-byte aligned");
-    // pieces of a row lie piece_stride floats apart and hold all N nodes: one piece (raw rows) or >= N*Q apart (window tensors)
-    if (P > 1 && (piece_stride < (long long)N * Q || piece_stride % 4 != 0))
-        return fail("corr_graph_rows: piece stride %lld unsupported (multiple of 4, >= N*Q = %d)", piece_stride, N * Q);
-    const long long clip_floats = (P > 1 ? (long long)(P - 1) * piece_stride : 0) + (long long)N * Q;
-    if (clip_floats * 4 >= (1LL << 31)) return fail("corr_graph_rows: a clip of %lld bytes exceeds the 2 GB one descriptor covers", clip_floats * 4);
+    if (p.error == kRowsPieceStride) return fail("corr_graph_rows: piece stride %lld unsupported (multiple of 4, >= N*Q = %d)", piece_stride, N * Q);
+    if (p.error == kRowsTwoGb) return fail("corr_graph_rows: a clip of %lld bytes exceeds the 2 GB one descriptor covers", p.clip_floats * 4);
+    if (p.error == kRowsRawSteps) return fail("corr_graph_rows_len: rows of %d floats are not %d steps of a multiple of 4 samples", Q, steps);
+    if (p.error == kRowsWindowSteps) return fail("corr_graph_rows_len: steps=%d for a window tensor of %d pieces (a step is a piece)", steps, P);
     hipStream_t st = S_(stream);
-    const int ns = corr_rows_nsplit(B, P, Q);
-    const int tile_floats = N * kRowChunk > kGramFloats ? N * kRowChunk : kGramFloats;
-    const size_t lds = 4 * (size_t)tile_floats * sizeof(float);            // <= 128 KB (N = 32)
-    const unsigned ps = P > 1 ? (unsigned)piece_stride : 0u;
-    if (len != nullptr) {
-        int unit = 0;                                 // samples per step of raw rows; 0: window tensors, a step = a piece
-        if (P == 1) {
-            if (steps < 1 || Q % steps != 0 || (Q / steps) % 4 != 0)
-                return fail("corr_graph_rows_len: rows of %d floats are not %d steps of a multiple of 4 samples", Q, steps);
-            unit = Q / steps;
-        } else if (steps != P) {
-            return fail("corr_graph_rows_len: steps=%d for a window tensor of %d pieces (a step is a piece)", steps, P);
-        }
-        if (N <= 20) {
-            EEG_SET_MAX_LDS((corr_gram_rows_kernel<true, true>), lds);
-            EEG_LAUNCH_P("corr_gram_rows_len", (corr_gram_rows_kernel<true, true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, unit);
-        } else {
-            EEG_SET_MAX_LDS((corr_gram_rows_kernel<false, true>), lds);
-            EEG_LAUNCH_P("corr_gram_rows_len", (corr_gram_rows_kernel<false, true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, unit);
-        }
-    } else if (N <= 20) {
-        EEG_SET_MAX_LDS((corr_gram_rows_kernel<true>), lds);
-        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<true>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, 0);
-    } else {
-        EEG_SET_MAX_LDS((corr_gram_rows_kernel<false>), lds);
-        EEG_LAUNCH_P("corr_gram_rows", (corr_gram_rows_kernel<false>), dim3(B, ns), dim3(256), lds, st, X, N, P, Q, ps, (unsigned)clip_floats, ws, tile_floats, len, 0);
-    }
+    if (p.len) p.rem4 ? run_corr_gram_rows<true, true>(p, X, N, P, Q, ws, len, st) : run_corr_gram_rows<false, true>(p, X, N, P, Q, ws, len, st);
+    else p.rem4 ? run_corr_gram_rows<true, false>(p, X, N, P, Q, ws, len, st) : run_corr_gram_rows<false, false>(p, X, N, P, Q, ws, len, st);
     if (check_launch("corr_gram_rows")) return 1;
-    EEG_LAUNCH_P("corr_finish", corr_finish_kernel, dim3(B), dim3(256), (2 * 32 * 33 + 64) * sizeof(float), st, ws, ns, N, top_k, adj, S1, S2);
-    return check_launch("corr_finish");
+    return corr_finish(ws, B, p.ns, N, top_k, adj, S1, S2, st);
 }
 int eeg_dcrnn_corr_graph_rows(const float* X, int B, int N, int P, int Q, long long piece_stride, int top_k, float* adj, float* S1, float* S2,
                               float* ws, void* stream) {

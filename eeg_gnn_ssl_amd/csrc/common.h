@@ -25,6 +25,7 @@ constexpr size_t kMaxLdsBytes = 160 * 1024;   // LDS of one gfx950 CU
 constexpr int kMaxM = 8;        // hop matrices incl. identity (K<=3 with two supports -> 7)
 constexpr int kPStride = 34;                       // row stride of a hop-polynomial matrix in LDS (lds_diffuse.h): lds_stride(32)
 constexpr int kPFloats = kMaxNodes * kPStride;     // one padded 32x32 matrix
+constexpr int kDiffPrefetch = 4;                   // float4 per thread per sample the forward LDS diffusion prefetches (kernels_diffuse.h): covers N*F <= 4096 floats
 #if defined(EEG_DEV)            // make dev / the test emulator: tuning knobs + the recurrent kernels' cycle probe
 constexpr bool kDevBuild = true;
 #else

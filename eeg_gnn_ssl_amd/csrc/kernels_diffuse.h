@@ -20,8 +20,8 @@ namespace eeg {
 // sample's rows prefetched into registers while the current one is diffused (HBM latency hidden
 // inside the workgroup, 3-4 workgroups per CU hide the rest).
 // LDS: Pl | tile [NR][FS] with NR = round_up(N,4), FS = lds_stride(M * FP), FP = round_up(F,16):
-// slot 0 = X, slots 1..M-1 = results (staged so the global stores are full coalesced rows).
-constexpr int kDiffPrefetch = 4;        // float4 per thread per sample: covers N*F <= 4096 floats
+// slot 0 = X, slots 1..M-1 = results (staged so the global stores are full coalesced rows).  The prefetch takes kDiffPrefetch
+// (common.h) float4 per thread per sample.
 
 // Wide rows are processed in column chunks: this launch covers columns [c0, c0+Fc) of the F-wide rows.
 __global__ __launch_bounds__(256) void diffuse_fwd_kernel(const float* __restrict__ X, const float* __restrict__ P,

@@ -17,11 +17,9 @@
 //    normalisation, |.|, diag = 1, top-k per row, S1/S2.
 #pragma once
 #include "common.h"
+#include "corr_launch.h"      // kGramTile, kGramFloats, kRowChunk: shared with the launch plans
 
 namespace eeg {
-
-constexpr int kGramTile = 256;                 // one 16x16 MFMA accumulator tile, C layout (r*64 + lane)
-constexpr int kGramFloats = 3 * kGramTile;     // tiles (0,0), (0,1), (1,1) of the padded 32x32 Gram
 
 // The six accumulators of a wave's Gram (REM4: c00b / c01b / c11b are the second chains, the odd k of every pair) and the two steps
 // both Gram kernels share: the MFMAs of one 16-byte fragment pair, and the hand-over of the four waves' sums as ONE partial Gram.
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(256) void corr_gram_kernel(const float* __restrict_
 // lane-linear, so the swizzle goes on the SOURCE address), and the read of unit u of node n goes to slot u ^ (n & 15).
 // Same pipeline as corr_gram_kernel: fragments to registers, then the next chunk's DMA flies during the MFMAs; same partial-Gram
 // layout, so corr_finish_kernel serves both.  Fixed chunk -> wave assignment, fixed order: bit-reproducible.
-constexpr int kRowChunk = 256, kRowQuads = kRowChunk / 16;
+constexpr int kRowQuads = kRowChunk / 16;
 // LEN (variable-length clips, dataloader_classification.py:356-361): the valid extent of a row is separate from its stride.  Raw rows
 // (P = 1, unit = samples per step): the first clip_steps(lengths, b, Q / unit) * unit floats of every row, the row stride stays Q and
 // the ragged last chunk is masked as above; window tensors (unit = 0): the first clip_steps(lengths, b, P) pieces.
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(256) void corr_gram_rows_kernel(const float* __rest
     gram_write_partial<REM4>(acc, sm, wave, lane, part + ((size_t)b * NS + sp) * kGramFloats);
 }
 
-// grid B, block 256.  LDS: G[32][33] | A[32][33] | rowsum[32] | colsum[32]
+// grid B, block 256.  LDS: G[32][33] | A[32][33] | rowsum[32] | colsum[32] (corr_finish_lds_bytes)
 __global__ __launch_bounds__(256) void corr_finish_kernel(const float* __restrict__ part, int NS, int N, int top_k,
                                                           float* __restrict__ adj_out, float* __restrict__ S1,
                                                           float* __restrict__ S2) {

@@ -1,7 +1,8 @@
-// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h, csrc/spec_launch.h, csrc/seq_launch.h and csrc/dec_launch.h for the
-// calls read from stdin, one line each (see tests/test_gemm_plans.py, tests/test_spec_plans.py, tests/test_seq_kernels.py,
-// tests/test_dec_plans.py).  Host code only: gemm_launch.h, spec_launch.h and dec_launch.h must compile without kernel bodies;
-// seq_launch.h brings kernels_seq.h along, which is host code under platform_emu.h.
+// TEST INFRASTRUCTURE: prints the launch plans of csrc/gemm_launch.h, csrc/spec_launch.h, csrc/seq_launch.h, csrc/dec_launch.h,
+// csrc/diffuse_launch.h and csrc/corr_launch.h for the calls read from stdin, one line each (see tests/test_gemm_plans.py,
+// tests/test_spec_plans.py, tests/test_seq_kernels.py, tests/test_dec_plans.py, tests/test_diffuse_corr_plans.py).  Host code only:
+// gemm_launch.h, spec_launch.h, dec_launch.h, diffuse_launch.h and corr_launch.h must compile without kernel bodies; seq_launch.h
+// brings kernels_seq.h along, which is host code under platform_emu.h.
 //   nn   nseg F R nct_total ldc O batch_major quad_pack bf3_nct num_cus KNOBS  ->  kind t1 t2 t3 gx gy block lds error
 //   tn   nseg F R O batch_major offer_quad num_cus KNOBS                       ->  kind t1 t2 t3 nsplit rps gx gy block lds remap error
 //   pair M H R num_cus KNOBS   (the two h-part problems of a cell)             ->  1 / 0: one paired launch or not
@@ -22,11 +23,20 @@
 // The persistent decoder: every field of DecCall in its order; a direction that does not run persistently prints `per_step` in
 // place of its launch:
 //   dec  T B N H Dout M L knob_fwd knob_bwd   ->  covered ; fwd: kernel symbol ; grid 1 block lds ; bwd: likewise
+// The hop diffusion: every field of DiffuseCall in its order, the direction being the op (DKNOBS = keys 5 6 9 18).  `none`: no launch
+// (one hop matrix, no copy); the LDS kernels go out once per column chunk: `x<launches> <columns per chunk>` behind the launch:
+//   dfwd p_batched S B N F M x_bt wants_copy DKNOBS   ->  none | launch | launch ; x<count> fc | error <code>
+//   dadj (the same fields)                            ->  likewise
+// The correlation Gram (knob = key 7): the Gram launch, the finish launch and the floats of workspace between them:
+//   gram  B T N D has_len knob                        ->  launch ; corr_finish_kernel ; B 1 256 lds ; ws_floats | error <code>
+//   grows B N P Q piece_stride has_len steps knob     ->  likewise
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
+#include "corr_launch.h"
 #include "dec_launch.h"
+#include "diffuse_launch.h"
 #include "gemm_launch.h"
 #include "spec_launch.h"
 #include "seq_launch.h"
@@ -157,11 +167,61 @@ static bool dec_line(const char* op, char* out) {
     return true;
 }
 
+// one hop-diffusion line; false: not such an op
+static bool diffuse_line(const char* op, char* out) {
+    if (strcmp(op, "dfwd") && strcmp(op, "dadj")) return false;
+    DiffuseCall c{};
+    int copy;
+    if (scanf("%d %d %d %d %d %d %d %d %d %d %d %d", &c.p_batched, &c.S, &c.B, &c.N, &c.F, &c.M, &c.x_bt, &copy, &c.fwd_wgs, &c.adj_wgs, &c.adj_lds,
+              &c.adj_planes) != 12) exit(2);
+    c.adjoint = op[1] == 'a'; c.wants_copy = copy != 0;
+    const DiffusePlan p = diffuse_plan(c);
+    char sym[64];
+    if (p.error) { sprintf(out, "error %d", p.error); return true; }
+    switch (p.kind) {
+        case DiffuseKind::None: sprintf(out, "none"); return true;
+        case DiffuseKind::StreamFwd: launch(out, "diffuse_fwd_stream_kernel<19>", p.gx, p.gy, p.block, p.lds); return true;
+        case DiffuseKind::StreamAdj: launch(out, "diffuse_adj_stream_kernel<19>", p.gx, p.gy, p.block, p.lds); return true;
+        case DiffuseKind::RowsAdj: sprintf(sym, "diffuse_adj_rows_kernel<19, %d>", p.mm); launch(out, sym, p.gx, p.gy, p.block, p.lds); return true;
+        default: break;
+    }
+    out += launch(out, p.kind == DiffuseKind::LdsFwd ? "diffuse_fwd_kernel" : "diffuse_adj_kernel", p.gx, p.gy, p.block, p.lds);
+    sprintf(out, " ; x%d %d", p.nchunks, p.fc);
+    return true;
+}
+
+// one correlation-Gram line; false: not such an op
+static bool corr_line(const char* op, char* out) {
+    char sym[64];
+    int B, T, N, D, P, Q, has_len, steps, knob, error, gy;
+    size_t lds, ws;
+    if (!strcmp(op, "gram")) {
+        if (scanf("%d %d %d %d %d %d", &B, &T, &N, &D, &has_len, &knob) != 6) exit(2);
+        const CorrGramPlan p = corr_gram_plan(B, T, N, D, has_len != 0, knob);
+        sprintf(sym, "corr_gram_kernel<%d, %s, %s>", p.nq, p.rem4 ? "true" : "false", p.len ? "true" : "false");
+        error = p.error; gy = p.gy; lds = p.lds; ws = p.ws_floats;
+    } else if (!strcmp(op, "grows")) {
+        long long piece_stride;
+        if (scanf("%d %d %d %d %lld %d %d %d", &B, &N, &P, &Q, &piece_stride, &has_len, &steps, &knob) != 8) exit(2);
+        const CorrRowsPlan p = corr_rows_plan(B, N, P, Q, piece_stride, has_len != 0, steps, knob);
+        sprintf(sym, "corr_gram_rows_kernel<%s, %s>", p.rem4 ? "true" : "false", p.len ? "true" : "false");
+        error = p.error; gy = p.gy; lds = p.lds; ws = p.ws_floats;
+    } else {
+        return false;
+    }
+    if (error) { sprintf(out, "error %d", error); return true; }
+    out += launch(out, sym, B, gy, 256, lds);
+    out += sprintf(out, " ; ");
+    out += launch(out, "corr_finish_kernel", B, 1, 256, corr_finish_lds_bytes());
+    sprintf(out, " ; %zu", ws);
+    return true;
+}
+
 int main() {
     char op[8], out[512];
     while (scanf("%7s", op) == 1) {
         int bm, quad;
-        if (spec_line(op, out) || seq_line(op, out) || dec_line(op, out)) {
+        if (spec_line(op, out) || seq_line(op, out) || dec_line(op, out) || diffuse_line(op, out) || corr_line(op, out)) {
         } else if (!strcmp(op, "nn")) {
             NnCall c{};
             if (scanf("%d %d %d %d %d %d %d %d %d %d", &c.nseg, &c.F, &c.R, &c.nct_total, &c.ldc, &c.O, &bm, &quad, &c.bf3_nct, &c.num_cus) != 10 || !knobs(c.knobs)) return 2;
