@@ -8,10 +8,12 @@ from . import ops, utils                                  # noqa: F401
 from .device_data import (DeviceDataset, EpochSampler, RecordingDataset, clip_table_classification, clip_table_detection,      # noqa: F401
                           clip_table_ssl, layout_recordings)
 from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
+from .interpret import OcclusionResult, occlusion_maps     # noqa: F401
 from .model.cell import DCGRUCell, DiffusionGraphConv     # noqa: F401
 from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,   # noqa: F401
                           DCRNNModel_nextTimePred)
 
 __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
            "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "RecordingDataset", "clip_table_detection",
-           "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "ops", "utils"]
+           "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "OcclusionResult",
+           "occlusion_maps", "ops", "utils"]

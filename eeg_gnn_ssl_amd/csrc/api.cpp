@@ -1,4 +1,5 @@
 // C ABI of libeeg_dcrnn_hip.so (see include/eeg_dcrnn.h): argument checking + kernel orchestration.
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -15,6 +16,7 @@
 #include "diffuse_launch.h"
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
+#include "kernels_occlude.h"
 #include "kernels_data.h"
 #include "kernels_records.h"
 #include "kernels_feat.h"
@@ -1329,6 +1331,62 @@ int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, doubl
     EEG_LAUNCH_P("ssl_eval_metrics", ssl_eval_metrics_kernel, dim3(1), dim3(kSslEvalThreads), kSslEvalThreads * sizeof(double), S_(stream), scores, (int)P,
                  (int)(G < P ? G : P), record);
     return check_launch("ssl_eval_metrics");
+}
+
+/* ---- occlusion maps: the variants of one window, their scores ------------------------------------- */
+static_assert(EEG_OCCLUDE_MAX_LAYERS == kOccMaxLayers && EEG_OCCLUDE_MAX_GROUPS == kOccMaxGroups, "include/eeg_dcrnn.h and kernels_occlude.h disagree");
+int eeg_dcrnn_occlude_expand(const float* x, const float* const* hext, int L, const int32_t* groups, const int64_t* lengths, int B, int T, int N, int D,
+                             int H, int G, int t0, int w, float fill, float* x_var, float* h0_var, int64_t* len_var, void* stream) {
+    if (x == nullptr || hext == nullptr || groups == nullptr) return fail("occlude_expand: null x / layer table / groups");
+    if (x_var == nullptr || h0_var == nullptr || len_var == nullptr) return fail("occlude_expand: null x_var / h0_var / len_var");
+    if (L < 1 || L > kOccMaxLayers) return fail("occlude_expand: %d layers (1..%d)", L, kOccMaxLayers);
+    if (G < 1 || G > kOccMaxGroups) return fail("occlude_expand: G=%d groups (1..%d)", G, kOccMaxGroups);
+    if (B < 1 || T < 1 || H < 1) return fail("occlude_expand: B=%d clips, T=%d steps, H=%d units", B, T, H);
+    if (N < 1 || N > kMaxNodes) return fail("occlude_expand: num_nodes=%d unsupported (1..%d)", N, kMaxNodes);
+    if (D < 4 || D % 4 != 0) return fail("occlude_expand: D=%d: the rows move in 16-byte pieces, D must be a positive multiple of 4", D);
+    if (((long long)N * H) % 4 != 0) return fail("occlude_expand: N*H=%lld must be a multiple of 4", (long long)N * H);
+    if (t0 < 0 || t0 >= T) return fail("occlude_expand: the window starts at t0=%d of T=%d steps", t0, T);
+    if (w < 1) return fail("occlude_expand: a window of w=%d steps", w);
+    if ((long long)(T + L) * B * G >= (1ll << 30) || (long long)N * D >= (1ll << 30) || (long long)N * H >= (1ll << 30))
+        return fail("occlude_expand: B=%d, G=%d, T=%d, N=%d, D=%d, H=%d: too many rows for one launch", B, G, T, N, D, H);
+    OccludeExpand a;
+    uintptr_t al = (uintptr_t)x | (uintptr_t)x_var | (uintptr_t)h0_var;
+    for (int l = 0; l < kOccMaxLayers; ++l) {
+        a.hext[l] = l < L ? hext[l] : nullptr;
+        if (l < L && hext[l] == nullptr) return fail("occlude_expand: null hext of layer %d", l);
+        al |= (uintptr_t)a.hext[l];
+    }
+    if ((al & 15) != 0) return fail("occlude_expand: x, hext, x_var and h0_var must be 16-byte aligned");
+    if (((uintptr_t)groups & 3) != 0 || (((uintptr_t)lengths | (uintptr_t)len_var) & 7) != 0)
+        return fail("occlude_expand: pointers must be aligned to their element size");
+    a.x = x; a.groups = reinterpret_cast<const int*>(groups); a.lengths = reinterpret_cast<const long long*>(lengths);
+    a.x_var = x_var; a.h0_var = h0_var; a.len_var = reinterpret_cast<long long*>(len_var);
+    a.B = B; a.T = T; a.N = N; a.D4 = D / 4; a.NH4 = N * H / 4; a.L = L; a.G = G; a.t0 = t0; a.w = w; a.fill = fill;
+    // the stretches of groups: one per (row, clip) unless the capped grid would stay unfilled
+    const int cap = kOccBlocksPerCu * platform_num_cus(), rows = (T - t0 + L) * B;
+    const int want = std::min(G, std::max(1, ceil_div(cap, rows)));
+    a.gper = ceil_div(G, want);
+    a.nch = ceil_div(G, a.gper);
+    const int units = rows * a.nch;
+    EEG_LAUNCH_P("occlude_expand", occlude_expand_kernel, dim3(std::min(units, cap)), dim3(kOccThreads), kMaxNodes * sizeof(unsigned long long), S_(stream), a);
+    return check_launch("occlude_expand");
+}
+int eeg_dcrnn_occlusion_scores(const float* var_logits, const float* base_logits, const int64_t* lengths, const int64_t* target, int B, int G, int C,
+                               int Tw, int k, int t0, float* maps, float* base_prob, int64_t* target_out, void* stream) {
+    if (var_logits == nullptr || base_logits == nullptr) return fail("occlusion_scores: null variant / baseline logits");
+    if (maps == nullptr || base_prob == nullptr) return fail("occlusion_scores: null maps / base_prob");
+    if (B < 1 || (long long)B * G >= (1ll << 30)) return fail("occlusion_scores: B=%d clips of G=%d groups", B, G);
+    if (G < 1 || G > kOccMaxGroups) return fail("occlusion_scores: G=%d groups (1..%d)", G, kOccMaxGroups);
+    if (C < 1 || C > kOccMaxClasses) return fail("occlusion_scores: C=%d classes unsupported (1..%d)", C, kOccMaxClasses);
+    if (Tw < 1 || k < 0 || k >= Tw) return fail("occlusion_scores: window k=%d of Tw=%d", k, Tw);
+    if (t0 < 0) return fail("occlusion_scores: the window starts at t0=%d", t0);
+    if ((((uintptr_t)var_logits | (uintptr_t)base_logits | (uintptr_t)maps | (uintptr_t)base_prob) & 3) != 0 ||
+        (((uintptr_t)lengths | (uintptr_t)target | (uintptr_t)target_out) & 7) != 0)
+        return fail("occlusion_scores: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("occlusion_scores", occlusion_scores_kernel, dim3(ceil_div(B * G, 256)), dim3(256), 0, S_(stream), var_logits, base_logits,
+                 reinterpret_cast<const long long*>(lengths), reinterpret_cast<const long long*>(target), B, G, C, Tw, k, t0, k == 0 ? 1 : 0, maps,
+                 base_prob, reinterpret_cast<long long*>(target_out));
+    return check_launch("occlusion_scores");
 }
 
 /* ---- per-clip correlation graph -> supports --------------------------------------------------- */

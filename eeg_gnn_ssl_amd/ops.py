@@ -12,7 +12,8 @@ Operators (namespace `eeg_dcrnn`):
     hop_polys, pack_cell, diffusion_hops, dconv (+ dconv_bwd), dcgru_layer (+ dcgru_layer_bwd),
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
-    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics.
+    clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
+    occlude_expand, occlusion_scores.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1599,6 +1600,87 @@ _define("ssl_eval_scores", "(Tensor pred, Tensor target, Tensor clip_w, Tensor c
 _define("ssl_eval_metrics", "(Tensor scores, int group, Tensor(a!) record) -> ()", _ssl_eval_metrics_impl, lambda *a: None)
 
 
+# ---- occlusion maps on the device (interpret.py: occlusion_maps) -------------------------------------------------------------------
+OCCLUDE_MAX_LAYERS = 4        # EEG_OCCLUDE_MAX_LAYERS
+OCCLUDE_MAX_GROUPS = 64       # EEG_OCCLUDE_MAX_GROUPS
+
+
+def _aligned16(what, **tensors):
+    for name, t in tensors.items():
+        if t.data_ptr() % 16 != 0:
+            raise RuntimeError(f"{what}: {name} is not 16-byte aligned (a view with an odd element offset): pass a tensor of its own")
+
+
+def _occlude_expand_impl(x, hext, groups, lengths, t0: int, w: int, fill: float, x_var, h0_var, len_var) -> None:
+    lib = _lib.get_lib()
+    what = "occlude_expand"
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be (B, T, N, D) float32, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    _check(lib, x, "x")
+    b, t, n, d = (int(v) for v in x.shape)
+    dev = x.device
+    layers = len(hext)
+    if not 1 <= layers <= OCCLUDE_MAX_LAYERS:
+        raise RuntimeError(f"{what}: {layers} layers (1..{OCCLUDE_MAX_LAYERS}: EEG_OCCLUDE_MAX_LAYERS)")
+    if d < 4 or d % 4 != 0:
+        raise RuntimeError(f"{what}: D={d}: the rows move in 16-byte pieces, D must be a positive multiple of 4")
+    if not torch.is_tensor(groups) or groups.dim() != 2 or groups.shape[1] != n or not 1 <= groups.shape[0] <= OCCLUDE_MAX_GROUPS:
+        raise RuntimeError(f"{what}: groups must be a (G, {n}) int32 0/1 mask with 1 <= G <= {OCCLUDE_MAX_GROUPS}, got "
+                           f"{tuple(groups.shape) if torch.is_tensor(groups) else type(groups).__name__}")
+    g = int(groups.shape[0])
+    _eval_tensor(what, "groups", groups, torch.int32, (g, n), dev)
+    if not 0 <= t0 < t or w < 1:
+        raise RuntimeError(f"{what}: a window of w={w} steps at t0={t0} of T={t}")
+    if hext[0].dim() != 3 or hext[0].shape[2] % n != 0:
+        raise RuntimeError(f"{what}: hext must be (T+1, B, N*H), got {tuple(hext[0].shape)}")
+    nh = int(hext[0].shape[2])
+    if nh % 4 != 0:
+        raise RuntimeError(f"{what}: N*H={nh} must be a multiple of 4")
+    for layer, he in enumerate(hext):
+        _eval_tensor(what, f"hext[{layer}]", he, torch.float32, (t + 1, b, nh), dev)
+    if lengths is not None:
+        _eval_tensor(what, "lengths", lengths, torch.int64, (b,), dev)
+    _eval_tensor(what, "x_var", x_var, torch.float32, (t - t0, b * g, n, d), dev)
+    _eval_tensor(what, "h0_var", h0_var, torch.float32, (layers, b * g, nh), dev)
+    _eval_tensor(what, "len_var", len_var, torch.int64, (b * g,), dev)
+    _aligned16(what, x=x, x_var=x_var, h0_var=h0_var, **{f"hext[{i}]": he for i, he in enumerate(hext)})
+    tab = (ctypes.c_void_p * layers)(*[he.data_ptr() for he in hext])
+    lib.call("eeg_dcrnn_occlude_expand", _p(x), tab, layers, _p(groups), _p(lengths), b, t, n, d, nh // n, g, int(t0), int(w), float(fill),
+             _p(x_var), _p(h0_var), _p(len_var), _stream(x))
+
+
+def _occlusion_scores_impl(var_logits, base_logits, lengths, target, k: int, t0: int, maps, base_prob, target_out) -> None:
+    lib = _lib.get_lib()
+    what = "occlusion_scores"
+    if not torch.is_tensor(maps) or maps.dim() != 3 or min(maps.shape) < 1:
+        raise RuntimeError(f"{what}: maps must be (B, Tw, G) float32, got {tuple(maps.shape) if torch.is_tensor(maps) else type(maps).__name__}")
+    _check(lib, maps, "maps")
+    b, tw, g = (int(v) for v in maps.shape)
+    dev = maps.device
+    if not torch.is_tensor(base_logits) or base_logits.dim() != 2 or base_logits.shape[0] != b or base_logits.shape[1] < 1:
+        raise RuntimeError(f"{what}: base_logits must be ({b}, C) for maps {tuple(maps.shape)}, got "
+                           f"{tuple(base_logits.shape) if torch.is_tensor(base_logits) else type(base_logits).__name__}")
+    c = int(base_logits.shape[1])
+    if g > OCCLUDE_MAX_GROUPS:
+        raise RuntimeError(f"{what}: G={g} groups (1..{OCCLUDE_MAX_GROUPS}: EEG_OCCLUDE_MAX_GROUPS)")
+    _eval_tensor(what, "base_logits", base_logits, torch.float32, (b, c), dev)
+    _eval_tensor(what, "var_logits", var_logits, torch.float32, (b * g, c), dev)
+    _eval_tensor(what, "base_prob", base_prob, torch.float32, (b,), dev)
+    for name, t in (("lengths", lengths), ("target", target), ("target_out", target_out)):
+        if t is not None:
+            _eval_tensor(what, name, t, torch.int64, (b,), dev)
+    if not 0 <= k < tw or t0 < 0:
+        raise RuntimeError(f"{what}: window k={k} of Tw={tw} at t0={t0}")
+    lib.call("eeg_dcrnn_occlusion_scores", _p(var_logits), _p(base_logits), _p(lengths), _p(target), b, g, c, tw, int(k), int(t0), _p(maps),
+             _p(base_prob), _p(target_out), _stream(maps))
+
+
+_define("occlude_expand", "(Tensor x, Tensor[] hext, Tensor groups, Tensor? lengths, int t0, int w, float fill, Tensor(a!) x_var, Tensor(b!) h0_var, "
+        "Tensor(c!) len_var) -> ()", _occlude_expand_impl, lambda *a: None)
+_define("occlusion_scores", "(Tensor var_logits, Tensor base_logits, Tensor? lengths, Tensor? target, int k, int t0, Tensor(a!) maps, "
+        "Tensor(b!) base_prob, Tensor(c!)? target_out) -> ()", _occlusion_scores_impl, lambda *a: None)
+
+
 def _loss_setup(ctx, inputs, output):
     ctx.save_for_backward(output[1])
     ctx.n_in = len(inputs)
@@ -2443,3 +2525,22 @@ def ssl_eval_metrics(scores, group: int, record=None):
         record = torch.zeros(SSL_EVAL_RECORD_WORDS, dtype=torch.float64, device=scores.device)
     torch.ops.eeg_dcrnn.ssl_eval_metrics(scores, int(group), record)
     return record
+
+
+def occlude_expand(x, hext, groups, lengths, t0: int, w: int, fill: float, x_var, h0_var, len_var):
+    """The B*G variants of ONE occlusion window (steps [t0, t0 + w)) of x (B, T, N, D), variant v = b*G + g, into buffers the caller
+    owns: x_var (T - t0, B*G, N, D) time-major -- `fill` where the step lies inside the window and groups[g, n] != 0, else
+    x[b, t0 + s, n, :] --, h0_var (L, B*G, N*H) = hext[l][t0, b] for every g (hext: the (T+1, B, N*H) state sequences of the encoder
+    layers of the unoccluded pass, L <= OCCLUDE_MAX_LAYERS) and len_var (B*G,) int64 = max(lengths[b] - t0, 1) (lengths None: T - t0).
+    groups: (G, N) int32 0/1 on the device, G <= OCCLUDE_MAX_GROUPS; an empty group occludes nothing.  A copy kernel: bit for bit, in
+    16-byte pieces (D % 4 == 0, N*H % 4 == 0, 16-byte aligned tensors).  One launch, no allocation."""
+    torch.ops.eeg_dcrnn.occlude_expand(x, list(hext), groups, lengths, int(t0), int(w), float(fill), x_var, h0_var, len_var)
+
+
+def occlusion_scores(var_logits, base_logits, lengths, target, k: int, t0: int, maps, base_prob, target_out=None):
+    """Slice k of an occlusion map from the logits of its window's variants: maps[b, k, g] = p_b - p_{b,k,g} with p = sigmoid(logit)
+    (one output) or softmax(logits)[target_b]; exactly 0.0 where the window starts at or behind the clip's end (t0 >= lengths[b]).
+    target: int64 (B,) on the device -- a class outside 0..C-1 is CLAMPED in the kernel -- or None: the arg-max of the baseline row,
+    lowest index on ties.  The probabilities are evaluated in double from the float32 logits.  k == 0 also writes base_prob (B,) and
+    (if given) the classes followed to target_out (B,) int64.  One launch, no allocation, no host synchronisation."""
+    torch.ops.eeg_dcrnn.occlusion_scores(var_logits, base_logits, lengths, target, int(k), int(t0), maps, base_prob, target_out)

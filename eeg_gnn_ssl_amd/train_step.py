@@ -611,6 +611,26 @@ class TrainStep:
         return DeviceSSLEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world, keep_predictions=keep_predictions,
                                   loss_batch=loss_batch)
 
+    def occlusion_maps(self, x, seq_lengths, supports=None, **kw):
+        """occlusion maps (`interpret.occlusion_maps`) of this step's model on the inputs of an evaluation step: x as the step takes
+        it (features, windows or raw signals) goes through the data chain WITHOUT augmentation draws -- with supports=None the
+        correlation graph of the unpadded clip, built once and held fixed for every variant -- and the maps are taken on what the
+        model would see.  Keywords: time_window, node_groups, fill, target, clips_per_pass, return_logits.  Leaves the model's mode,
+        the step's counters, generators, optimiser state and sampler alone."""
+        from .interpret import _check_options, occlusion_maps
+        if self.task == "ssl":
+            raise ValueError("TrainStep.occlusion_maps: task='ssl' predicts signals, not a probability; occlusion maps exist for the "
+                             "detection and classification models (its evaluation pass is TrainStep.ssl_evaluator / evaluate_ssl)")
+        classes = int(self.model.fc.weight.shape[0])
+        if (self.task == "detection") != (classes == 1):
+            raise ValueError(f"TrainStep.occlusion_maps(task={self.task!r}): the model's head has {classes} outputs")
+        if not torch.is_tensor(x):
+            raise ValueError(f"TrainStep.occlusion_maps: x must be a tensor, got {type(x).__name__}")
+        _check_options(self.model, int(self.model.num_nodes), x.device, kw.get("time_window", 1), kw.get("node_groups"), kw.get("clips_per_pass", 16))
+        with torch.no_grad():
+            feats, _, sup = self._data_chain(x, None, seq_lengths, supports)
+        return occlusion_maps(self.model, feats, seq_lengths, sup, **kw)
+
     # -- checkpointing (utils.CheckpointSaver / load_model_checkpoint use these like an optimizer's) -------
     def state_dict(self):
         """with a sampler attached also its (seed, epoch, cursor): a resumed run continues mid-epoch on the same clips"""

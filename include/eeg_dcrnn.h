@@ -469,6 +469,32 @@ int eeg_dcrnn_ssl_eval_scores(const float* pred, const float* target, const floa
                               void* stream);
 int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, double* record, void* stream);
 
+/* Occlusion maps on the device: group g of channels of clip b is overwritten with `fill` over the window of steps [t0, t0 + w) and the
+ * map records how far the predicted probability drops.  All variants of a window start from the unoccluded clip's state at t0.
+ *
+ * eeg_dcrnn_occlude_expand: one launch per window builds what the layer entry points need for its B * G variants, v = b * G + g,
+ * into buffers the caller owns.  x (B, T, N, D) float32, batch-major; hext: a HOST table of L <= EEG_OCCLUDE_MAX_LAYERS device
+ * pointers, the `hext` (T+1, B, N*H) of every encoder layer of the unoccluded pass (slot t = the state in front of step t);
+ * groups (G, N) int32 0/1 in device memory, 1 <= G <= EEG_OCCLUDE_MAX_GROUPS (an empty group occludes nothing); lengths: device
+ * int64 (B) or NULL.  Written:
+ *   x_var   (T - t0, B*G, N, D)  time-major: `fill` where step s < w and groups[g][n] != 0, else x[b][t0 + s][n][:]
+ *   h0_var  (L, B*G, N*H)        hext[l][t0][b][:] for every g
+ *   len_var (B*G) int64          max(lengths[b] - t0, 1); lengths NULL: T - t0
+ * and nothing else.  D % 4 == 0, N*H % 4 == 0, x / hext / x_var / h0_var 16-byte aligned (the rows move as 16-byte pieces, bit for bit).
+ *
+ * eeg_dcrnn_occlusion_scores: one launch per window behind the head.  var_logits (B*G, C), base_logits (B, C) float32;
+ * maps (B, Tw, G) float32: maps[b][k][g] = p_b - p_{b,k,g}, exactly 0.0f where the window starts at or behind the clip's end
+ * (t0 >= lengths[b]; lengths NULL: never).  C == 1: p = sigmoid(logit); C > 1: p = softmax(logits)[cls_b] with cls_b = target[b]
+ * CLAMPED to 0..C-1, or (target NULL) the arg-max of the baseline row, lowest index on ties.  The probabilities are evaluated in
+ * double from the float32 logits and the difference is rounded to float32 once.  k == 0 also writes base_prob[b] = p_b and
+ * (target_out nullable, int64 (B)) the class followed. */
+#define EEG_OCCLUDE_MAX_LAYERS 4
+#define EEG_OCCLUDE_MAX_GROUPS 64
+int eeg_dcrnn_occlude_expand(const float* x, const float* const* hext, int L, const int32_t* groups, const int64_t* lengths, int B, int T, int N, int D,
+                             int H, int G, int t0, int w, float fill, float* x_var, float* h0_var, int64_t* len_var, void* stream);
+int eeg_dcrnn_occlusion_scores(const float* var_logits, const float* base_logits, const int64_t* lengths, const int64_t* target, int B, int G, int C,
+                               int Tw, int k, int t0, float* maps, float* base_prob, int64_t* target_out, void* stream);
+
 /* utils.last_relevant_pytorch (utils.py:346-357): last[b] = Htop[lengths[b]-1, b]. Htop (T,B,NH). */
 int eeg_dcrnn_gather_last(const float* Htop, const int64_t* lengths, int T, int B, int NH,
                           float* last, void* stream);
