@@ -129,7 +129,13 @@ def _clip_weights(what: str, clip_w: torch.Tensor, denom: torch.Tensor, b: int, 
 
 
 def _new(shape, like: torch.Tensor, dtype=torch.float32):
+    """THE allocation of the device implementations (outputs, saved tensors, workspaces): uninitialised memory on like's device"""
     return torch.empty(shape, dtype=dtype, device=like.device)
+
+
+def _new_like(t: torch.Tensor):
+    """as `_new`, with the shape and dtype of the contiguous tensor t"""
+    return _new(t.shape, t, t.dtype)
 
 
 def _none_if_empty(t: Optional[torch.Tensor]):
@@ -951,7 +957,7 @@ def _rng_take_impl(rng_state, groups: int):
     stream (so a replayed HIP graph keeps drawing fresh masks)"""
     lib = _lib.get_lib()
     _check_rng(lib, rng_state, "rng_state")
-    used = torch.empty_like(rng_state)
+    used = _new_like(rng_state)
     lib.call("eeg_dcrnn_rng_take", _p(rng_state), int(groups), _p(used), _stream(rng_state))
     return used
 
@@ -965,7 +971,7 @@ def _cls_head_bwd_impl(z, w, dlogits, arg, dropout_p: float, rng_used, dw, db):
             or tuple(dw.shape) != (c, h) or db.numel() != c:
         raise RuntimeError(f"cls_head_bwd: operands do not fit: z {tuple(z.shape)}, w {tuple(w.shape)}, dlogits {tuple(dlogits.shape)}, "
                            f"arg {tuple(arg.shape)} {arg.dtype}, dw {tuple(dw.shape)}, db {tuple(db.shape)}")
-    dz = torch.empty_like(z)
+    dz = _new_like(z)
     lib.call("eeg_dcrnn_cls_head_bwd", _p(z), _p(w), _p(dlogits), _p(arg), b, n, h, w.shape[0], float(dropout_p),
              _p(rng_used) if dropout_p > 0 else None, _p(dz), _p(dw), _p(db), _stream(z))
     return dz
@@ -976,7 +982,7 @@ def _dropout_mask_impl(rng_used, n: int, dropout_p: float):
     forward call reported (tests: handed to the oracle)"""
     lib = _lib.get_lib()
     _check_rng(lib, rng_used, "rng_used")
-    mask = torch.empty((n,), dtype=torch.float32, device=rng_used.device)
+    mask = _new((n,), rng_used)
     lib.call("eeg_dcrnn_dropout_mask", _p(rng_used), n, float(dropout_p), _p(mask), _stream(rng_used))
     return mask
 
@@ -1004,7 +1010,7 @@ def _cls_head_backward(ctx, dlogits, _darg):
     if dlogits is None:
         return None, None, None, None, None
     sunk = [GradSink.take(q) for q in ctx.params]
-    dw = sunk[0] if sunk[0] is not None else torch.empty_like(w)
+    dw = sunk[0] if sunk[0] is not None else _new_like(w)
     db = sunk[1] if sunk[1] is not None else _new((w.shape[0],), z)
     dz = torch.ops.eeg_dcrnn.cls_head_bwd(z, w, dlogits, arg, ctx.dropout_p, rng_used if ctx.dropout_p > 0 else None, dw, db)
     return dz, (None if sunk[0] is not None else dw), (None if sunk[1] is not None else db), None, None
@@ -1042,7 +1048,7 @@ def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_us
             raise RuntimeError("cls_head_loss: dropout_p > 0 needs rng_used (ops.rng_take)")
         _check_rng(lib, rng_used, "rng_used")
     loss, logits, arg = _new((1,), z), _new((b, c), z), _new((b, c), z, torch.int32)
-    dlogits, dz = _new((b, c), z), torch.empty_like(z)
+    dlogits, dz = _new((b, c), z), _new_like(z)
     ws = _new((lib.query("eeg_dcrnn_cls_head_loss_ws_floats", b, h, c),), z)
     if clip_w is None:
         lib.call("eeg_dcrnn_cls_head_loss", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
@@ -1120,7 +1126,7 @@ def _fft_features_impl(raw, window: int, mean: float, std: float, standardise: b
     b, n, total = raw.shape
     t_len = total // window
     feat_raw = _new((b, t_len, n, window // 2), raw)
-    feat_std = torch.empty_like(feat_raw) if standardise else _new((0,), raw)
+    feat_std = _new_like(feat_raw) if standardise else _new((0,), raw)
     if perm is not None:
         if perm.numel() != b * n:
             raise RuntimeError(f"fft_features: perm has shape {tuple(perm.shape)}, expected ({b}, {n}) source channels")
@@ -1190,7 +1196,7 @@ def _fft_features_pair_impl(raw_x, raw_y, window: int, mean: float, std: float, 
     tx, ty = total // window, raw_y.shape[2] // window
     perm, log_scale = _check_draws("fft_features_pair", perm, log_scale, b, n, raw_x, permutation=True)
     feat_raw = _new((b, tx, n, window // 2), raw_x)
-    x_std = torch.empty_like(feat_raw)
+    x_std = _new_like(feat_raw)
     y_std = _new((b, ty, n, window // 2), raw_x)
     lib.call("eeg_dcrnn_fft_features_pair", _p(raw_x), _p(raw_y), b, n, tx, ty, int(window), _p(perm), _p(log_scale), float(mean), float(std),
              _p(feat_raw), _p(x_std), _p(y_std), _stream(raw_x))
@@ -1225,7 +1231,7 @@ def _augment_features_impl(x, y, perm, log_scale, feature_std: float):
     # the per-clip quotient (B floats) is left to the framework: it is then the very value the expression
     # `x.gather(2, idx) + (log_scale / feature_std)[:, None, None, None]` adds, on whichever device
     shift = (log_scale / float(feature_std)).contiguous()
-    x_out, y_out = torch.empty_like(x), torch.empty_like(y)
+    x_out, y_out = _new_like(x), _new_like(y)
     lib.call("eeg_dcrnn_augment_features", _p(x), _p(y), b, tx, int(y.shape[1]), n, d, _p(perm), _p(shift), _p(x_out), _p(y_out), _stream(x))
     return x_out, y_out
 
@@ -1325,8 +1331,8 @@ def _augment_windows_impl(x, y, perm, scale, mean: float, std: float):
     # the two per-clip factors (B floats each) are left to the framework, like `shift` of augment_features: they are then the very
     # values the expression `x.gather(2, idx) * a[:, None, None, None] + c[:, None, None, None]` uses, on whichever device
     c = ((a - 1.0) * (float(mean) / float(std))).contiguous()
-    x_out = torch.empty_like(x)
-    y_out = torch.empty_like(y) if y is not None else _new((0,), x)
+    x_out = _new_like(x)
+    y_out = _new_like(y) if y is not None else _new((0,), x)
     lib.call("eeg_dcrnn_augment_windows", _p(x), _p(y), b, tx, ty, n, d, _p(perm), _p(a), _p(c), _p(x_out), _p(y_out) if y is not None else None,
              _stream(x))
     return x_out, y_out
@@ -1385,7 +1391,7 @@ def _bce_logits_impl(logits, y, clip_w=None, denom=None):
     _check(lib, yy, "targets")
     if yy.numel() != x.numel():
         raise RuntimeError(f"bce_logits: {yy.numel()} targets for {x.numel()} logits")
-    loss, dx = _new((1,), x), torch.empty_like(x)
+    loss, dx = _new((1,), x), _new_like(x)
     if clip_w is None:
         lib.call("eeg_dcrnn_bce_logits", _p(x), _p(yy), x.numel(), _p(loss), _p(dx), _stream(x))
     else:
@@ -1402,7 +1408,7 @@ def _ce_logits_impl(logits, y, clip_w=None, denom=None):
     _check(lib, yy, "targets", torch.int64)
     if x.dim() != 2 or yy.numel() != x.shape[0]:
         raise RuntimeError(f"ce_logits: logits {tuple(x.shape)} need shape (B, C) and {yy.numel()} targets B entries")
-    loss, dx = _new((1,), x), torch.empty_like(x)
+    loss, dx = _new((1,), x), _new_like(x)
     if clip_w is None:
         lib.call("eeg_dcrnn_ce_logits", _p(x), _p(yy), x.shape[0], x.shape[1], _p(loss), _p(dx), _stream(x))
     else:
@@ -1424,7 +1430,7 @@ def _masked_loss_impl(pred, y, use_scaler: bool, mean: float, std: float, mask_v
     _check(lib, t, "y_true")
     if pr.shape != t.shape:
         raise RuntimeError(f"y_predicted {tuple(pr.shape)} and y_true {tuple(t.shape)} differ in shape")
-    loss, dp = _new((1,), pr), torch.empty_like(pr)
+    loss, dp = _new((1,), pr), _new_like(pr)
     ws = _new((lib.query("eeg_dcrnn_masked_loss_ws_floats"),), pr)
     if clip_w is None:
         lib.call("eeg_dcrnn_masked_loss", _p(pr), _p(t), pr.numel(), 1 if use_scaler else 0, float(mean), float(std),
@@ -2320,8 +2326,8 @@ def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.
     _weights_together("cls_head_loss", clip_w, denom, z)
     used = rng_take(rng_state, z.numel() // 4) if dropout_p > 0 else None
     sunk = [GradSink.take(q) for q in (fc_weight, fc_bias)]
-    dw = sunk[0] if sunk[0] is not None else torch.empty_like(fc_weight)
-    db = sunk[1] if sunk[1] is not None else torch.empty_like(fc_bias)
+    dw = sunk[0] if sunk[0] is not None else _new_like(fc_weight)
+    db = sunk[1] if sunk[1] is not None else _new_like(fc_bias)
     kind = 0 if task == "detection" else 1
     if clip_w is None:
         loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,

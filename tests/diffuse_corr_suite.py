@@ -205,7 +205,8 @@ def case_line(case):
 
 
 # ---- one case ------------------------------------------------------------------------------------------------------------------------
-def check_diffuse_case(name, device):
+def diffuse_call(name, device):
+    """-> (run(): the operator call of a diffusion case on `device` -> its result, want: the float64 restatement, role)"""
     from eeg_gnn_ssl_amd import _lib, ops
     c = DIFFUSE_CASES[name]
     s, b, n, f, m, pb = c["s"], c["b"], c["n"], c["f"], c["m"], c["pb"]
@@ -213,26 +214,38 @@ def check_diffuse_case(name, device):
     graphs = b if pb else 1
     polys = torch.randn(graphs, m - 1, n, n, generator=g) / n ** 0.5
     p64 = polys.double()[torch.arange(s) % b if pb else torch.zeros(s, dtype=torch.long)]          # (S, M-1, N, N): sample s = t * B + clip
-    role = "diffuse_adj" if c["adjoint"] else "diffuse_fwd"
     if not c["adjoint"]:
         x = torch.randn(s, n, f, generator=g)
-        out = {}
-        ran = ps.kernels_run(lambda: out.update(planes=ops.diffusion_hops(x.to(device), polys.to(device), pb, b)))
+        xd, pd = x.to(device), polys.to(device)
         want = torch.einsum("smij,sjf->msif", p64, x.double())
-        ps.assert_close(out["planes"].cpu().numpy(), want.numpy(), f"{name}: hop planes")
-    else:
-        z = torch.randn(s, n, m * f, generator=g)
-        zd, pd = z.to(device), polys.to(device)
+        return (lambda: ops.diffusion_hops(xd, pd, pb, b)), want, "diffuse_fwd"
+    z = torch.randn(s, n, m * f, generator=g)
+    zd, pd = z.to(device), polys.to(device)
+    lib = _lib.get_lib()
+
+    def run():
         dx = torch.full((s, n, f), float("nan"), device=device)
-        lib = _lib.get_lib()
-        ran = ps.kernels_run(lambda: lib.call("eeg_dcrnn_diffuse_adj", ops._p(zd), ops._p(pd), pb, s, b, n, f, m, ops._p(dx), ops._stream(zd)))
-        slots = z.double().reshape(s, n, m, f)
-        want = slots[:, :, 0] + torch.einsum("smji,sjmf->sif", p64, slots[:, :, 1:])
-        ps.assert_close_scaled(dx.cpu().numpy(), want.numpy(), f"{name}: adjoint")
+        lib.call("eeg_dcrnn_diffuse_adj", ops._p(zd), ops._p(pd), pb, s, b, n, f, m, ops._p(dx), ops._stream(zd))
+        return dx
+    slots = z.double().reshape(s, n, m, f)
+    want = slots[:, :, 0] + torch.einsum("smji,sjmf->sif", p64, slots[:, :, 1:])
+    return run, want, "diffuse_adj"
+
+
+def check_diffuse_case(name, device):
+    c = DIFFUSE_CASES[name]
+    run, want, role = diffuse_call(name, device)
+    out = {}
+    ran = ps.kernels_run(lambda: out.update(res=run()))
+    if not c["adjoint"]:
+        ps.assert_close(out["res"].cpu().numpy(), want.numpy(), f"{name}: hop planes")
+    else:
+        ps.assert_close_scaled(out["res"].cpu().numpy(), want.numpy(), f"{name}: adjoint")
     assert ran == {role: {c["expect"]: c["launches"]}}, (name, ran)
 
 
-def check_corr_case(name, device):
+def corr_call(name, device):
+    """-> (call(): the operator call of a correlation case on `device` -> (adj, s1, s2), role, the host rows, valid steps per clip, width)"""
     c = CORR_CASES[name]
     b, n, lengths = c["b"], c["n"], c["lengths"]
     if c["kind"] == "gram":
@@ -257,9 +270,15 @@ def check_corr_case(name, device):
     else:
         call = (lambda: op.corr_graph_rows_len(xd, TOP_K, ln, steps)) if lengths else (lambda: op.corr_graph_rows(xd, TOP_K))
         role = "corr_gram_rows_len" if lengths else "corr_gram_rows"
+    return call, role, rows, valid, width
+
+
+def check_corr_case(name, device):
+    c = CORR_CASES[name]
+    call, role, rows, valid, width = corr_call(name, device)
     out = {}
     ran = ps.kernels_run(lambda: out.update(res=call()))
     adj, s1, s2 = (t.cpu().numpy() for t in out["res"])
-    for i in range(b):
+    for i in range(c["b"]):
         vs._graph_check(adj[i], s1[i], s2[i], rows[i][:, :valid[i] * width], TOP_K, (name, i))
     assert ran == {role: {c["expect"]: 1}, "corr_finish": {FINISH: 1}}, (name, ran)

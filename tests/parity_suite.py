@@ -230,11 +230,9 @@ def shared_laplacian(n, adj3d, g):
     return orc.compute_supports(a, "laplacian")[0]
 
 
-def check_spectral_form(device, adj3d, din=100, layers=2, t_len=3, b=4, classes=1, k=2, n=19, seed=0, lengths=None, act="tanh"):
-    """The spectral form of the hoisted x-part (csrc/spec_common.h): a model fed the ONE symmetric support in its shared (N,N) form
-    runs every layer in the eigenbasis of that support -- logits and all parameter gradients against the oracle (which diffuses hop
-    by hop on the batched form, cell.py:83-93) and against the general path of the same library (batched form of the same graph)."""
-    from eeg_gnn_ssl_amd import DCRNNModel_classification, ops
+def spectral_form_operands(adj3d, din=100, layers=2, t_len=3, b=4, classes=1, k=2, n=19, seed=0, lengths=None, act="tanh"):
+    """the model of check_spectral_form: configuration, parameters, the ONE symmetric support in its 2-D and its batched form, clips,
+    lengths and labels (host tensors)"""
     g = torch.Generator().manual_seed(seed)
     cfg = orc.DCRNNConfig(filter_type="laplacian", input_dim=din, rnn_units=64, num_rnn_layers=layers, num_classes=classes,
                           max_diffusion_step=k, num_nodes=n, dcgru_activation=act)
@@ -247,6 +245,34 @@ def check_spectral_form(device, adj3d, din=100, layers=2, t_len=3, b=4, classes=
     x = torch.randn(b, t_len, n, din, generator=g)
     seq = torch.tensor(lengths if lengths is not None else [t_len] * b, dtype=torch.int64)
     y = (torch.rand(b, generator=g) > 0.5).float() if classes == 1 else torch.randint(0, classes, (b,), generator=g)
+    return types.SimpleNamespace(cfg=cfg, params=params, s2=s2, supb=supb, x=x, seq=seq, y=y, classes=classes, layers=layers, k=k)
+
+
+def run_spectral_form(device, c, x=None):
+    """-> run(): one forward + backward of that model on `device`, fed the shared 2-D support (every layer in the eigenbasis) ->
+    (logits, {parameter name: gradient}).  x: other clips than c.x"""
+    from eeg_gnn_ssl_amd import DCRNNModel_classification, ops
+    model = DCRNNModel_classification(make_args(c.cfg), c.classes, device=device)
+    load(model, c.params, device)
+    xd, sd, yd, shared = (c.x if x is None else x).to(device), c.seq.to(device), c.y.to(device), [c.s2.to(device)]
+
+    def run():
+        model.zero_grad(set_to_none=True)
+        before = ops.spectral_layer_calls
+        lg = model(xd, sd, shared)
+        assert ops.spectral_layer_calls == before + c.layers, "every layer of the encoder takes the spectral form"
+        (torch.nn.functional.binary_cross_entropy_with_logits(lg.view(-1), yd) if c.classes == 1 else torch.nn.functional.cross_entropy(lg, yd)).backward()
+        return lg.detach().clone(), {name: p.grad.detach().clone() for name, p in model.named_parameters()}
+    return run
+
+
+def check_spectral_form(device, adj3d, din=100, layers=2, t_len=3, b=4, classes=1, k=2, n=19, seed=0, lengths=None, act="tanh"):
+    """The spectral form of the hoisted x-part (csrc/spec_common.h): a model fed the ONE symmetric support in its shared (N,N) form
+    runs every layer in the eigenbasis of that support -- logits and all parameter gradients against the oracle (which diffuses hop
+    by hop on the batched form, cell.py:83-93) and against the general path of the same library (batched form of the same graph)."""
+    from eeg_gnn_ssl_amd import DCRNNModel_classification, ops
+    c = spectral_form_operands(adj3d, din, layers, t_len, b, classes, k, n, seed, lengths, act)
+    cfg, params, s2, supb, x, seq, y = c.cfg, c.params, c.s2, c.supb, c.x, c.seq, c.y
     po = {name: v.clone().requires_grad_(True) for name, v in params.items()}
     lo = orc.classification_forward(po, cfg, x, seq, supb)
     (orc.bce_with_logits(lo, y) if classes == 1 else orc.cross_entropy(lo, y)).backward()

@@ -338,6 +338,7 @@ def run_layer(case, op, w, wsel, device):
             out = ops.dcgru_layer_ex(x, 0, h0d, p, p_batched, q["wg"], q["bg"], q["wc"], q["bc"], n, h, m, case["act"], lengths, basis=basis)
             hseq, hsel = out.hseq, out.hsel
         _loss(hseq, hsel if lengths is not None else None, wd, wseld).backward()
+        run.hsel = hsel.detach() if lengths is not None else None                         # (the state at each clip's last step, as returned)
         grads = dict(dX=x.grad.transpose(0, 1) if case["bm"] else x.grad, dWg=q["wg"].grad, dbg=q["bg"].grad, dWc=q["wc"].grad, dbc=q["bc"].grad)
         if h0d is not None:
             grads["dh0"] = h0d.grad

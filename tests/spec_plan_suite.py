@@ -173,6 +173,17 @@ def reachable_instances(exe, cus=256):
 
 
 # ---- the model under test -------------------------------------------------------------------------------------------------------
+SEED = 21
+
+
+def run_model(name, device, adj3d, x_scale=1.0):
+    """-> run(): one forward + backward of the case's model in the spectral form (operands of check_case; dev knobs are the caller's to
+    set) -> (logits, {parameter name: gradient}).  x_scale: the clips scaled"""
+    case = CASES[name]
+    c = ps.spectral_form_operands(adj3d, din=case["din"], layers=2, t_len=T_LEN, b=case["b"], classes=1, n=case["n"], seed=SEED)
+    return ps.run_spectral_form(device, c, c.x * x_scale if x_scale != 1.0 else None)
+
+
 def check_case(name, device, adj3d, exe, cus, set_knob=None):
     """One case: check_spectral_form with the recorder on; per role the spectral-family symbols recorded (the general-path comparison inside
     the check launches other kernels under some of the same roles) against the plan.  set_knob(key, value): sets a dev knob."""
@@ -185,7 +196,7 @@ def check_case(name, device, adj3d, exe, cus, set_knob=None):
             if value:
                 set_knob(key, value)
         ran = ps.kernels_run(lambda: ps.check_spectral_form(device, adj3d, din=case["din"], layers=2, t_len=T_LEN, b=case["b"], classes=1,
-                                                            n=case["n"], seed=21))
+                                                            n=case["n"], seed=SEED))
     finally:
         for key, value in zip(KNOB_KEYS, case["knobs"]):
             if value:
