@@ -9,6 +9,7 @@ from .device_data import (DeviceDataset, EpochSampler, RecordingDataset, clip_ta
                           clip_table_ssl, layout_recordings)
 from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
 from .interpret import OcclusionResult, occlusion_maps     # noqa: F401
+from .statistics import ScalerFit, fit_scaler     # noqa: F401
 from .model.cell import DCGRUCell, DiffusionGraphConv     # noqa: F401
 from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,   # noqa: F401
                           DCRNNModel_nextTimePred)
@@ -16,4 +17,4 @@ from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,
 __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
            "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "RecordingDataset", "clip_table_detection",
            "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "OcclusionResult",
-           "occlusion_maps", "ops", "utils"]
+           "occlusion_maps", "ScalerFit", "fit_scaler", "ops", "utils"]

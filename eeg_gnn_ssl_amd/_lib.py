@@ -119,6 +119,10 @@ _SIGNATURES = {
     "eeg_dcrnn_ssl_eval_scores": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_float, c_float, _FP, _FP,
                                           c_void_p]),
     "eeg_dcrnn_ssl_eval_metrics": (c_int, [_FP, c_int64, c_int64, _FP, c_void_p]),
+    # the fit of the input scaler: per-clip moments of the un-standardised inputs behind the gather, then the pool's float64 record
+    "eeg_dcrnn_moments_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "eeg_dcrnn_feature_moments": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, _FP, _FP, _FP, c_int, c_int, c_int64, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_moments_record": (c_int, [_FP, c_int64, _FP, c_void_p]),
     # occlusion maps: the B*G variants of one window (inputs, initial states, lengths), then their scores; `hext` is a host pointer table
     "eeg_dcrnn_occlude_expand": (c_int, [_FP, POINTER(c_void_p), c_int, _FP, _FP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                          _FP, _FP, _FP, c_void_p]),

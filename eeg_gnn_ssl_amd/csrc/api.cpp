@@ -16,6 +16,7 @@
 #include "diffuse_launch.h"
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
+#include "kernels_moments.h"
 #include "kernels_occlude.h"
 #include "kernels_data.h"
 #include "kernels_records.h"
@@ -1331,6 +1332,65 @@ int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, doubl
     EEG_LAUNCH_P("ssl_eval_metrics", ssl_eval_metrics_kernel, dim3(1), dim3(kSslEvalThreads), kSslEvalThreads * sizeof(double), S_(stream), scores, (int)P,
                  (int)(G < P ? G : P), record);
     return check_launch("ssl_eval_metrics");
+}
+
+/* ---- the fit of the input scaler: per-clip moments of the un-standardised inputs, the pool's record ----- */
+static_assert(EEG_MOMENTS_RECORD_WORDS == kMomRecordWords && EEG_MOMENTS_MAX_BATCH == kMomMaxBatch, "include/eeg_dcrnn.h and kernels_moments.h disagree");
+// the checks the size query and the launch share; `what` names the entry point in refusals
+static int moments_shape(const char* what, int B, int N, int T, int W, int kind) {
+    if (B < 1 || N < 1 || T < 1) return fail("%s: empty input (B=%d, N=%d, T=%d)", what, B, N, T);
+    if (B > kMomMaxBatch) return fail("%s: B=%d clips exceed one launch (limit %d)", what, B, kMomMaxBatch);
+    if (kind != 0 && kind != 1) return fail("%s: kind=%d (0: log|FFT| features, 1: the values as given)", what, kind);
+    if (W < 4 || W % 4 != 0) return fail("%s: window=%d unsupported (a positive multiple of 4)", what, W);
+    if (kind == 0 && W / 4 + 1 > 64) return fail("%s: window=%d unsupported for kind=0 (multiple of 4, <= 252)", what, W);
+    if ((long long)N * T * W >= kMomMaxClipElems) return fail("%s: a clip of %lld elements unsupported (below 2^31)", what, (long long)N * T * W);
+    return 0;
+}
+size_t eeg_dcrnn_moments_ws_bytes(int B, int N, int T, int W, int kind) {
+    if (moments_shape("moments_ws_bytes", B, N, T, W, kind)) return 0;
+    return (size_t)B * (size_t)moments_chunks(N, T, W, kind) * 4 * sizeof(double);
+}
+int eeg_dcrnn_feature_moments(const float* raw, int B, int N, int T, int W, int kind, const int64_t* lengths, const float* clip_w,
+                              const int64_t* cursor, int rank, int world, int64_t P, void* ws, double* scores, void* stream) {
+    if (raw == nullptr) return fail("feature_moments: null raw");
+    if (scores == nullptr || ws == nullptr) return fail("feature_moments: null scores / ws (eeg_dcrnn_moments_ws_bytes)");
+    if (moments_shape("feature_moments", B, N, T, W, kind)) return 1;
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("feature_moments: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (world < 1 || rank < 0 || rank >= world) return fail("feature_moments: rank=%d of world=%d", rank, world);
+    if (((uintptr_t)raw & 15) != 0) return fail("feature_moments: raw must be 16-byte aligned");
+    if (((uintptr_t)clip_w & 3) != 0 || (((uintptr_t)lengths | (uintptr_t)cursor | (uintptr_t)scores | (uintptr_t)ws) & 7) != 0)
+        return fail("feature_moments: lengths / clip_w / cursor / scores / ws must be aligned to their element size");
+    hipStream_t st = S_(stream);
+    const long long* len = reinterpret_cast<const long long*>(lengths);
+    const long long* cur = reinterpret_cast<const long long*>(cursor);
+    const long long step = (long long)B * world, slot0 = (long long)rank * B;
+    const int chunks = (int)moments_chunks(N, T, W, kind);
+    double* part = static_cast<double*>(ws);
+    const dim3 grid((unsigned)chunks, (unsigned)B);
+    if (kind != 0) {
+        EEG_LAUNCH_P("feature_moments", moments_values_kernel, grid, dim3(kMomThreads), kMomThreads * sizeof(double), st, raw, (unsigned)N,
+                     (unsigned)(T * (W / 4)), (unsigned)(W / 4), T, len, clip_w, cur, step, slot0, (long long)P, part);
+    } else if (W == kFftWin) {
+        const size_t lds = 4 * (size_t)kFftWaveDoubles * sizeof(double);
+        EEG_SET_MAX_LDS(moments_fft200_kernel, lds);
+        EEG_LAUNCH_P("feature_moments", moments_fft200_kernel, grid, dim3(kMomThreads), lds, st, raw, N, T, len, clip_w, cur, step, slot0, (long long)P,
+                     part);
+    } else {
+        const size_t lds = (size_t)std::max(4 * W, kMomThreads) * sizeof(double);
+        EEG_LAUNCH_P("feature_moments", moments_dft_kernel, grid, dim3(kMomThreads), lds, st, raw, N, T, W, len, clip_w, cur, step, slot0, (long long)P,
+                     part);
+    }
+    if (int rc = check_launch("feature_moments")) return rc;
+    EEG_LAUNCH_P("feature_moments_fold", moments_fold_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, st, part, chunks, clip_w, cur, step, slot0,
+                 (long long)P, B, scores);
+    return check_launch("feature_moments_fold");
+}
+int eeg_dcrnn_moments_record(const double* scores, int64_t P, double* record, void* stream) {
+    if (scores == nullptr || record == nullptr) return fail("moments_record: null scores / record");
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("moments_record: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if ((((uintptr_t)scores | (uintptr_t)record) & 7) != 0) return fail("moments_record: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("moments_record", moments_record_kernel, dim3(1), dim3(kMomThreads), kMomThreads * sizeof(double), S_(stream), scores, (int)P, record);
+    return check_launch("moments_record");
 }
 
 /* ---- occlusion maps: the variants of one window, their scores ------------------------------------- */

@@ -23,6 +23,30 @@ __device__ __forceinline__ int perm_source(const int* __restrict__ perm, int b, 
     return (unsigned)s < (unsigned)N ? s : nd;
 }
 
+// The window body of the direct DFT, shared by the storing kernel below and the reducing kernel of kernels_moments.h (the same
+// instructions on the same operands: both see the same values).  xs: the W samples of the window as doubles (LDS, wave-private);
+// lane k <= W/4 owns the frequency pair (k, W/2 - k), (c1, s1) = (cos, sin) of 2 pi k / W; emit(bin, log amplitude) is called for
+// the lane's one or two bins.
+template <class Emit>
+__device__ __forceinline__ void dft_window(const double* xs, int W, int lane, double c1, double s1, Emit&& emit) {
+    const int H2 = W / 2;
+    double ec = 0.0, es = 0.0, oc = 0.0, os = 0.0, c = 1.0, s = 0.0;
+    for (int n = 0; n < W; n += 2) {
+        const double x0 = xs[n], x1 = xs[n + 1];
+        ec = fma(x0, c, ec); es = fma(x0, s, es);
+        double cn = c * c1 - s * s1, sn = s * c1 + c * s1;
+        oc = fma(x1, cn, oc); os = fma(x1, sn, os);
+        c = cn * c1 - sn * s1; s = sn * c1 + cn * s1;
+    }
+    auto bin = [&](int k, double re, double im) {
+        double amp = sqrt(re * re + im * im);
+        if (amp == 0.0) amp = 1e-8;                // computeFFT: avoid log of 0
+        emit(k, log(amp));
+    };
+    if (lane < H2) bin(lane, ec + oc, es + os);
+    if (lane > 0 && H2 - lane > lane && H2 - lane < H2) bin(H2 - lane, ec - oc, es - os);
+}
+
 // LEN (variable-length clips, dataloader_classification.py:25-85,321-343: a clip has curr_len <= max_seq_len steps, is augmented and
 // standardised as it is and THEN padded with padding_val): clip b has clip_steps(lengths, b, T) valid windows; a window behind them is
 // not transformed -- its feat_std row is pad_val (the padding behind the scaler), its feat_raw row 0 (adds nothing to a Gram).
@@ -59,25 +83,12 @@ __global__ __launch_bounds__(64) void fft_features_kernel(const float* __restric
         for (int i = lane; i < W; i += 64) xs[i] = (double)sig[(size_t)t * W + i];
         EEG_WAVE_SYNC();
         if (active) {
-            double ec = 0.0, es = 0.0, oc = 0.0, os = 0.0, c = 1.0, s = 0.0;
-            for (int n = 0; n < W; n += 2) {
-                const double x0 = xs[n], x1 = xs[n + 1];
-                ec = fma(x0, c, ec); es = fma(x0, s, es);
-                double cn = c * c1 - s * s1, sn = s * c1 + c * s1;
-                oc = fma(x1, cn, oc); os = fma(x1, sn, os);
-                c = cn * c1 - sn * s1; s = sn * c1 + cn * s1;
-            }
             // the un-augmented features stay at the source channel (perm is a permutation: every slot is written once)
             const size_t o_raw = (((size_t)b * T + t) * N + src) * H2, o_std = (((size_t)b * T + t) * N + nd) * H2;
-            auto emit = [&](int k, double re, double im) {
-                double amp = sqrt(re * re + im * im);
-                if (amp == 0.0) amp = 1e-8;                // computeFFT: avoid log of 0
-                const double v = log(amp);
+            dft_window(xs, W, lane, c1, s1, [&](int k, double v) {
                 if (feat_raw != nullptr) feat_raw[o_raw + k] = (float)v;
                 if (feat_std != nullptr) feat_std[o_std + k] = (float)(((v + ls) - (double)mean) * (double)inv_std);
-            };
-            if (lane < H2) emit(lane, ec + oc, es + os);
-            if (lane > 0 && H2 - lane > lane && H2 - lane < H2) emit(H2 - lane, ec - oc, es - os);
+            });
         }
     }
 }
@@ -164,6 +175,59 @@ __device__ __forceinline__ void fft200_store_pad(int N, const int* __restrict__ 
     if (feat_std != nullptr) *reinterpret_cast<f32x4*>(feat_std + (size_t)wj * kFftBins + pos) = f32x4{pad_val, pad_val, pad_val, pad_val};
 }
 
+// The transform of the wave's six windows, shared by the storing item below and the reducing kernel of kernels_moments.h (the same
+// instructions on the same operands: both see the same values).  Lane (w, q) of a LIVE window reads its samples at sig_of() (the
+// 200 floats of the window; called by live lanes only) and leaves with v[k2] = the float32 log amplitude of bin q + 10 k2; the ten
+// lanes of a window that is not live sit the transform out.  tile: the wave's kFftWaveDoubles doubles of LDS; the caller syncs the
+// wave before it reuses them.
+template <class Sig>
+__device__ __forceinline__ void fft200_windows(Sig&& sig_of, bool live, int w, int q, cplx* tile, const cplx (&tw1)[10], const cplx (&tw2)[10],
+                                               double log_floor, float (&v)[10]) {
+    cplx a[10], A[10];
+    if (live) {
+        const float* sig = sig_of();
+#pragma unroll
+        for (int n1 = 0; n1 < 10; ++n1) {
+            const f32x2 z = *reinterpret_cast<const f32x2*>(sig + 20 * n1 + 2 * q);        // z[10 n1 + q]
+            a[n1] = {(double)z[0], (double)z[1]};
+        }
+        dft10(a, A);                                                 // over n1 -> k1
+#pragma unroll
+        for (int k1 = 0; k1 < 10; ++k1) tile[(w * 10 + q) * kFftRow + k1] = cmul(A[k1], tw1[k1]);
+    }
+    EEG_WAVE_SYNC();
+    if (live) {
+#pragma unroll
+        for (int n2 = 0; n2 < 10; ++n2) a[n2] = tile[(w * 10 + n2) * kFftRow + q];
+        dft10(a, A);                                                 // over n2 -> k2: A[k2] = Z[q + 10 k2]
+    }
+    EEG_WAVE_SYNC();
+    if (live) {
+#pragma unroll
+        for (int k2 = 0; k2 < 10; ++k2) tile[w * 110 + q + 10 * k2] = A[k2];              // Z[k] at [w][k]
+    }
+    EEG_WAVE_SYNC();
+    if (live) {
+#pragma unroll
+        for (int k2 = 0; k2 < 10; ++k2) {
+            const int k = q + 10 * k2;
+            const cplx zp = tile[w * 110 + (k == 0 ? 0 : 100 - k)];
+            const double ar = A[k2].re + zp.re, ai = A[k2].im - zp.im;                    // Z[k] + conj Z[100-k]
+            const double br = A[k2].re - zp.re, bi = A[k2].im + zp.im;                    // Z[k] - conj Z[100-k]
+            const double xr = ar + (tw2[k2].re * bi - tw2[k2].im * br);
+            const double xi = ai - (tw2[k2].re * br + tw2[k2].im * bi);
+            const double pw = 0.25 * (xr * xr + xi * xi);
+            // log|X| = ln2/2 * (e + log2 m), |X|^2 = m 2^e with m in [0.5, 1): the exponent split is exact in fp64, the mantissa's
+            // log2 is one v_log_f32 (absolute error ~1e-7 on a value in (-1, 0]) and the two parts are combined in fp64 -- the fp64
+            // library log (~70 fp64 instructions per bin) was 60 % of this kernel's instructions
+            int ex;
+            const double mant = frexp(pw, &ex);
+            const double lg = 0.34657359027997264 * ((double)ex + (double)fast_log2((float)mant));
+            v[k2] = (float)(pw == 0.0 ? log_floor : lg);
+        }
+    }
+}
+
 // One item = 6 consecutive (b, t, node) windows of ONE (B, N, T*200) buffer, transformed by one wave (the body shared by the
 // single-buffer and the paired kernel: the same instructions on the same operands, so both give the same bits).
 // LEN: windows (b, t >= clip_steps(lengths, b, T)) are padding (see fft_features_kernel).  `vmask` = the valid windows of the item, the
@@ -202,54 +266,15 @@ __device__ __forceinline__ void fft200_item(const float* __restrict__ raw, int N
         }
     }
     const bool live = active && wg < n_windows && (!LEN || ((vmask >> w) & 1u) != 0u);
-    cplx a[10], A[10];
-    if (live) {
+    auto sig_of = [&]() {
         const int nd = (int)(wg % N);
         const long long bt = wg / N;
         const int t = (int)(bt % T), b = (int)(bt / T);
         const int src = perm_source(perm, b, N, nd);     // EEG_seq_reflect[:, pair] = EEG_seq[:, swapped pair]
-        const float* sig = raw + (((size_t)b * N + src) * T + t) * kFftWin;
-#pragma unroll
-        for (int n1 = 0; n1 < 10; ++n1) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(sig + 20 * n1 + 2 * q);        // z[10 n1 + q]
-            a[n1] = {(double)v[0], (double)v[1]};
-        }
-        dft10(a, A);                                                 // over n1 -> k1
-#pragma unroll
-        for (int k1 = 0; k1 < 10; ++k1) tile[(w * 10 + q) * kFftRow + k1] = cmul(A[k1], tw1[k1]);
-    }
-    EEG_WAVE_SYNC();
-    if (live) {
-#pragma unroll
-        for (int n2 = 0; n2 < 10; ++n2) a[n2] = tile[(w * 10 + n2) * kFftRow + q];
-        dft10(a, A);                                                 // over n2 -> k2: A[k2] = Z[q + 10 k2]
-    }
-    EEG_WAVE_SYNC();
-    if (live) {
-#pragma unroll
-        for (int k2 = 0; k2 < 10; ++k2) tile[w * 110 + q + 10 * k2] = A[k2];              // Z[k] at [w][k]
-    }
-    EEG_WAVE_SYNC();
+        return raw + (((size_t)b * N + src) * T + t) * kFftWin;
+    };
     float v[10];
-    if (live) {
-#pragma unroll
-        for (int k2 = 0; k2 < 10; ++k2) {
-            const int k = q + 10 * k2;
-            const cplx zp = tile[w * 110 + (k == 0 ? 0 : 100 - k)];
-            const double ar = A[k2].re + zp.re, ai = A[k2].im - zp.im;                    // Z[k] + conj Z[100-k]
-            const double br = A[k2].re - zp.re, bi = A[k2].im + zp.im;                    // Z[k] - conj Z[100-k]
-            const double xr = ar + (tw2[k2].re * bi - tw2[k2].im * br);
-            const double xi = ai - (tw2[k2].re * br + tw2[k2].im * bi);
-            const double pw = 0.25 * (xr * xr + xi * xi);
-            // log|X| = ln2/2 * (e + log2 m), |X|^2 = m 2^e with m in [0.5, 1): the exponent split is exact in fp64, the mantissa's
-            // log2 is one v_log_f32 (absolute error ~1e-7 on a value in (-1, 0]) and the two parts are combined in fp64 -- the fp64
-            // library log (~70 fp64 instructions per bin) was 60 % of this kernel's instructions
-            int ex;
-            const double mant = frexp(pw, &ex);
-            const double lg = 0.34657359027997264 * ((double)ex + (double)fast_log2((float)mant));
-            v[k2] = (float)(pw == 0.0 ? log_floor : lg);
-        }
-    }
+    fft200_windows(sig_of, live, w, q, tile, tw1, tw2, log_floor, v);
     EEG_WAVE_SYNC();                                                 // every partner read is done: the tile becomes the output tile
     if (live) {
 #pragma unroll

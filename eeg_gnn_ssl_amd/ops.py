@@ -13,7 +13,7 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    occlude_expand, occlusion_scores.
+    feature_moments, moments_record, occlude_expand, occlusion_scores.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1606,8 +1606,115 @@ _define("ssl_eval_scores", "(Tensor pred, Tensor target, Tensor clip_w, Tensor c
 _define("ssl_eval_metrics", "(Tensor scores, int group, Tensor(a!) record) -> ()", _ssl_eval_metrics_impl, lambda *a: None)
 
 
+# ---- the fit of the input scaler on the device (statistics.py: fit_scaler; csrc/kernels_moments.h) ---------------------------------
+MOMENTS_RECORD_WORDS = 7              # EEG_MOMENTS_RECORD_WORDS: float64 words of the pool's record
+MOMENTS_RECORD = ("clips", "count", "sum", "sumsq", "mean", "std", "bad")
+MOMENTS_MAX_BATCH = 65535             # EEG_MOMENTS_MAX_BATCH
+MOMENTS_MAX_CLIP_ELEMS = 1 << 31      # a clip holds fewer elements than this
+
+
+def _moments_tensor(what, name, t, dtype, shape, dev):
+    """the operands of the moments operators are read / written ON THE DEVICE as they are: no conversion, anything else is refused"""
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {got}")
+
+
+def _moments_pool(what, scores):
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[0] != 4 or scores.shape[1] < 1 or scores.dtype != torch.float64 or \
+            not scores.is_contiguous():
+        got = f"{scores.dtype} {tuple(scores.shape)}" if torch.is_tensor(scores) else type(scores).__name__
+        raise ValueError(f"{what}: scores must be a contiguous (4, P) float64 tensor (sum | sumsq | count | bad; ops.moments_buffers), got {got}")
+    p = int(scores.shape[1])
+    if p > EVAL_MAX_CLIPS:
+        raise ValueError(f"{what}: P={p} clips exceed the limit of one pass, {EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    return p
+
+
+def _moments_shape(raw, window: int, use_fft: bool):
+    """(N, T, W, kind) of the C call for a batch `raw`: raw signals (B, N, T*window), or ready features / windows (B, T, N, D) with
+    window = 0 -- always the values as given, read as one row of T steps of N*D values per clip"""
+    what = "feature_moments"
+    if not torch.is_tensor(raw) or raw.dtype != torch.float32 or raw.dim() not in (3, 4) or raw.numel() == 0:
+        got = f"{raw.dtype} {tuple(raw.shape)}" if torch.is_tensor(raw) else type(raw).__name__
+        raise ValueError(f"{what}: raw must be float32 raw signals (B, N, T*window) or features / windows (B, T, N, D), got {got}")
+    if not raw.is_contiguous():
+        raise ValueError(f"{what}: raw {tuple(raw.shape)} must be contiguous (the clips are read in place)")
+    if raw.dim() == 4:
+        if window:
+            raise ValueError(f"{what}: raw {tuple(raw.shape)} holds features / windows (B, T, N, D), taken as given: window={window} has no "
+                             f"meaning there (raw signals are (B, N, T*window))")
+        n, t, w, kind = 1, int(raw.shape[1]), int(raw.shape[2] * raw.shape[3]), 1
+        if w % 4 != 0:
+            raise ValueError(f"{what}: a step of {tuple(raw.shape[2:])} = {w} values is no whole number of 16-byte pieces (N*D % 4 == 0)")
+    else:
+        w, kind = int(window), 0 if use_fft else 1
+        if w < 4 or w % 4 != 0:
+            raise ValueError(f"{what}: window={window} unsupported (a positive multiple of 4)")
+        if kind == 0 and w // 4 + 1 > 64:
+            raise ValueError(f"{what}: window={window} unsupported with use_fft=True (a multiple of 4, at most 252)")
+        if raw.shape[2] % w != 0:
+            raise ValueError(f"{what}: raw {tuple(raw.shape)} is no whole number of steps of window={w} samples per channel")
+        n, t = int(raw.shape[1]), int(raw.shape[2]) // w
+    if raw[0].numel() >= MOMENTS_MAX_CLIP_ELEMS:
+        raise ValueError(f"{what}: a clip of {raw[0].numel()} elements; at most {MOMENTS_MAX_CLIP_ELEMS - 1}")
+    if raw.shape[0] > MOMENTS_MAX_BATCH:
+        raise ValueError(f"{what}: B={raw.shape[0]} clips exceed one launch (EEG_MOMENTS_MAX_BATCH = {MOMENTS_MAX_BATCH})")
+    if raw.data_ptr() % 16:
+        raise ValueError(f"{what}: raw is not 16-byte aligned (a view with an odd element offset): pass a tensor of its own")
+    return n, t, w, kind
+
+
+def _feature_moments_impl(raw, lengths, clip_w, cursor, rank: int, world: int, window: int, use_fft: bool, scores) -> None:
+    lib = _lib.get_lib()
+    p = _moments_pool("feature_moments", scores)
+    n, t, w, kind = _moments_shape(raw, window, use_fft)
+    dev, b = scores.device, int(raw.shape[0])
+    if lib.is_device_build and not scores.is_cuda:
+        raise ValueError(f"feature_moments: scores is on {dev}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    if raw.device != dev:
+        raise ValueError(f"feature_moments: raw is on {raw.device}, scores on {dev}: one device")
+    if lengths is not None:
+        _moments_tensor("feature_moments", "lengths", lengths, torch.int64, (b,), dev)
+    if clip_w is not None:
+        _moments_tensor("feature_moments", "clip_w", clip_w, torch.float32, (b,), dev)
+    if cursor is not None:
+        _moments_tensor("feature_moments", "cursor", cursor, torch.int64, (1,), dev)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"feature_moments: rank={rank} of world={world}")
+    nbytes = int(lib.query("eeg_dcrnn_moments_ws_bytes", b, n, t, w, kind))
+    if nbytes == 0:
+        raise ValueError(f"feature_moments: {lib.last_error()}")
+    ws = _new((nbytes // 8,), scores, torch.float64)                   # the chunks' partial words: every word read is written first
+    lib.call("eeg_dcrnn_feature_moments", _p(raw), b, n, t, w, kind, _p(lengths), _p(clip_w), _p(cursor), int(rank), int(world), p, _p(ws),
+             _p(scores), _stream(scores))
+
+
+def moments_buffers(num_clips: int, device):
+    """(scores, record) of a scaler fit over `num_clips` clips: the (4, P) float64 per-clip buffer (sum | sumsq | count | bad, zeroed)
+    and the float64 record of MOMENTS_RECORD_WORDS words; allocated once by the caller (`statistics.fit_scaler`)"""
+    if not 1 <= int(num_clips) <= EVAL_MAX_CLIPS:
+        raise ValueError(f"moments_buffers: P={num_clips} clips outside 1..{EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    return (torch.zeros(4, int(num_clips), dtype=torch.float64, device=device),
+            torch.zeros(MOMENTS_RECORD_WORDS, dtype=torch.float64, device=device))
+
+
+def _moments_record_impl(scores, record) -> None:
+    lib = _lib.get_lib()
+    p = _moments_pool("moments_record", scores)
+    if lib.is_device_build and not scores.is_cuda:
+        raise ValueError(f"moments_record: scores is on {scores.device}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    _moments_tensor("moments_record", "record", record, torch.float64, (MOMENTS_RECORD_WORDS,), scores.device)
+    lib.call("eeg_dcrnn_moments_record", _p(scores), p, _p(record), _stream(scores))
+
+
+_define("feature_moments", "(Tensor raw, Tensor? lengths, Tensor? clip_w, Tensor? cursor, int rank, int world, int window, bool use_fft, "
+        "Tensor(a!) scores) -> ()", _feature_moments_impl, lambda *a: None)
+_define("moments_record", "(Tensor scores, Tensor(a!) record) -> ()", _moments_record_impl, lambda *a: None)
+
+
 # ---- occlusion maps on the device (interpret.py: occlusion_maps) -------------------------------------------------------------------
-OCCLUDE_MAX_LAYERS = 4        # EEG_OCCLUDE_MAX_LAYERS
+OCCLUDE_MAX_LAYERS = 4       # EEG_OCCLUDE_MAX_LAYERS
 OCCLUDE_MAX_GROUPS = 64       # EEG_OCCLUDE_MAX_GROUPS
 
 
@@ -2530,6 +2637,36 @@ def ssl_eval_metrics(scores, group: int, record=None):
     if record is None:
         record = torch.zeros(SSL_EVAL_RECORD_WORDS, dtype=torch.float64, device=scores.device)
     torch.ops.eeg_dcrnn.ssl_eval_metrics(scores, int(group), record)
+    return record
+
+
+def feature_moments(raw, scores, clip_w, cursor, rank: int = 0, world: int = 1, *, window: Optional[int] = None, use_fft: bool = True, lengths=None):
+    """Per-clip moments of the UN-standardised model inputs of a gathered batch, one step of a scaler fit (`statistics.fit_scaler`).
+    raw: raw signals (B, N, T*window) -- use_fft=True: the values are the float32 log|FFT| features `fft_features` returns as
+    feat_raw for the batch, bit for bit and never stored (window % 4 == 0, at most 252; 200: the mixed-radix transform); use_fft=
+    False: the samples themselves -- or ready features / windows (B, T, N, D) with window=None, always taken as given.  lengths:
+    None or int64 (B,) on the device: clip b counts its first clamp(lengths[b], 1, T) steps only.  scores: (4, P) float64 (sum |
+    sumsq | count | bad; `moments_buffers`): slot b is pool position cursor - B*world + rank*B + b and writes its four words there
+    only if clip_w[b] != 0 and 0 <= position < P (clip_w None: every slot counts; cursor None: position rank*B + b).  A NaN or
+    infinite value is counted in bad and left out of the sums.  No floating-point atomics; a clip's words have the same bits whatever
+    B, slot, rank, cursor and length.  Operands that do not fit raise ValueError before any launch.  Returns scores; no host sync."""
+    for name, t in (("raw", raw), ("lengths", lengths), ("clip_w", clip_w), ("cursor", cursor)):      # (the dispatcher would route a stray
+        if torch.is_tensor(t) and torch.is_tensor(scores) and t.device != scores.device:               # device by its own rules)
+            raise ValueError(f"feature_moments: {name} is on {t.device}, scores on {scores.device}: one device")
+    torch.ops.eeg_dcrnn.feature_moments(raw, lengths, clip_w, cursor, int(rank), int(world), 0 if window is None else int(window), bool(use_fft),
+                                        scores)
+    return scores
+
+
+def moments_record(scores, record=None):
+    """The record of a scaler fit from its (4, P) scores, on the device, as MOMENTS_RECORD_WORDS float64 words named by
+    MOMENTS_RECORD: clips (positions with count > 0), count, sum, sumsq, mean = sum / count, std = sqrt(sumsq / count - mean^2)
+    (the population std, np.std), bad.  A variance at or below 2^-50 * sumsq lies inside the rounding of the sums (negative values
+    among them) and gives std = 0: a pool of equal values reports 0, not noise.  count == 0: mean = std = 0.  One block, an order
+    that depends on P alone.  record: `moments_buffers` (allocated here when not given).  Returns record; no host sync."""
+    if record is None:
+        record = torch.zeros(MOMENTS_RECORD_WORDS, dtype=torch.float64, device=scores.device if torch.is_tensor(scores) else None)
+    torch.ops.eeg_dcrnn.moments_record(scores, record)
     return record
 
 

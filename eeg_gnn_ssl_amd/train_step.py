@@ -611,6 +611,30 @@ class TrainStep:
         return DeviceSSLEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world, keep_predictions=keep_predictions,
                                   loss_batch=loss_batch)
 
+    def fit_scaler(self, dataset, batch_size: int = 256):
+        """Fit this step's input scaler on the device (`statistics.fit_scaler`): the mean and std of the un-standardised inputs the
+        step's raw chain produces for `dataset` -- log|FFT| features, or with use_fft=False the samples -- over its clips (valid steps
+        only, of an SSL data set the input half), on the process group's ranks.  Sets `raw_mean` / `raw_std` and returns the
+        `ScalerFit`.  Before any capture: a captured graph holds the scaler as kernel arguments.  A step without raw_window takes
+        features that are already standardised: there is nothing to fit."""
+        from .statistics import fit_scaler
+        if self.raw_window is None:
+            raise ValueError("TrainStep.fit_scaler: the step has raw_window=None: its inputs are features / windows taken as already "
+                             "standardised; fit a pool of un-standardised features with eeg_gnn_ssl_amd.fit_scaler(dataset)")
+        if self._graphs:
+            raise ValueError(f"TrainStep.fit_scaler: {len(self._graphs)} graph(s) captured: raw_mean / raw_std are kernel arguments baked into "
+                             f"them; fit the scaler in front of capture / capture_epoch")
+        dataset.check_step(self, "TrainStep.fit_scaler")
+        dev = self.fp.flat.device
+        if dataset.device != dev:
+            raise ValueError(f"TrainStep.fit_scaler: dataset on {dataset.device}, model on {dev}: one device")
+        if len(dataset.x_shape) != 2:
+            raise ValueError(f"TrainStep.fit_scaler: TrainStep(raw_window={self.raw_window}) takes raw signals (P, N, T*{self.raw_window}), the "
+                             f"pool holds {(len(dataset),) + tuple(dataset.x_shape)}")
+        fit = fit_scaler(dataset, batch_size, window=int(self.raw_window), use_fft=self.use_fft)
+        self.raw_mean, self.raw_std = fit.mean, fit.std
+        return fit
+
     def occlusion_maps(self, x, seq_lengths, supports=None, **kw):
         """occlusion maps (`interpret.occlusion_maps`) of this step's model on the inputs of an evaluation step: x as the step takes
         it (features, windows or raw signals) goes through the data chain WITHOUT augmentation draws -- with supports=None the

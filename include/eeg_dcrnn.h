@@ -469,6 +469,34 @@ int eeg_dcrnn_ssl_eval_scores(const float* pred, const float* target, const floa
                               void* stream);
 int eeg_dcrnn_ssl_eval_metrics(const double* scores, int64_t P, int64_t G, double* record, void* stream);
 
+/* The fit of the input scaler on the device: the scalar mean and std of the UN-standardised model inputs over a pool of P clips (the
+ * reference's StandardScaler, whose two numbers it reads from files made offline), without writing the inputs.
+ *
+ * eeg_dcrnn_feature_moments: one call behind the gather of every step of a pass over the pool in order.  raw: the gathered batch
+ * (B, N, T*W) float32, 16-byte aligned.  kind 0: the values of clip b are the float32 numbers eeg_dcrnn_fft_features writes to
+ * feat_raw for it without augmentation (W % 4 == 0, W/4 + 1 <= 64; W = 200: the mixed-radix transform, else the direct DFT), bit
+ * for bit, never stored.  kind 1: the float32 samples as given (W % 4 == 0) -- the time-domain windows; ready features (B, T, N, D)
+ * go in as N = 1, W = N*D.  lengths: null, or int64 (B): clip b counts its first clamp(lengths[b], 1, T) steps only.  scores is
+ * (4, P) float64: sum | sumsq | count | bad of the clip at each pool position: every finite value v adds (double)v and
+ * (double)v * (double)v and 1 to count, a NaN or infinite value 1 to bad.  Slot arithmetic and bound of eeg_dcrnn_ssl_eval_scores
+ * (unsigned: pos = cursor[0] - B*world + rank*B + b; a slot writes only if clip_w[b] != 0 AND 0 <= pos < P; clip_w null: every slot
+ * counts; cursor null: pos = rank*B + b); nothing is written outside scores and ws.  No floating-point atomics: fixed per-thread
+ * order, a fixed tree per workgroup, the chunks of a clip added in chunk order from ws (eeg_dcrnn_moments_ws_bytes(B, N, T, W, kind)
+ * bytes, 8-byte aligned; 0: the shape is refused).  The partition depends on (N, T, W, kind) alone: a clip's four words have the same
+ * bits whatever B, slot, rank, cursor and length.  B <= EEG_MOMENTS_MAX_BATCH, N*T*W < 2^31, P <= EEG_EVAL_MAX_CLIPS.
+ *
+ * eeg_dcrnn_moments_record: the pool's record from scores, EEG_MOMENTS_RECORD_WORDS float64 words in device memory, one block, an
+ * order that depends on P alone: 0 clips = positions with count > 0, 1 count, 2 sum, 3 sumsq, 4 mean = sum / count, 5 std =
+ * sqrt(sumsq / count - mean^2) (the population std; every operation rounded on its own), 0 where that variance is at or below
+ * 2^-50 * sumsq -- inside the rounding of the sums, negative values among them: a pool of equal values reports std = 0 --, 6 bad;
+ * count == 0: mean = std = 0.  No allocation, no host synchronisation. */
+#define EEG_MOMENTS_RECORD_WORDS 7
+#define EEG_MOMENTS_MAX_BATCH 65535
+size_t eeg_dcrnn_moments_ws_bytes(int B, int N, int T, int W, int kind);
+int eeg_dcrnn_feature_moments(const float* raw, int B, int N, int T, int W, int kind, const int64_t* lengths, const float* clip_w,
+                              const int64_t* cursor, int rank, int world, int64_t P, void* ws, double* scores, void* stream);
+int eeg_dcrnn_moments_record(const double* scores, int64_t P, double* record, void* stream);
+
 /* Occlusion maps on the device: group g of channels of clip b is overwritten with `fill` over the window of steps [t0, t0 + w) and the
  * map records how far the predicted probability drops.  All variants of a window start from the unoccluded clip's state at t0.
  *
