@@ -5,7 +5,7 @@ Drop-in for the DCRNN hot path of tsy935/eeg-gnn-ssl (model/cell.py, model/model
 gfx950 behind a C ABI (include/eeg_dcrnn.h). 
 """
 from . import ops, utils                                  # noqa: F401
-from .device_data import (DeviceDataset, EpochSampler, RecordingDataset, clip_table_classification, clip_table_detection,      # noqa: F401
+from .device_data import (BalancedEpochSampler, DeviceDataset, EpochSampler, RecordingDataset, clip_table_classification, clip_table_detection,      # noqa: F401
                           clip_table_ssl, layout_recordings)
 from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
 from .interpret import OcclusionResult, occlusion_maps     # noqa: F401
@@ -15,6 +15,6 @@ from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,
                           DCRNNModel_nextTimePred)
 
 __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
-           "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "RecordingDataset", "clip_table_detection",
+           "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "BalancedEpochSampler", "RecordingDataset", "clip_table_detection",
            "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "OcclusionResult",
            "occlusion_maps", "ScalerFit", "fit_scaler", "ops", "utils"]

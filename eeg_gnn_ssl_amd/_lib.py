@@ -111,6 +111,14 @@ _SIGNATURES = {
     "eeg_dcrnn_ce_logits_w": (c_int, [_FP, _FP, c_int, c_int, _FP, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_masked_loss_w": (c_int, [_FP, _FP, c_size_t, c_int, _FP, _FP, c_int, c_float, c_float, c_float, c_int, _FP, _FP, _FP, c_void_p]),
     "eeg_dcrnn_teacher_flags_dev": (c_int, [_FP, _FP, _FP, ctypes.c_double, c_int, _FP, c_void_p]),
+    # class / sample weights: the criteria with a per-clip multiplier (clip_u float[B], denom float[1], device memory) and the launch
+    # that writes the two from the labels (sampler form: label pool, perm, cursor; batch form: the batch's labels)
+    "eeg_dcrnn_cls_head_loss_cw": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_int, c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                           _FP, _FP, c_void_p]),
+    "eeg_dcrnn_bce_logits_cw": (c_int, [_FP, _FP, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_ce_logits_cw": (c_int, [_FP, _FP, c_int, c_int, _FP, _FP, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_clip_weights": (c_int, [_FP, c_int, _FP, c_int64, c_int64, _FP, c_int64, c_int, c_int, c_int, _FP, c_int, _FP, c_int, _FP, _FP,
+                                       c_void_p]),
     # the evaluation pass on the device: per-clip scores behind the head, then the scores of the pool as one int64 record
     "eeg_dcrnn_eval_scores": (c_int, [_FP, _FP, c_int, _FP, _FP, c_int, c_int, c_int, c_int, c_int64, _FP, _FP, c_void_p]),
     "eeg_dcrnn_eval_metrics_ws_bytes": (c_size_t, [c_int64, c_int]),

@@ -30,6 +30,7 @@
 #include "spec_common.h"
 #include "spec_launch.h"
 #include "kernels_tail.h"
+#include "kernels_weights.h"
 #include "prof.h"
 #include "seq_launch.h"
 #include "gemmq_launch.h"
@@ -1820,10 +1821,11 @@ int eeg_dcrnn_cls_head_bwd(const float* z, const float* W, const float* dlogits,
 size_t eeg_dcrnn_cls_head_loss_ws_floats(int B, int H, int C) {
     return (B >= 1 && H >= 1 && C >= 1) ? (size_t)ceil_div(B, 4) * ((size_t)C * H + C + 1) : 0;
 }
-// clip_w != nullptr: the weighted head (eeg_dcrnn_cls_head_loss_w), else the plain one -- the same checks and launch shapes
+// clip_w != nullptr: the weighted head (eeg_dcrnn_cls_head_loss_w; multiply: eeg_dcrnn_cls_head_loss_cw), else the plain one -- the same
+// checks and launch shapes
 static int cls_head_loss_launch(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
-                                float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom, float* logits, int32_t* arg,
-                                float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
+                                float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom, bool multiply, float* logits,
+                                int32_t* arg, float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
     if (B < 1 || N < 1 || H < 1 || C < 1) return fail("cls_head_loss: empty input (B=%d, N=%d, H=%d, C=%d)", B, N, H, C);
     if (N > 64) return fail("cls_head_loss: num_nodes=%d unsupported (<= 64)", N);
     if (H % 4 != 0) return fail("cls_head_loss: rnn_units=%d must be a multiple of 4", H);
@@ -1838,6 +1840,14 @@ static int cls_head_loss_launch(const float* z, const float* W, const float* bia
     const int O = C * H + C, nblk = ceil_div(B, 4);
     const size_t lds = (size_t)(4 * cls_tail_wave_floats(N, H, C) + 4 * (O + 1)) * sizeof(float);
     if (lds > kMaxLdsBytes) return fail("cls_head_loss: N=%d x (classes=%d + rnn_units=%d) floats of four clips do not fit the %zu-byte LDS", N, C, H, (size_t)kMaxLdsBytes);
+    if (clip_w != nullptr && multiply) {
+        EEG_SET_MAX_LDS(cls_head_loss_cw_kernel, lds);
+        EEG_LAUNCH_P("cls_head_loss", cls_head_loss_cw_kernel, dim3(nblk), dim3(256), lds, S_(stream), z, W, bias, targets, kind, B, N, H, C, drop,
+                     reinterpret_cast<const unsigned long long*>(rng_used), clip_w, denom, logits, reinterpret_cast<int*>(arg), dlogits, dz, ws);
+        if (check_launch("cls_head_loss_cw")) return 1;
+        EEG_LAUNCH_P("cls_head_loss", cls_head_loss_w_finish_kernel, dim3(1), dim3(256), 0, S_(stream), ws, nblk, denom, H, C, dW, dbias, loss);
+        return check_launch("cls_head_loss_cw_finish");
+    }
     if (clip_w != nullptr) {
         EEG_SET_MAX_LDS(cls_head_loss_w_kernel, lds);
         EEG_LAUNCH_P("cls_head_loss", cls_head_loss_w_kernel, dim3(nblk), dim3(256), lds, S_(stream), z, W, bias, targets, kind, B, N, H, C, drop,
@@ -1856,15 +1866,22 @@ static int cls_head_loss_launch(const float* z, const float* W, const float* bia
 int eeg_dcrnn_cls_head_loss(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
                             float dropout_p, const uint64_t* rng_used, float* logits, int32_t* arg, float* dlogits, float* dz,
                             float* dW, float* dbias, float* loss, float* ws, void* stream) {
-    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, nullptr, nullptr, logits, arg, dlogits, dz, dW, dbias,
-                                loss, ws, stream);
+    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, nullptr, nullptr, false, logits, arg, dlogits, dz, dW,
+                                dbias, loss, ws, stream);
 }
 int eeg_dcrnn_cls_head_loss_w(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
                               float dropout_p, const uint64_t* rng_used, const float* clip_w, const float* denom, float* logits, int32_t* arg,
                               float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
     if (clip_w == nullptr || denom == nullptr) return fail("cls_head_loss_w: null clip_w / denom");
-    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, clip_w, denom, logits, arg, dlogits, dz, dW, dbias,
-                                loss, ws, stream);
+    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, clip_w, denom, false, logits, arg, dlogits, dz, dW,
+                                dbias, loss, ws, stream);
+}
+int eeg_dcrnn_cls_head_loss_cw(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N, int H, int C,
+                               float dropout_p, const uint64_t* rng_used, const float* clip_u, const float* denom, float* logits, int32_t* arg,
+                               float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws, void* stream) {
+    if (clip_u == nullptr || denom == nullptr) return fail("cls_head_loss_cw: null clip_u / denom");
+    return cls_head_loss_launch(z, W, bias, targets, kind, B, N, H, C, dropout_p, rng_used, clip_u, denom, true, logits, arg, dlogits, dz, dW,
+                                dbias, loss, ws, stream);
 }
 size_t eeg_dcrnn_dconv_fwd_ws_floats(int B, int N, int F, int M, int O) {
     if (B < 1 || N < 1 || F < 1 || M < 1 || O < 1) return 0;
@@ -1953,6 +1970,52 @@ int eeg_dcrnn_ce_logits_w(const float* logits, const int64_t* y, int B, int C, c
     EEG_LAUNCH_P("loss_ce", ce_logits_w_kernel, dim3(1), dim3(256), 256 * sizeof(float), S_(stream), logits,
                  reinterpret_cast<const long long*>(y), B, C, clip_w, denom, loss, dlogits);
     return check_launch("ce_logits_w");
+}
+int eeg_dcrnn_bce_logits_cw(const float* logits, const float* y, int B, const float* clip_u, const float* denom, float* loss, float* dlogits,
+                            void* stream) {
+    if (B < 1) return fail("bce_logits_cw: empty batch");
+    if (logits == nullptr || y == nullptr || loss == nullptr || dlogits == nullptr) return fail("bce_logits_cw: null logits / y / loss / dlogits");
+    if (clip_u == nullptr || denom == nullptr) return fail("bce_logits_cw: null clip_u / denom");
+    EEG_LAUNCH_P("loss_bce", bce_logits_cw_kernel, dim3(1), dim3(256), 256 * sizeof(float), S_(stream), logits, y, B, clip_u, denom, loss, dlogits);
+    return check_launch("bce_logits_cw");
+}
+int eeg_dcrnn_ce_logits_cw(const float* logits, const int64_t* y, int B, int C, const float* clip_u, const float* denom, float* loss,
+                           float* dlogits, void* stream) {
+    if (B < 1 || C < 1) return fail("ce_logits_cw: empty batch");
+    if (logits == nullptr || y == nullptr || loss == nullptr || dlogits == nullptr) return fail("ce_logits_cw: null logits / y / loss / dlogits");
+    if (clip_u == nullptr || denom == nullptr) return fail("ce_logits_cw: null clip_u / denom");
+    EEG_LAUNCH_P("loss_ce", ce_logits_cw_kernel, dim3(1), dim3(256), 256 * sizeof(float), S_(stream), logits,
+                 reinterpret_cast<const long long*>(y), B, C, clip_u, denom, loss, dlogits);
+    return check_launch("ce_logits_cw");
+}
+/* ---- the step's per-clip multipliers and their divisor (class / sample weights), written on the device ---- */
+int eeg_dcrnn_clip_weights(const void* labels, int label_bytes, const int64_t* perm, int64_t n_perm, int64_t P, const int64_t* cursor, int64_t back,
+                           int B, int rank, int world, const float* class_w, int C, const float* sample_w, int norm, float* clip_u, float* denom,
+                           void* stream) {
+    if (labels == nullptr || clip_u == nullptr || denom == nullptr) return fail("clip_weights: null labels / clip_u / denom");
+    if (label_bytes != 4 && label_bytes != 8) return fail("clip_weights: label_bytes=%d unsupported (4: float 0/1 labels, 8: int64 classes)", label_bytes);
+    if (B < 1 || world < 1 || rank < 0 || rank >= world) return fail("clip_weights: B=%d, rank=%d, world=%d unsupported (B >= 1, 0 <= rank < world)", B, rank, world);
+    if (norm != kWeightNormSum && norm != kWeightNormCount) return fail("clip_weights: norm=%d (0 = sum of the weights, 1 = count of the clips)", norm);
+    if ((class_w == nullptr) != (C == 0) || C < 0) return fail("clip_weights: class_w and C=%d disagree (no class weights: NULL and 0)", C);
+    if (class_w != nullptr && label_bytes == 4 && C != 2) return fail("clip_weights: float labels are 0 / 1: C=%d class weights (2)", C);
+    if ((((uintptr_t)labels) & (uintptr_t)(label_bytes == 8 ? 7 : 3)) != 0 || (((uintptr_t)perm | (uintptr_t)cursor) & 7) != 0 ||
+        (((uintptr_t)class_w | (uintptr_t)sample_w | (uintptr_t)clip_u | (uintptr_t)denom) & 3) != 0)
+        return fail("clip_weights: labels / perm / cursor / class_w / sample_w / clip_u / denom must be aligned to their element size");
+    long long slots = B;
+    if (perm != nullptr) {       // the sampler form: the label pool through perm and the cursor
+        if (cursor == nullptr) return fail("clip_weights: perm without cursor");
+        if (P < 1 || n_perm < 1) return fail("clip_weights: P=%lld clips, n_perm=%lld entries (both >= 1)", (long long)P, (long long)n_perm);
+        slots = (long long)B * world;
+        if (back != 0 && back != slots) return fail("clip_weights: back=%lld (0: ahead of the gather, B*world=%lld: behind it)", (long long)back, slots);
+    } else {                     // the batch form: the batch's own labels, the rank's own divisor
+        if (cursor != nullptr || sample_w != nullptr || back != 0) return fail("clip_weights: cursor / sample_w / back belong to the sampler form (perm is NULL)");
+        rank = 0;
+        world = 1;
+    }
+    EEG_LAUNCH_P("clip_weights", clip_weights_kernel, dim3(1), dim3(kClipWeightThreads), kClipWeightThreads * sizeof(double), S_(stream), labels, label_bytes,
+                 reinterpret_cast<const long long*>(perm), (long long)n_perm, (long long)P, reinterpret_cast<const long long*>(cursor), (long long)back, B,
+                 (long long)rank * B, slots, world, class_w, C, sample_w, norm, clip_u, denom);
+    return check_launch("clip_weights");
 }
 size_t eeg_dcrnn_masked_loss_ws_floats(void) { return 2 * kLossBlocks + 64; }
 int eeg_dcrnn_masked_loss(const float* pred, const float* y, size_t n, int use_scaler, float mean, float std_,

@@ -125,11 +125,15 @@ __global__ void cls_head_bwd_w_kernel(const float* __restrict__ z, const float* 
 // kind 0: nn.BCEWithLogitsLoss on logits (B,1), float targets; kind 1: nn.CrossEntropyLoss on (B,C), int64 targets (a label outside
 // 0..C-1 makes the LOSS NaN, see ce_logits_kernel).  LDS per wave: [N][C] node logits | [N][H] masked relu(z) | [C] dlogits | [C] arg.
 __host__ __device__ inline int cls_tail_wave_floats(int N, int H, int C) { return N * C + N * H + 2 * C; }
-// kWeighted (cls_head_loss_w_kernel, an epoch's short last batch): clip b counts iff clip_w[b] != 0 and the mean divides by denom[0]
+// kClipSelect (cls_head_loss_w_kernel, an epoch's short last batch): clip b counts iff clip_w[b] != 0 and the mean divides by denom[0]
 // (device memory) instead of B.  A clip that does not count is SELECTED out, not multiplied: its dlogits are zero -- hence dz and
 // its dW / dbias contributions -- and its loss term is zero whatever its label holds (no NaN from a label outside 0..C-1 there);
 // logits and arg are written for it as for every clip.  The arithmetic and the order of the sums are those of the unweighted kernel.
-template <bool kWeighted>
+// kClipMultiply (cls_head_loss_cw_kernel, class and sample weights: clip_weights_kernel): clip_w[b] = u_b >= 0 is a MULTIPLIER -- term
+// u_b * l_b, dlogits (u_b * g_b) / denom[0], the product first, then the one division -- and u_b == 0 selects the clip out as above.
+// 1 * x is x: with u = 1 and denom = B the bits of the unweighted kernel.  The two older modes compile to the code they always were.
+enum ClipMode { kClipNone = 0, kClipSelect = 1, kClipMultiply = 2 };
+template <ClipMode kMode>
 __device__ __forceinline__ void cls_head_loss_body(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
                                                    const void* __restrict__ targets, int kind, int B, int N, int H, int C, const DropCfg& drop,
                                                    const unsigned long long* __restrict__ used, float* __restrict__ logits,
@@ -177,14 +181,17 @@ __device__ __forceinline__ void cls_head_loss_body(const float* __restrict__ z, 
         EEG_WAVE_SYNC();
         if (lane == 0) {                                       // the clip's loss term and d loss / d logits (C is a handful)
             float term;
-            const float div = kWeighted ? denom[0] : (float)B;
-            if (kWeighted && clip_w[b] == 0.f) {
+            const float div = kMode != kClipNone ? denom[0] : (float)B;
+            const float u = kMode == kClipMultiply ? clip_w[b] : 1.f;
+            if (kMode != kClipNone && clip_w[b] == 0.f) {
                 term = 0.f;
                 for (int c = 0; c < C; ++c) dl[c] = 0.f;
             } else if (kind == 0) {
                 const float v = dl[0], t = reinterpret_cast<const float*>(targets)[b];
                 term = fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));
-                dl[0] = (1.f / (1.f + expf(-v)) - t) / div;
+                const float g = 1.f / (1.f + expf(-v)) - t;
+                dl[0] = (kMode == kClipMultiply ? u * g : g) / div;
+                if (kMode == kClipMultiply) term = u * term;
             } else {
                 float mx = dl[0];
                 for (int c = 1; c < C; ++c) mx = fmaxf(mx, dl[c]);
@@ -195,7 +202,11 @@ __device__ __forceinline__ void cls_head_loss_body(const float* __restrict__ z, 
                 const bool t_ok = tl >= 0 && tl < (long long)C;
                 const int t = t_ok ? (int)tl : -1;
                 term = lse - (t_ok ? dl[t] : __builtin_nanf(""));
-                for (int c = 0; c < C; ++c) dl[c] = (expf(dl[c] - lse) - (c == t ? 1.f : 0.f)) / div;
+                for (int c = 0; c < C; ++c) {
+                    const float g = expf(dl[c] - lse) - (c == t ? 1.f : 0.f);
+                    dl[c] = (kMode == kClipMultiply ? u * g : g) / div;
+                }
+                if (kMode == kClipMultiply) term = u * term;
             }
             contrib[w * (O + 1) + O] = term;
             for (int c = 0; c < C; ++c) dlogits[(size_t)b * C + c] = dl[c];
@@ -236,14 +247,21 @@ __global__ __launch_bounds__(256) void cls_head_loss_kernel(const float* __restr
                                                             const unsigned long long* __restrict__ used, float* __restrict__ logits,
                                                             int* __restrict__ arg, float* __restrict__ dlogits, float* __restrict__ dz,
                                                             float* __restrict__ partial) {
-    cls_head_loss_body<false>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, nullptr, nullptr);
+    cls_head_loss_body<kClipNone>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, nullptr, nullptr);
 }
 __global__ __launch_bounds__(256) void cls_head_loss_w_kernel(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
                                                               const void* __restrict__ targets, int kind, int B, int N, int H, int C, DropCfg drop,
                                                               const unsigned long long* __restrict__ used, const float* __restrict__ clip_w,
                                                               const float* __restrict__ denom, float* __restrict__ logits, int* __restrict__ arg,
                                                               float* __restrict__ dlogits, float* __restrict__ dz, float* __restrict__ partial) {
-    cls_head_loss_body<true>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, clip_w, denom);
+    cls_head_loss_body<kClipSelect>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, clip_w, denom);
+}
+__global__ __launch_bounds__(256) void cls_head_loss_cw_kernel(const float* __restrict__ z, const float* __restrict__ W, const float* __restrict__ bias,
+                                                               const void* __restrict__ targets, int kind, int B, int N, int H, int C, DropCfg drop,
+                                                               const unsigned long long* __restrict__ used, const float* __restrict__ clip_u,
+                                                               const float* __restrict__ denom, float* __restrict__ logits, int* __restrict__ arg,
+                                                               float* __restrict__ dlogits, float* __restrict__ dz, float* __restrict__ partial) {
+    cls_head_loss_body<kClipMultiply>(z, W, bias, targets, kind, B, N, H, C, drop, used, logits, arg, dlogits, dz, partial, clip_u, denom);
 }
 // dW / dbias / loss from the per-workgroup partials, in block order; div: the divisor of the mean
 __device__ __forceinline__ void cls_head_loss_finish_body(const float* __restrict__ partial, int nblk, float div, int H, int C,

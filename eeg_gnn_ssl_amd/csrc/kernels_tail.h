@@ -116,6 +116,59 @@ __global__ void ce_logits_w_kernel(const float* __restrict__ x, const long long*
     if (threadIdx.x == 0) loss[0] = sm[0] / div;
 }
 
+// The two criteria with a MULTIPLIER per clip (class and sample weights, clip_weights_kernel of kernels_weights.h): clip i carries
+// clip_u[i] >= 0, loss = (sum_i u_i * l_i) / denom[0], dlogits_i = (u_i * g_i) / denom[0] -- the product first, then the one division.
+// nn.CrossEntropyLoss(weight=w) is u_i = w[y_i], denom = sum_i u_i; nn.BCEWithLogitsLoss(pos_weight=p) on 0/1 labels is u_i = y_i ? p :
+// 1, denom = B.  u_i == 0 selects the clip out exactly as the _w kernels do (its label and logits are not looked at).  Same launch
+// shape, same order of the sums; 1 * x is x: with clip_u = 1 and denom = B the results are those of the unweighted kernels bit for
+// bit.  A label outside 0..C-1 on a clip that counts: NaN loss and the softmax alone as gradient, as everywhere.
+__global__ void bce_logits_cw_kernel(const float* __restrict__ x, const float* __restrict__ y, int B, const float* __restrict__ clip_u,
+                                     const float* __restrict__ denom, float* __restrict__ loss, float* __restrict__ dx) {
+    EEG_DYN_SMEM(sm);
+    const float div = denom[0];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+        const float u = clip_u[i];
+        if (u == 0.f) { dx[i] = 0.f; continue; }
+        const float v = x[i], t = y[i];
+        acc += u * bce_logits_term(v, t);
+        dx[i] = (u * (1.f / (1.f + expf(-v)) - t)) / div;
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = sm[0] / div;
+}
+__global__ void ce_logits_cw_kernel(const float* __restrict__ x, const long long* __restrict__ y, int B, int C, const float* __restrict__ clip_u,
+                                    const float* __restrict__ denom, float* __restrict__ loss, float* __restrict__ dx) {
+    EEG_DYN_SMEM(sm);
+    const float div = denom[0];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+        const float u = clip_u[i];
+        if (u == 0.f) {
+            for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = 0.f;
+            continue;
+        }
+        const float* r = x + (size_t)i * C;
+        const float lse = ce_row_lse(r, C);
+        const long long tl = y[i];
+        const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
+        acc += u * ce_logits_term(r, C, tl, lse);
+        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (u * (expf(r[c] - lse) - (c == t ? 1.f : 0.f))) / div;
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = sm[0] / div;
+}
+
 // utils.compute_regression_loss (utils.py:431-495): optional scalar StandardScaler inverse transform
 // (v*std + mean), mask = (y_true != mask_val), loss = sum(e * mask) / count(mask) with e = |d| (kind 0,
 // masked MAE) or d^2 followed by sqrt (kind 1: `masked_mse_loss`, really a masked RMSE).

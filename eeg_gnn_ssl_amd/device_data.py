@@ -25,7 +25,11 @@ signal buffer, a clip is a row (rec, x_start, x_samples, y_start) of an int64 ta
 the step's batch -- raw signals (B, N, Tx*W), the SSL target (B, N, Ty*W), lengths, labels -- in front of the unchanged raw chain.
 The SSL target is then no pool of its own, a classification clip needs no host padding, and overlapping or strided clips cost a
 table row each.  `clip_table_detection` / `clip_table_ssl` / `clip_table_classification` restate the three loaders' arithmetic.
-Both data sets hand their batch over through one method, `gather`."""
+Both data sets hand their batch over through one method, `gather`.
+
+Class imbalance.  `BalancedEpochSampler` draws a balanced epoch out of the whole resident pool -- every epoch anew, or once per run
+as the reference's detection loader does -- into a permutation shorter than the pool, which the gathers take as it is;
+`TrainStep(class_weights=, sample_weights=)` weighs the clips of a step on the device (`ops.clip_weights`)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -346,23 +350,35 @@ class EpochSampler:
 
     def __init__(self, P: int, batch_size: int, seed: int, rank: Optional[int] = None, world: Optional[int] = None, device=None,
                  drop_last: bool = True):
-        has_pg = dist.is_available() and dist.is_initialized()
-        self.rank = int(rank) if rank is not None else (dist.get_rank() if has_pg else 0)
-        self.world = int(world) if world is not None else (dist.get_world_size() if has_pg else 1)
-        self.P, self.batch_size, self.seed = int(P), int(batch_size), int(seed)
-        if self.world < 1 or not 0 <= self.rank < self.world:
-            raise ValueError(f"EpochSampler: rank={self.rank} of world={self.world}")
+        self._shard(rank, world, batch_size, seed)
+        self.P = int(P)
         if self.batch_size < 1 or self.batch_size * self.world > self.P:
             raise ValueError(f"EpochSampler: batch_size*world = {self.batch_size}*{self.world} clips per step, the pool holds P={self.P} "
                              f"(1 <= batch_size*world <= P)")
-        if not 0 <= self.seed < 2 ** 63:
-            raise ValueError(f"EpochSampler: seed={seed} outside 0..2^63-1")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
+        self._allocate(self.P, device, drop_last)
+
+    def _shard(self, rank, world, batch_size, seed):
+        """this rank's place in the step, the batch size and the seed (refusals by the name of the class)"""
+        who = type(self).__name__
+        has_pg = dist.is_available() and dist.is_initialized()
+        self.rank = int(rank) if rank is not None else (dist.get_rank() if has_pg else 0)
+        self.world = int(world) if world is not None else (dist.get_world_size() if has_pg else 1)
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        if self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError(f"{who}: rank={self.rank} of world={self.world}")
+        if not 0 <= self.seed < 2 ** 63:
+            raise ValueError(f"{who}: seed={seed} outside 0..2^63-1")
+
+    def _allocate(self, epoch_len: int, device, drop_last: bool):
+        """the device state of an epoch of `epoch_len` clips out of the pool's P (EpochSampler: all P; BalancedEpochSampler: its quotas):
+        perm (epoch_len,), cursor, the key buffers over the pool and, for drop_last=False, the tail buffers -- fixed addresses"""
+        self.epoch_len = int(epoch_len)
         self.drop_last = bool(drop_last)
         per_step = self.batch_size * self.world
-        self.steps_per_epoch = self.P // per_step if self.drop_last else -(-self.P // per_step)
-        self.perm = torch.arange(self.P, dtype=torch.int64, device=device)
+        self.steps_per_epoch = self.epoch_len // per_step if self.drop_last else -(-self.epoch_len // per_step)
+        self.perm = torch.arange(self.epoch_len, dtype=torch.int64, device=device)
         self.cursor = torch.zeros(1, dtype=torch.int64, device=device)
         self._keys = torch.empty(self.P, dtype=torch.int64, device=device)
         self._sorted = torch.empty(self.P, dtype=torch.int64, device=device)
@@ -396,12 +412,12 @@ class EpochSampler:
 
     def take(self) -> int:
         """the global number of clips that count in the step about to be issued; moves the host mirror of the cursor on by one
-        step.  No device read: batch_size * world for the default sampler, clamp(P - cursor, 0, batch_size * world) from the mirror
+        step.  No device read: batch_size * world for the default sampler, clamp(epoch_len - cursor, 0, batch_size * world) from the mirror
         for drop_last=False."""
         per_step = self.batch_size * self.world
         if self.drop_last:
             return per_step
-        n = min(max(self.P - self._host_cursor, 0), per_step)
+        n = min(max(self.epoch_len - self._host_cursor, 0), per_step)
         self._host_cursor += per_step
         return n
 
@@ -412,8 +428,82 @@ class EpochSampler:
         """the permutation is a function of (seed, epoch): it is drawn again, and the cursor returns to where the run stopped"""
         self.seed = int(state["seed"])
         if state["epoch"] is None:
-            self.perm.copy_(torch.arange(self.P, dtype=torch.int64, device=self.device))
+            self.perm.copy_(torch.arange(self.epoch_len, dtype=torch.int64, device=self.device))
             self.epoch = None
         else:
             self.begin_epoch(int(state["epoch"]))
         self.seek(int(state["cursor"]))
+
+
+class BalancedEpochSampler(EpochSampler):
+    """Balanced under-sampling per epoch, on the device: the reference's detection loader keeps int(scale_ratio * n_seizure) seizure clips
+    and draws as many non-seizure clips at random, ONCE, when the loader is built (data/dataloader_detection.py:88-127,
+    `parseTxtFiles`).  Here the pool stays whole in HBM and every epoch is a draw of `quotas[c]` clips of each class c.
+
+    labels: the dataset's label pool on the device -- float32 0 / 1 (detection; class = label >= 0.5) or int64 classes 0..C-1.  The
+    class counts n_c are read ONCE, here (the sampler's only synchronisation).  Default quotas: q_c = min(n_c, int(scale_ratio *
+    n_rarest)), the reference's arithmetic with the rarest class present in the role of "seizure"; quotas=[q_0, ..] overrides them
+    (one per class; q_c > n_c is refused).  `epoch_len` = sum_c q_c is the length of `perm` -- fixed size, fixed address -- and what
+    steps_per_epoch and `take` count; `P` stays the pool size (what `TrainStep` checks against the dataset).
+
+    begin_epoch(e), e < 2^30, outside any graph, no host read: selection keys k1 = epoch_keys(seed, 2 * e') with e' = e if redraw
+    else 0, order keys k2 = epoch_keys(seed, 2 * e + 1); within each class the q_c clips with the smallest (k1_i, i) are selected, and
+    perm is the selected clips sorted by (k2_i, i).  redraw=False is the reference -- one draw of the negatives per run, reshuffled
+    every epoch; redraw=True (the default) is the point of keeping every recording resident: fresh negatives every epoch.  The sorts
+    are the framework's, all sizes host integers.  Everything else -- shards, drop_last=False tail buffers, seek, state_dict -- is
+    EpochSampler's; `redraw`, the quotas and drop_last are constructor properties, not state."""
+
+    def __init__(self, labels: torch.Tensor, batch_size: int, seed: int, scale_ratio: float = 1.0, quotas=None, redraw: bool = True,
+                 drop_last: bool = True, rank: Optional[int] = None, world: Optional[int] = None):
+        who = "BalancedEpochSampler"
+        if not torch.is_tensor(labels) or labels.dim() != 1 or labels.numel() < 1 or labels.dtype not in (torch.float32, torch.int64):
+            got = f"{labels.dtype} {tuple(labels.shape)}" if torch.is_tensor(labels) else type(labels).__name__
+            raise ValueError(f"{who}: labels must be the label pool (P,), float32 0 / 1 (detection) or int64 classes, got {got}")
+        self._shard(rank, world, batch_size, seed)
+        self.P, self.redraw = int(labels.numel()), bool(redraw)
+        classes = (labels >= 0.5).to(torch.int64) if labels.dtype == torch.float32 else labels
+        lo, hi = int(classes.min().item()), int(classes.max().item())          # the one synchronisation (with the counts below)
+        if lo < 0:
+            raise ValueError(f"{who}: labels hold the class {lo}; classes are 0..C-1")
+        num_classes = 2 if labels.dtype == torch.float32 else hi + 1
+        self.class_counts = torch.bincount(classes, minlength=num_classes).tolist()
+        present = [n for n in self.class_counts if n > 0]
+        if quotas is None:
+            if not float(scale_ratio) > 0:
+                raise ValueError(f"{who}: scale_ratio={scale_ratio} (> 0)")
+            keep = int(float(scale_ratio) * min(present))
+            quotas = [min(n, keep) for n in self.class_counts]
+        quotas = [int(q) for q in quotas]
+        if len(quotas) != num_classes:
+            raise ValueError(f"{who}: {len(quotas)} quotas for the {num_classes} classes of the labels")
+        for c, (q, n) in enumerate(zip(quotas, self.class_counts)):
+            if q < 0 or q > n:
+                raise ValueError(f"{who}: quota {q} for class {c}, which has {n} clips (0 <= quota <= count: no over-sampling)")
+        self.quotas = quotas
+        if self.batch_size < 1 or self.batch_size * self.world > sum(quotas):
+            raise ValueError(f"{who}: batch_size*world = {self.batch_size}*{self.world} clips per step, a balanced epoch holds "
+                             f"{sum(quotas)} (quotas {quotas} of class counts {self.class_counts})")
+        self._allocate(sum(quotas), labels.device, drop_last)
+        self._keys2 = torch.empty(self.P, dtype=torch.int64, device=labels.device)
+        # the members of each class in pool order (ascending i: a stable sort of their keys breaks ties by i)
+        self._members = [torch.nonzero(classes == c).view(-1) if q > 0 else None for c, q in enumerate(quotas)]
+
+    def begin_epoch(self, epoch: int):
+        """outside any captured graph (the sorts are the framework's and allocate); no host read"""
+        epoch = int(epoch)
+        if not 0 <= epoch < 2 ** 30:
+            raise ValueError(f"BalancedEpochSampler: epoch={epoch} outside 0..2^30-1 (two key streams per epoch)")
+        ops.epoch_keys(self._keys, self.seed, 2 * epoch if self.redraw else 0)
+        ops.epoch_keys(self._keys2, self.seed, 2 * epoch + 1)
+        chosen = []
+        for members, q in zip(self._members, self.quotas):
+            if q > 0:
+                order = torch.sort(self._keys[members], stable=True).indices
+                chosen.append(members[order[:q]])
+        chosen = torch.sort(torch.cat(chosen)).values                           # ascending i: ties of k2 break by i below
+        order = torch.sort(self._keys2[chosen], stable=True).indices
+        torch.index_select(chosen, 0, order, out=self.perm)
+        self.cursor.zero_()
+        self._host_cursor = 0
+        self.epoch = epoch
+        return self

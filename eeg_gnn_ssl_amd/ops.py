@@ -13,7 +13,7 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    feature_moments, moments_record, occlude_expand, occlusion_scores.
+    feature_moments, moments_record, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -115,12 +115,13 @@ def _clip_lengths(what: str, lengths: torch.Tensor, b: int, ref: torch.Tensor):
     return lengths.contiguous()
 
 
-def _clip_weights(what: str, clip_w: torch.Tensor, denom: torch.Tensor, b: int, ref: torch.Tensor):
-    """`clip_w` / `denom` of the weighted criteria (written by `gather_clips(..., clip_w=, denom=, n_valid=)`), read by the kernels ON
-    THE DEVICE: anything but a float32 (B,) tensor and one float32 on the device of the clips is refused"""
+def _clip_weights(what: str, clip_w: torch.Tensor, denom: torch.Tensor, b: int, ref: torch.Tensor, name: str = "clip_w"):
+    """`clip_w` / `denom` of the weighted criteria (written by `gather_clips(..., clip_w=, denom=, n_valid=)`; name "clip_u": the
+    multipliers of `clip_weights`), read by the kernels ON THE DEVICE: anything but a float32 (B,) tensor and one float32 on the device
+    of the clips is refused"""
     if not torch.is_tensor(clip_w) or clip_w.dtype != torch.float32 or tuple(clip_w.shape) != (b,) or clip_w.device != ref.device:
         got = f"{clip_w.dtype} {tuple(clip_w.shape)} on {clip_w.device}" if torch.is_tensor(clip_w) else type(clip_w).__name__
-        raise RuntimeError(f"{what}: clip_w must be a float32 tensor of shape ({b},) on {ref.device} (one weight per clip, read on the "
+        raise RuntimeError(f"{what}: {name} must be a float32 tensor of shape ({b},) on {ref.device} (one weight per clip, read on the "
                            f"device), got {got}")
     if not torch.is_tensor(denom) or denom.dtype != torch.float32 or denom.numel() != 1 or denom.device != ref.device:
         got = f"{denom.dtype} {tuple(denom.shape)} on {denom.device}" if torch.is_tensor(denom) else type(denom).__name__
@@ -1019,10 +1020,11 @@ def _cls_head_backward(ctx, dlogits, _darg):
 torch.library.register_autograd(f"{NS}::cls_head", _cls_head_backward, setup_context=_cls_head_setup, lib=_libdef)
 
 
-def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, dw, db, clip_w=None, denom=None):
+def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, dw, db, clip_w=None, denom=None, multiply=False):
     """head forward + criterion + the head's backward for one optimisation step (eeg_dcrnn_cls_head_loss): returns
     (loss (1,), logits (B,C), arg (B,C) int32, dlogits (B,C), dz (B,N,H)); dw (C,H) / db (C) are overwritten.
-    clip_w / denom (the operator cls_head_loss_w): over the clips that count (eeg_dcrnn_cls_head_loss_w)."""
+    clip_w / denom (the operator cls_head_loss_w): over the clips that count (eeg_dcrnn_cls_head_loss_w); multiply (the operator
+    cls_head_loss_cw): clip_w holds the per-clip multipliers clip_u (eeg_dcrnn_cls_head_loss_cw)."""
     lib = _lib.get_lib()
     z, w, bias = z.contiguous(), w.detach().contiguous(), bias.detach().contiguous()
     for t, nm in ((z, "head input"), (w, "fc.weight"), (bias, "fc.bias"), (dw, "fc.weight gradient"), (db, "fc.bias gradient")):
@@ -1054,14 +1056,18 @@ def _cls_head_loss_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_us
         lib.call("eeg_dcrnn_cls_head_loss", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
                  _p(logits), _p(arg), _p(dlogits), _p(dz), _p(dw), _p(db), _p(loss), _p(ws), _stream(z))
     else:
-        clip_w, denom = _clip_weights("cls_head_loss", clip_w, denom, b, z)
-        lib.call("eeg_dcrnn_cls_head_loss_w", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
+        clip_w, denom = _clip_weights("cls_head_loss", clip_w, denom, b, z, "clip_u" if multiply else "clip_w")
+        lib.call("eeg_dcrnn_cls_head_loss_cw" if multiply else "eeg_dcrnn_cls_head_loss_w", _p(z), _p(w), _p(bias), _p(tg), int(kind), b, n, h, c, float(dropout_p), _p(rng_used) if drop else None,
                  _p(clip_w), _p(denom), _p(logits), _p(arg), _p(dlogits), _p(dz), _p(dw), _p(db), _p(loss), _p(ws), _stream(z))
     return loss, logits, arg, dlogits, dz
 
 
 def _cls_head_loss_w_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, clip_w, denom, dw, db):
     return _cls_head_loss_impl(z, w, bias, targets, kind, dropout_p, rng_used, dw, db, clip_w, denom)
+
+
+def _cls_head_loss_cw_impl(z, w, bias, targets, kind: int, dropout_p: float, rng_used, clip_u, denom, dw, db):
+    return _cls_head_loss_impl(z, w, bias, targets, kind, dropout_p, rng_used, dw, db, clip_u, denom, multiply=True)
 
 
 def _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db):
@@ -1074,6 +1080,9 @@ _define("cls_head_loss", "(Tensor z, Tensor w, Tensor bias, Tensor targets, int 
 _define("cls_head_loss_w", "(Tensor z, Tensor w, Tensor bias, Tensor targets, int kind, float dropout_p, Tensor? rng_used, Tensor clip_w, Tensor denom, "
         "Tensor(a!) dw, Tensor(b!) db) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", _cls_head_loss_w_impl,
         lambda z, w, bias, targets, kind, dropout_p, rng_used, clip_w, denom, dw, db: _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db))
+_define("cls_head_loss_cw", "(Tensor z, Tensor w, Tensor bias, Tensor targets, int kind, float dropout_p, Tensor? rng_used, Tensor clip_u, Tensor denom, "
+        "Tensor(a!) dw, Tensor(b!) db) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", _cls_head_loss_cw_impl,
+        lambda z, w, bias, targets, kind, dropout_p, rng_used, clip_u, denom, dw, db: _cls_head_loss_fake(z, w, bias, targets, kind, dropout_p, rng_used, dw, db))
 
 
 def _gather_last_impl(htop, lengths):
@@ -1383,7 +1392,7 @@ _define("corr_graph_rows_len", "(Tensor x, int top_k, Tensor lengths, int steps)
 # =============================================================================================
 # losses that seed backward, optimiser tail
 # =============================================================================================
-def _bce_logits_impl(logits, y, clip_w=None, denom=None):
+def _bce_logits_impl(logits, y, clip_w=None, denom=None, multiply=False):
     lib = _lib.get_lib()
     x = logits.contiguous().view(-1)
     yy = y.to(torch.float32).contiguous().view(-1)
@@ -1395,12 +1404,12 @@ def _bce_logits_impl(logits, y, clip_w=None, denom=None):
     if clip_w is None:
         lib.call("eeg_dcrnn_bce_logits", _p(x), _p(yy), x.numel(), _p(loss), _p(dx), _stream(x))
     else:
-        clip_w, denom = _clip_weights("bce_logits", clip_w, denom, x.numel(), x)
-        lib.call("eeg_dcrnn_bce_logits_w", _p(x), _p(yy), x.numel(), _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
+        clip_w, denom = _clip_weights("bce_logits", clip_w, denom, x.numel(), x, "clip_u" if multiply else "clip_w")
+        lib.call("eeg_dcrnn_bce_logits_cw" if multiply else "eeg_dcrnn_bce_logits_w", _p(x), _p(yy), x.numel(), _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
     return loss[0], dx.view(logits.shape)
 
 
-def _ce_logits_impl(logits, y, clip_w=None, denom=None):
+def _ce_logits_impl(logits, y, clip_w=None, denom=None, multiply=False):
     lib = _lib.get_lib()
     x = logits.contiguous()
     yy = y.to(torch.int64).contiguous()
@@ -1412,8 +1421,8 @@ def _ce_logits_impl(logits, y, clip_w=None, denom=None):
     if clip_w is None:
         lib.call("eeg_dcrnn_ce_logits", _p(x), _p(yy), x.shape[0], x.shape[1], _p(loss), _p(dx), _stream(x))
     else:
-        clip_w, denom = _clip_weights("ce_logits", clip_w, denom, x.shape[0], x)
-        lib.call("eeg_dcrnn_ce_logits_w", _p(x), _p(yy), x.shape[0], x.shape[1], _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
+        clip_w, denom = _clip_weights("ce_logits", clip_w, denom, x.shape[0], x, "clip_u" if multiply else "clip_w")
+        lib.call("eeg_dcrnn_ce_logits_cw" if multiply else "eeg_dcrnn_ce_logits_w", _p(x), _p(yy), x.shape[0], x.shape[1], _p(clip_w), _p(denom), _p(loss), _p(dx), _stream(x))
     return loss[0], dx
 
 
@@ -1454,6 +1463,68 @@ _define("bce_logits_w", "(Tensor logits, Tensor y, Tensor clip_w, Tensor denom) 
 _define("ce_logits_w", "(Tensor logits, Tensor y, Tensor clip_w, Tensor denom) -> (Tensor loss, Tensor dlogits)", _ce_logits_impl, _loss_fake)
 _define("masked_loss_w", "(Tensor pred, Tensor y, bool use_scaler, float mean, float std, float mask_val, int kind, Tensor clip_w, Tensor denom) "
         "-> (Tensor loss, Tensor dpred)", _masked_loss_impl, _loss_fake)
+# the two supervised criteria with a multiplier per clip (class / sample weights): clip_u (B,) float32 >= 0 and denom (1,) float32 in
+# device memory (`clip_weights`): loss = sum(u * l) / denom, dlogits = u * g / denom; u == 0 selects the clip out
+_define("bce_logits_cw", "(Tensor logits, Tensor y, Tensor clip_u, Tensor denom) -> (Tensor loss, Tensor dlogits)",
+        lambda logits, y, clip_u, denom: _bce_logits_impl(logits, y, clip_u, denom, multiply=True), _loss_fake)
+_define("ce_logits_cw", "(Tensor logits, Tensor y, Tensor clip_u, Tensor denom) -> (Tensor loss, Tensor dlogits)",
+        lambda logits, y, clip_u, denom: _ce_logits_impl(logits, y, clip_u, denom, multiply=True), _loss_fake)
+
+
+WEIGHT_NORMS = {"sum": 0, "count": 1}     # eeg_dcrnn_clip_weights `norm`
+
+
+def _clip_weights_impl(labels, perm, cursor, back: int, rank: int, world: int, class_w, sample_w, norm: int, clip_u, denom) -> None:
+    """the step's multipliers clip_u (B,) and their divisor denom (1,), written in place (eeg_dcrnn_clip_weights).  perm / cursor given:
+    the sampler form (labels = the label pool); both None: the batch form (labels = the batch's own)."""
+    lib = _lib.get_lib()
+    what, dev = "clip_weights", labels.device
+    if labels.dtype not in (torch.float32, torch.int64) or labels.dim() != 1 or labels.numel() < 1:
+        raise RuntimeError(f"{what}: labels must be float32 (detection, 0 / 1) or int64 (classification) of shape (n,), got {labels.dtype} "
+                           f"{tuple(labels.shape)}")
+    _check(lib, labels, "labels", labels.dtype)
+    b = clip_u.numel()
+    for t, name, dtype, shape in ((clip_u, "clip_u", torch.float32, (b,)), (denom, "denom", torch.float32, (1,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous() or b < 1:
+            raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {shape if name == 'denom' else '(B,)'} on {dev}, got "
+                               f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    if (perm is None) != (cursor is None):
+        raise RuntimeError(f"{what}: perm and cursor come together (the sampler form), or neither (the batch form)")
+    pooled = perm is not None
+    if pooled:
+        for t, name, n in ((perm, "perm", None), (cursor, "cursor", 1)):
+            if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1 or (n is not None and t.numel() != n) or t.device != dev or not t.is_contiguous():
+                raise RuntimeError(f"{what}: {name} must be a contiguous int64 vector{'' if n is None else ' of one element'} on {dev}, got {t.dtype} "
+                                   f"{tuple(t.shape)} on {t.device}")
+        if not 0 <= rank < world:
+            raise RuntimeError(f"{what}: rank={rank} of world={world}")
+        if back not in (0, b * world):
+            raise RuntimeError(f"{what}: back={back} (0: in front of the step's gather; {b * world} = batch_size*world: behind it)")
+    else:
+        if labels.numel() != b:
+            raise RuntimeError(f"{what}: {labels.numel()} labels for the {b} clips of clip_u (the batch form: the batch's own labels)")
+        if sample_w is not None or back != 0:
+            raise RuntimeError(f"{what}: sample_w / back belong to the sampler form (perm and cursor are None)")
+    if norm not in (0, 1):
+        raise RuntimeError(f"{what}: norm={norm} (0 = sum, 1 = count)")
+    classes = 0
+    if class_w is not None:
+        classes = class_w.numel()
+        if class_w.dtype != torch.float32 or class_w.dim() != 1 or classes < 1 or class_w.device != dev or not class_w.is_contiguous() or \
+                (labels.dtype == torch.float32 and classes != 2):
+            raise RuntimeError(f"{what}: class_w must be a contiguous float32 vector on {dev}, one weight per class (2 for float 0 / 1 labels), "
+                               f"got {class_w.dtype} {tuple(class_w.shape)} on {class_w.device}")
+    if sample_w is not None and (sample_w.dtype != torch.float32 or tuple(sample_w.shape) != (labels.numel(),) or sample_w.device != dev or
+                                 not sample_w.is_contiguous()):
+        raise RuntimeError(f"{what}: sample_w must be a contiguous float32 tensor of shape ({labels.numel()},) on {dev} (one weight per clip of "
+                           f"the pool), got {sample_w.dtype} {tuple(sample_w.shape)} on {sample_w.device}")
+    lib.call("eeg_dcrnn_clip_weights", _p(labels), labels.element_size(), _p(perm), perm.numel() if pooled else 0, labels.numel() if pooled else 0,
+             _p(cursor), int(back), b, int(rank) if pooled else 0, int(world) if pooled else 1, _p(class_w), classes, _p(sample_w), int(norm),
+             _p(clip_u), _p(denom), _stream(clip_u))
+
+
+_define("clip_weights", "(Tensor labels, Tensor? perm, Tensor? cursor, int back, int rank, int world, Tensor? class_w, Tensor? sample_w, int norm, "
+        "Tensor(a!) clip_u, Tensor(b!) denom) -> ()", _clip_weights_impl, lambda *a: None)
 
 
 # ---- the evaluation pass on the device (train.py:332-431; evaluation.py: DeviceEvaluator) ----------------------------------------
@@ -1804,7 +1875,7 @@ def _loss_backward(ctx, dloss, _dgrad):
     return (dx * dloss,) + (None,) * (ctx.n_in - 1)
 
 
-for _name in ("bce_logits", "ce_logits", "masked_loss", "bce_logits_w", "ce_logits_w", "masked_loss_w"):
+for _name in ("bce_logits", "ce_logits", "masked_loss", "bce_logits_w", "ce_logits_w", "masked_loss_w", "bce_logits_cw", "ce_logits_cw"):
     torch.library.register_autograd(f"{NS}::{_name}", _loss_backward, setup_context=_loss_setup, lib=_libdef)
 
 
@@ -2412,16 +2483,25 @@ def cls_head(z, w, bias, dropout_p=0.0, rng_state=None, return_rng_used=False):
     return (logits, used) if return_rng_used else logits
 
 
-def _weights_together(what, clip_w, denom, ref):
+def _weights_together(what, clip_w, denom, ref, clip_u=None):
     """the pair of the weighted criteria: both or none, and on the device of the clips (the dispatcher picks the implementation by
-    the devices of ALL tensor arguments: a stray one is refused here, by name; dtype and shape are the operator's to refuse)"""
+    the devices of ALL tensor arguments: a stray one is refused here, by name; dtype and shape are the operator's to refuse).
+    clip_u (the multipliers of `clip_weights`) takes the place of clip_w (the selector of the validity gather): never both."""
+    if clip_u is not None:
+        if clip_w is not None:
+            raise RuntimeError(f"{what}: clip_w (which clips count) and clip_u (a multiplier per clip; 0 selects a clip out) are mutually "
+                               f"exclusive: fold the validity into clip_u (ops.clip_weights does)")
+        if denom is None:
+            raise RuntimeError(f"{what}: clip_u and denom come together (denom is None)")
+        _clip_weights(what, clip_u, denom, clip_u.numel() if torch.is_tensor(clip_u) and clip_u.dim() == 1 else -1, ref, "clip_u")
+        return
     if (clip_w is None) != (denom is None):
         raise RuntimeError(f"{what}: clip_w and denom come together (one of them is None)")
     if clip_w is not None:
         _clip_weights(what, clip_w, denom, clip_w.numel() if torch.is_tensor(clip_w) and clip_w.dim() == 1 else -1, ref)
 
 
-def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.0, rng_state=None, clip_w=None, denom=None):
+def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.0, rng_state=None, clip_w=None, denom=None, clip_u=None):
     """The tail of a supervised optimisation step behind the encoder (model.py:267-270 + train.py:203-206,266-272) in two launches:
     dropout -> relu -> fc -> max over nodes, the criterion (task "detection": BCE-with-logits, "classification": cross-entropy) and
     their backward.  z (B,N,H) = the top layer's state at len-1, DETACHED from autograd: the gradients of fc go straight into
@@ -2429,14 +2509,19 @@ def cls_head_loss(z, fc_weight, fc_bias, targets, task="detection", dropout_p=0.
     backward with the returned dz (`last.backward(dz)`).  Returns (loss (), logits (B,C), dz (B,N,H)).
     clip_w (B,) float32 / denom (1,) float32, both on the device and given together (`gather_clips(..., clip_w=, denom=, n_valid=)`,
     an epoch's short last batch): the mean runs over the clips with clip_w != 0 and divides by denom; the others get dz = 0 and add
-    nothing to the loss and to the gradients of fc, whatever their label holds.  logits are returned for every clip."""
-    _weights_together("cls_head_loss", clip_w, denom, z)
+    nothing to the loss and to the gradients of fc, whatever their label holds.  logits are returned for every clip.
+    clip_u (B,) float32 >= 0 with denom, instead of clip_w (`clip_weights`: class / sample weights): loss = sum_b u_b * l_b / denom and
+    every gradient carries u_b / denom; u_b == 0 selects the clip out as clip_w == 0 does."""
+    _weights_together("cls_head_loss", clip_w, denom, z, clip_u)
     used = rng_take(rng_state, z.numel() // 4) if dropout_p > 0 else None
     sunk = [GradSink.take(q) for q in (fc_weight, fc_bias)]
     dw = sunk[0] if sunk[0] is not None else _new_like(fc_weight)
     db = sunk[1] if sunk[1] is not None else _new_like(fc_bias)
     kind = 0 if task == "detection" else 1
-    if clip_w is None:
+    if clip_u is not None:
+        loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss_cw(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,
+                                                                           kind, float(dropout_p), used, clip_u, denom, dw, db)
+    elif clip_w is None:
         loss, logits, _arg, _dl, dz = torch.ops.eeg_dcrnn.cls_head_loss(z.detach(), fc_weight.detach(), fc_bias.detach(), targets,
                                                                         kind, float(dropout_p), used, dw, db)
     else:
@@ -2478,20 +2563,28 @@ def masked_regression_loss(y_predicted, y_true, mean=None, std=None, loss_fn="ma
     return torch.ops.eeg_dcrnn.masked_loss_w(*args, clip_w, denom)[0]
 
 
-def bce_with_logits(logits, y, clip_w=None, denom=None):
+def bce_with_logits(logits, y, clip_w=None, denom=None, clip_u=None):
     """nn.BCEWithLogitsLoss() (mean): value and dlogits from one HIP launch (train.py:203-204).
-    clip_w (B,) / denom (1,) (float32 on the device, together): sum over the clips with clip_w != 0, divided by denom."""
-    _weights_together("bce_with_logits", clip_w, denom, logits)
+    clip_w (B,) / denom (1,) (float32 on the device, together): sum over the clips with clip_w != 0, divided by denom.
+    clip_u (B,) >= 0 with denom, instead of clip_w: sum_b u_b * l_b / denom -- u_b = y_b ? p : 1, denom = B is `pos_weight=p` on 0 / 1
+    labels (`clip_weights(class_w=(1, p), norm="count")`)."""
+    _weights_together("bce_with_logits", clip_w, denom, logits, clip_u)
+    if clip_u is not None:
+        return torch.ops.eeg_dcrnn.bce_logits_cw(logits, y, clip_u, denom)[0]
     if clip_w is None:
         return torch.ops.eeg_dcrnn.bce_logits(logits, y)[0]
     return torch.ops.eeg_dcrnn.bce_logits_w(logits, y, clip_w, denom)[0]
 
 
-def cross_entropy(logits, y, clip_w=None, denom=None):
+def cross_entropy(logits, y, clip_w=None, denom=None, clip_u=None):
     """nn.CrossEntropyLoss() (mean) on (B,C) logits and int64 class targets (train.py:205-206).
     clip_w (B,) / denom (1,) (float32 on the device, together): sum over the clips with clip_w != 0, divided by denom; the label of
-    a clip that does not count is not looked at."""
-    _weights_together("cross_entropy", clip_w, denom, logits)
+    a clip that does not count is not looked at.
+    clip_u (B,) >= 0 with denom, instead of clip_w: sum_b u_b * l_b / denom -- u_b = w[y_b], denom = sum_b u_b is `weight=w`
+    (`clip_weights(class_w=w, norm="sum")`)."""
+    _weights_together("cross_entropy", clip_w, denom, logits, clip_u)
+    if clip_u is not None:
+        return torch.ops.eeg_dcrnn.ce_logits_cw(logits, y, clip_u, denom)[0]
     if clip_w is None:
         return torch.ops.eeg_dcrnn.ce_logits(logits, y)[0]
     return torch.ops.eeg_dcrnn.ce_logits_w(logits, y, clip_w, denom)[0]
@@ -2544,6 +2637,31 @@ def clip_adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, betas, eps, wei
     """Fused clip_grad_norm_ + Adam (coupled L2) over flat fp32 buffers (train.py:273-275)."""
     torch.ops.eeg_dcrnn.clip_adam_(params, grads, exp_avg, exp_avg_sq, int(step), float(lr), float(betas[0]), float(betas[1]),
                                    float(eps), float(weight_decay), float(max_norm), float(grad_scale), ws, norm_out)
+
+
+def clip_weights(labels, clip_u, denom, class_w=None, sample_w=None, norm="sum", perm=None, cursor=None, back: int = 0, rank: int = 0, world: int = 1):
+    """The multipliers of one step's criterion and their divisor, written on the device into clip_u (B,) float32 and denom (1,) float32
+    (fixed addresses, one launch, capturable): u = valid * class_w[class(label)] * sample_w[src], every factor optional.  class(label):
+    the int64 label (outside 0..C-1: weight 1), or label >= 0.5 for detection's float labels, which are taken to be 0 or 1 (class_w
+    has two entries then).  norm "sum": denom = sum of u over the step / world (`nn.CrossEntropyLoss(weight=)`; a zero sum gives 1);
+    "count": denom = max(n_valid, 1) / world (`nn.BCEWithLogitsLoss(pos_weight=p)` with class_w = (1, p)).
+    Batch form (perm=None): labels (B,) are the batch's own, every slot is valid, the divisor is the rank's own (world is ignored:
+    data-parallel, the result is the mean of the ranks' weighted means); no sample_w.
+    Sampler form (perm=, cursor= of an `EpochSampler`): labels is the label pool (P,), sample_w (P,) goes with it, and the kernel
+    walks all batch_size*world slots of the step through perm from the cursor as the step's gather saw it -- back=0 in front of the
+    gather, back=batch_size*world behind it -- with the validity rule of a drop_last=False epoch: every rank gets its own slice of
+    the weights and the same global divisor / world, with no communication."""
+    if norm not in WEIGHT_NORMS:
+        raise RuntimeError(f"clip_weights: norm={norm!r} ('sum' or 'count')")
+    for name, t in (("labels", labels), ("clip_u", clip_u), ("denom", denom)):
+        if not torch.is_tensor(t):
+            raise RuntimeError(f"clip_weights: {name} must be a tensor, got {type(t).__name__}")
+    for name, t in (("clip_u", clip_u), ("denom", denom), ("class_w", class_w), ("sample_w", sample_w), ("perm", perm), ("cursor", cursor)):
+        if t is not None and (not torch.is_tensor(t) or t.device != labels.device):      # (the dispatcher would route a stray tensor by its key)
+            raise RuntimeError(f"clip_weights: {name} must be a tensor on {labels.device} (the labels' device), got "
+                               f"{t.device if torch.is_tensor(t) else type(t).__name__}")
+    torch.ops.eeg_dcrnn.clip_weights(labels, perm, cursor, int(back), int(rank), int(world), class_w, sample_w, WEIGHT_NORMS[norm], clip_u, denom)
+    return clip_u, denom
 
 
 def epoch_keys(keys: torch.Tensor, seed: int, epoch: int) -> torch.Tensor:

@@ -59,8 +59,20 @@ class TrainStep:
                  always_reduce: bool = False, raw_window: Optional[int] = None, raw_mean: float = 0.0, raw_std: float = 1.0,
                  shared_graph: bool = True, data_augment: bool = False, swap_perm=None, reflected_supports=None,
                  feature_std: Optional[float] = None, use_fft: bool = True, feature_mean: Optional[float] = None,
-                 padding_val: Optional[float] = None):
-        """shared_graph: batched supports whose clips all carry one and the same graph (the reference's trainers pass the distance
+                 padding_val: Optional[float] = None, class_weights=None, weight_norm: Optional[str] = None, sample_weights=None):
+        """class_weights / sample_weights / weight_norm: the criterion of the supervised tasks with a weight per clip (class
+        imbalance; `_step_weights`).  class_weights: one weight >= 0 per class, a sequence or a float32 tensor on the model's device
+        -- (C,) for classification, `nn.CrossEntropyLoss(weight=)`; (2,) for detection, whose float labels are taken to be 0 or 1
+        (class = label >= 0.5): (1, p) is `nn.BCEWithLogitsLoss(pos_weight=p)`.  sample_weights: a float32 (P,) pool on the model's
+        device, one weight >= 0 per clip of the data set of `step_from` / `capture_epoch` (not for `step` / `capture`, which see no
+        pool).  weight_norm: "sum" divides by the sum of the step's weights (the default for classification), "count" by the number
+        of its clips (the default for detection); it has no effect without weights.  Every step then writes the clips' weights and
+        the divisor on the device (`ops.clip_weights`, one launch, capturable) and runs the multiplicative criteria.  From a
+        sampler the weights cover the step's clips on ALL ranks: the validity of a drop_last=False epoch's short last batch is part
+        of them and the divisor is global (on a drop_last=True sampler a step issued past the end of the epoch has weight 0
+        throughout).  `step` / `capture` weigh the rank's own batch: data-parallel, the mean of the ranks' weighted means.
+        `samples_seen` counts clips, not weights, and `evaluator` stays unweighted, as the reference's evaluation loss is.
+        shared_graph: batched supports whose clips all carry one and the same graph (the reference's trainers pass the distance
         graph that way) are handed to the model in their 2-D form, which lets the encoder run its hoisted GEMMs in the
         eigenbasis of that graph (`ops.collapse_shared_supports`: one comparison + one flag read per supports TENSOR, cached; a
         captured step keeps the decision of its capture -- refill a captured supports buffer with per-clip graphs only after
@@ -108,6 +120,8 @@ class TrainStep:
         if padding_val is not None and task == "ssl":
             raise ValueError("TrainStep: padding_val (variable-length clips) is for the supervised tasks; the SSL pair has no seq_lengths")
         self.padding_val = None if padding_val is None else float(padding_val)
+        self.class_weights, self.sample_weights, self.weight_norm = self._check_weights(model, task, class_weights, sample_weights, weight_norm)
+        self._weight_buffers = {}         # batch size -> (clip_u, denom): fixed addresses, a captured step rewrites them
         self.model, self.task, self.max_grad_norm = model, task, max_grad_norm
         self.fp = FlatParameters(model)
         # optimiser state lives in flat buffers; the update is ONE fused HIP kernel (clip + Adam)
@@ -230,11 +244,88 @@ class TrainStep:
         sc = None if self.scaler_mean is None else utils.StandardScaler(self.scaler_mean, self.scaler_std)
         return utils.compute_regression_loss(y_true=y, y_predicted=out, standard_scaler=sc, loss_fn="MAE")
 
-    def loss_and_grad(self, out, y, clip_w=None, denom=None):
+    @staticmethod
+    def _check_weights(model, task, class_weights, sample_weights, weight_norm):
+        """the weights of the criterion as device tensors, or the ValueError that names what is wrong with them -- before anything is
+        launched.  -> (class_weights (C,) | None, sample_weights (P,) | None, weight_norm)"""
+        if weight_norm is not None and weight_norm not in ops.WEIGHT_NORMS:
+            raise ValueError(f"TrainStep: weight_norm={weight_norm!r} ('sum': divide by the sum of the step's weights; 'count': by the number "
+                             f"of its clips)")
+        if class_weights is None and sample_weights is None:
+            return None, None, weight_norm
+        if task == "ssl":
+            raise ValueError("TrainStep: class_weights / sample_weights weigh the clips of the supervised criteria; task='ssl' has a "
+                             "regression loss and no classes")
+        dev = next(model.parameters()).device
+
+        def vector(value, name, length, what):
+            if torch.is_tensor(value):
+                if value.dtype != torch.float32 or value.device != dev:
+                    raise ValueError(f"TrainStep: {name} must be float32 on {dev} (the model's device), got {value.dtype} on {value.device}")
+                t = value
+            else:
+                t = torch.tensor([float(v) for v in value], dtype=torch.float32)
+            if t.dim() != 1 or (length is not None and t.numel() != length) or t.numel() < 1:
+                raise ValueError(f"TrainStep: {name} has shape {tuple(t.shape)}, expected ({length if length is not None else 'P'},): {what}")
+            host = t.detach().cpu()
+            if not bool(torch.isfinite(host).all()) or bool((host < 0).any()):
+                raise ValueError(f"TrainStep: {name} must be finite and >= 0 (a weight of 0 selects the clips out)")
+            return host, t.detach().to(dev).contiguous()
+
+        cw = sw = None
+        if class_weights is not None:
+            classes = 2 if task == "detection" else int(model.fc.weight.shape[0])
+            host, cw = vector(class_weights, "class_weights", classes,
+                              "one weight per class" + (" of the 0 / 1 labels: (1, p) is pos_weight=p" if task == "detection" else ""))
+            if not bool((host > 0).any()):
+                raise ValueError("TrainStep: class_weights are all zero: no clip would count")
+        if sample_weights is not None:
+            if not torch.is_tensor(sample_weights):
+                raise ValueError(f"TrainStep: sample_weights must be a float32 (P,) tensor on {dev}, one weight per clip of the pool, got "
+                                 f"{type(sample_weights).__name__}")
+            _, sw = vector(sample_weights, "sample_weights", None, "one weight per clip of the pool")
+        return cw, sw, weight_norm if weight_norm is not None else ("count" if task == "detection" else "sum")
+
+    def _step_weights(self, y, sampler, label_pool):
+        """this step's clip_u (B,) / denom (1,) in the buffers the step owns (`ops.clip_weights`, one launch).  With a sampler: from the
+        label pool through the sampler's perm and the cursor its gather has just advanced; else from the batch's own labels."""
+        b = int(y.shape[0])
+        if b not in self._weight_buffers:
+            dev = self.fp.flat.device
+            self._weight_buffers[b] = (torch.zeros(b, dtype=torch.float32, device=dev), torch.ones(1, dtype=torch.float32, device=dev))
+        clip_u, denom = self._weight_buffers[b]
+        if sampler is None:
+            labels = y.to(torch.float32 if self.task == "detection" else torch.int64).contiguous().view(-1)
+            ops.clip_weights(labels, clip_u, denom, class_w=self.class_weights, norm=self.weight_norm)
+        else:
+            ops.clip_weights(label_pool, clip_u, denom, class_w=self.class_weights, sample_w=self.sample_weights, norm=self.weight_norm,
+                             perm=sampler.perm, cursor=sampler.cursor, back=sampler.batch_size * sampler.world, rank=sampler.rank,
+                             world=sampler.world)
+        return clip_u, denom
+
+    def _check_step_weights(self, y, sampler, label_pool):
+        """what a weighted step refuses, before its first launch"""
+        if sampler is None:
+            if self.sample_weights is not None:
+                raise ValueError("TrainStep(sample_weights=...): the weights belong to the clips of a pool; step() / capture() see a batch "
+                                 "only -- use step_from() / capture_epoch() with the dataset and a sampler")
+            return
+        if label_pool is None or label_pool.dim() != 1:
+            raise ValueError("TrainStep(class_weights / sample_weights): a step from a sampler weighs its clips through the dataset's label "
+                             "pool (P,): forward_backward(..., sampler=, label_pool=dataset.y)")
+        if self.sample_weights is not None and self.sample_weights.numel() != label_pool.numel():
+            raise ValueError(f"TrainStep: sample_weights holds {self.sample_weights.numel()} weights, the pool {label_pool.numel()} clips")
+        if y.shape[0] != sampler.batch_size:
+            raise ValueError(f"TrainStep: a batch of {y.shape[0]} clips from a sampler of batch_size={sampler.batch_size}")
+
+    def loss_and_grad(self, out, y, clip_w=None, denom=None, clip_u=None):
         """(loss, d loss / d out) of the task's criterion from the fused HIP loss kernels (same values as `self.loss`).
-        clip_w / denom (device tensors of a drop_last=False sampler): over the clips that count, divided by denom"""
+        clip_w / denom (device tensors of a drop_last=False sampler): over the clips that count, divided by denom; clip_u / denom
+        (`_step_weights`, supervised tasks): a multiplier per clip instead"""
         E = torch.ops.eeg_dcrnn
         weights = () if clip_w is None else (clip_w, denom)
+        if clip_u is not None:
+            return E.bce_logits_cw(out.view(-1), y, clip_u, denom) if self.task == "detection" else E.ce_logits_cw(out, y, clip_u, denom)
         if self.task == "detection":
             return (E.bce_logits_w if weights else E.bce_logits)(out.view(-1), y, *weights)
         if self.task == "classification":
@@ -244,15 +335,23 @@ class TrainStep:
         return (E.masked_loss_w if weights else E.masked_loss)(out, y, scaled, float(self.scaler_mean) if scaled else 0.0,
                                                                float(self.scaler_std) if scaled else 1.0, 0.0, 1, *weights)
 
-    def forward_backward(self, x, y, seq_lengths, supports, sampler=None):
+    def forward_backward(self, x, y, seq_lengths, supports, sampler=None, label_pool=None):
         """supports=None: build the per-clip correlation graph and its dual random-walk supports from
         the clips on the device (the DataLoader-side `_get_indiv_graphs` of the reference).
         sampler: the `EpochSampler` whose gather filled x / y (`step_from` / `capture_epoch` pass theirs).  One that keeps the
         epoch's short last batch (drop_last=False) hands its device-resident `clip_w` / `denom` to the criterion and, for ssl, its
-        `n_valid` to the curriculum counter; everything in front of the criterion sees the B real clips of the batch tensors."""
+        `n_valid` to the curriculum counter; everything in front of the criterion sees the B real clips of the batch tensors.
+        label_pool: the data set's labels (P,), read by a step with class / sample weights through the sampler (`_step_weights`)."""
         tail = sampler is not None and not sampler.drop_last
         clip_w, denom = (sampler.clip_w, sampler.denom) if tail else (None, None)
+        clip_u = None
+        weighted = self.class_weights is not None or self.sample_weights is not None
+        if weighted:
+            self._check_step_weights(y, sampler, label_pool)
         self.fp.zero_grad()
+        if weighted:                      # the multipliers carry the validity of a short last batch: they take the selector's place
+            clip_u, denom = self._step_weights(y, sampler, label_pool)
+            clip_w = None
         perm, log_scale = None, None
         if self.data_augment and self.model.training:
             supports, perm, log_scale = self._draw_augmentation(x.shape[0], supports)
@@ -270,7 +369,8 @@ class TrainStep:
             drop_p = m._drop_p()
             with self.fp.sink:
                 loss, self.last_logits, dz = ops.cls_head_loss(last, m.fc.weight, m.fc.bias, y, self.task, drop_p,
-                                                               m._rng_state(last.device) if drop_p > 0 else None, clip_w=clip_w, denom=denom)
+                                                               m._rng_state(last.device) if drop_p > 0 else None, clip_w=clip_w, denom=denom,
+                                                               clip_u=clip_u)
                 last.backward(dz)
             return loss.detach()
         else:
@@ -278,7 +378,7 @@ class TrainStep:
         # The loss kernels return value AND gradient (d loss / d out) from one pass: backward is seeded with that gradient
         # directly -- `loss.backward()` would first fill a ones tensor and multiply the saved gradient by it (two framework
         # kernels per step for a factor of exactly 1).  `self.loss(out, y).backward()` remains the equivalent public path.
-        loss, seed = self.loss_and_grad(out.detach(), y, clip_w, denom)
+        loss, seed = self.loss_and_grad(out.detach(), y, clip_w, denom, clip_u)
         with self.fp.sink:                       # backward operators write into the flat gradient bucket
             out.backward(seed.view_as(out))
         return loss.detach()
@@ -523,7 +623,14 @@ class TrainStep:
             else:                         # whole clips: the constant lengths the model's last-step gather reads (ssl: None); a raw
                 lens, gathered = dataset.full_lengths(b, self.raw_window, "TrainStep(raw_window=...)"), False      # pool needs raw_window
             self._epoch_batches[key] = (dataset, x, y, lens, gathered)    # (the dataset is held: its id stays its own)
+        if self.class_weights is not None or self.sample_weights is not None:      # refused here, in front of the gather
+            self._check_step_weights(self._epoch_batches[key][2], sampler, self._label_pool(dataset))
         return self._epoch_batches[key][1:]
+
+    @staticmethod
+    def _label_pool(dataset):
+        """the data set's labels (P,) for a weighted step (None for a target pool: ssl, which takes no weights)"""
+        return None if dataset.y_is_target else dataset.y
 
     def _gather_batch(self, dataset, sampler, batch):
         x, y, lens, gathered = batch
@@ -536,10 +643,10 @@ class TrainStep:
         epoch is the caller's error and applies a zero gradient."""
         batch = self._epoch_batch(dataset, sampler)
         self._gather_batch(dataset, sampler, batch)
-        if sampler.drop_last:
+        if sampler.drop_last and self.class_weights is None and self.sample_weights is None:
             return self.step(batch[0], batch[1], batch[2], supports)
         # the epoch's short last batch is kept: the criterion runs over the clips that count, and so does `samples_seen`
-        loss = self.forward_backward(batch[0], batch[1], batch[2], supports, sampler=sampler)
+        loss = self.forward_backward(batch[0], batch[1], batch[2], supports, sampler=sampler, label_pool=self._label_pool(dataset))
         self._advance(0, sampler.take())
         self.reduce_and_update()
         return loss
@@ -560,7 +667,7 @@ class TrainStep:
 
         def body():
             self._gather_batch(dataset, sampler, batch)
-            loss = self.forward_backward(x, y, lens, supports, sampler=sampler)
+            loss = self.forward_backward(x, y, lens, supports, sampler=sampler, label_pool=self._label_pool(dataset))
             if include_update:
                 self.reduce_and_update(count=False)
             return loss

@@ -589,6 +589,35 @@ int eeg_dcrnn_ce_logits_w(const float* logits, const int64_t* y, int B, int C, c
                           float* dlogits, void* stream);
 int eeg_dcrnn_masked_loss_w(const float* pred, const float* y, size_t n, int B, const float* clip_w, const float* denom, int use_scaler,
                             float mean, float std_, float mask_val, int kind, float* loss, float* dpred, float* ws, void* stream);
+/* Class and sample weights.  The criteria with a MULTIPLIER per clip: clip_u (DEVICE float[B], every u_b >= 0) and denom (DEVICE
+ * float[1]) as written by eeg_dcrnn_clip_weights; loss[0] = (sum_b u_b * l_b) / denom[0], dlogits = (u_b * g_b) / denom[0] with l_b,
+ * g_b the clip's own criterion term and its gradient (hence dz, dW, dbias of the head).  u_b = w[y_b], denom = sum_b u_b is
+ * nn.CrossEntropyLoss(weight=w); u_b = y_b ? p : 1, denom = B is nn.BCEWithLogitsLoss(pos_weight=p) on 0/1 labels.  u_b == 0 selects
+ * the clip out as clip_w == 0 does in the _w entry points (its label is not looked at; logits and arg are still written).  Same
+ * launches and order of sums: clip_u = 1 and denom = B give the unweighted results bit for bit. */
+int eeg_dcrnn_cls_head_loss_cw(const float* z, const float* W, const float* bias, const void* targets, int kind, int B, int N,
+                               int H, int C, float dropout_p, const uint64_t* rng_used, const float* clip_u, const float* denom,
+                               float* logits, int32_t* arg, float* dlogits, float* dz, float* dW, float* dbias, float* loss, float* ws,
+                               void* stream);
+int eeg_dcrnn_bce_logits_cw(const float* logits, const float* y, int B, const float* clip_u, const float* denom, float* loss,
+                            float* dlogits, void* stream);
+int eeg_dcrnn_ce_logits_cw(const float* logits, const int64_t* y, int B, int C, const float* clip_u, const float* denom, float* loss,
+                           float* dlogits, void* stream);
+/* The multipliers of one step and their divisor, one launch of one workgroup, plain stores at fixed addresses (capturable):
+ *   u = valid * class_w[class(label)] * sample_w[src]      (class_w DEVICE float[C] or NULL with C = 0; sample_w DEVICE float[P] or NULL)
+ * class(label) = the int64 label (label_bytes 8; outside 0..C-1: weight 1) or label >= 0.5 ? 1 : 0 (label_bytes 4: detection's float
+ * labels, taken to be 0 or 1; C == 2).  clip_u[b] for this rank's B slots; denom[0] = D / world with norm 0: D = the sum of u over
+ * ALL slots of the step (a zero sum: D = 1), norm 1: D = max(number of valid slots, 1) -- behind the summed all-reduce and its
+ * 1 / world the gradient is sum u g / D.  The sum is float64 in a fixed order, rounded once.
+ * Sampler form (perm != NULL): labels is the label POOL (P entries), slot s of the step's B * world is the clip of
+ * eeg_dcrnn_gather_clips at position (cursor[0] - back) + s of perm (same wrap, clamp and validity rule as
+ * eeg_dcrnn_gather_clips_tail); back = 0 in front of the step's gather, B * world behind it (the gather has advanced the cursor).
+ * Every rank computes the same divisor bits from its own copy of the pool: no communication.
+ * Batch form (perm == NULL; cursor, sample_w NULL, back 0): labels are the batch's own B labels, every slot is valid and the divisor
+ * is the rank's own (world is taken as 1: data-parallel, the mean of the ranks' weighted means). */
+int eeg_dcrnn_clip_weights(const void* labels, int label_bytes, const int64_t* perm, int64_t n_perm, int64_t P, const int64_t* cursor,
+                           int64_t back, int B, int rank, int world, const float* class_w, int C, const float* sample_w, int norm,
+                           float* clip_u, float* denom, void* stream);
 /* clip_grad_norm_(max_norm) + torch.optim.Adam(lr, betas, eps, weight_decay = coupled L2) step
  * `step` (1-based) over flat fp32 buffers of n elements (train.py:222-223,273-275).  grads are
  * first multiplied by grad_scale (1/world_size after a summed all-reduce).  ws: 64 floats scratch;
