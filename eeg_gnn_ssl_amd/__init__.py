@@ -6,8 +6,9 @@ gfx950 behind a C ABI (include/eeg_dcrnn.h).
 """
 from . import ops, utils                                  # noqa: F401
 from .device_data import (BalancedEpochSampler, DeviceDataset, EpochSampler, RecordingDataset, clip_table_classification, clip_table_detection,      # noqa: F401
-                          clip_table_ssl, layout_recordings)
+                          clip_table_ssl, layout_recordings, clip_table_scan, clip_labels_detection, annotation_bins)
 from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
+from .scan import Scanner, ScanResult, scores_from_scan_record     # noqa: F401
 from .interpret import OcclusionResult, occlusion_maps     # noqa: F401
 from .statistics import ScalerFit, fit_scaler     # noqa: F401
 from .model.cell import DCGRUCell, DiffusionGraphConv     # noqa: F401
@@ -17,4 +18,5 @@ from .model.model import (DCGRUDecoder, DCRNNEncoder, DCRNNModel_classification,
 __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
            "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "BalancedEpochSampler", "RecordingDataset", "clip_table_detection",
            "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "OcclusionResult",
-           "occlusion_maps", "ScalerFit", "fit_scaler", "ops", "utils"]
+           "occlusion_maps", "ScalerFit", "fit_scaler", "clip_table_scan", "clip_labels_detection", "annotation_bins", "Scanner", "ScanResult",
+           "scores_from_scan_record", "ops", "utils"]

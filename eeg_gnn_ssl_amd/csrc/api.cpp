@@ -17,6 +17,7 @@
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
 #include "kernels_moments.h"
+#include "kernels_scan.h"
 #include "kernels_occlude.h"
 #include "kernels_data.h"
 #include "kernels_records.h"
@@ -1392,6 +1393,70 @@ int eeg_dcrnn_moments_record(const double* scores, int64_t P, double* record, vo
     if ((((uintptr_t)scores | (uintptr_t)record) & 7) != 0) return fail("moments_record: pointers must be aligned to their element size");
     EEG_LAUNCH_P("moments_record", moments_record_kernel, dim3(1), dim3(kMomThreads), kMomThreads * sizeof(double), S_(stream), scores, (int)P, record);
     return check_launch("moments_record");
+}
+
+/* ---- whole recordings: the timeline of a scan, its events, their scores --------------------------- */
+static_assert(EEG_SCAN_CHUNK_BINS == kScanChunkBins && EEG_SCAN_MAX_SMOOTH_BINS == kScanMaxSmoothBins && EEG_SCAN_RECORD_WORDS == kScanRecordWords,
+              "include/eeg_dcrnn.h and kernels_scan.h disagree");
+// the checks the three entry points share; `what` names the entry point in refusals
+static int scan_shape(const char* what, int64_t R, int64_t total_bins) {
+    if (R < 1 || R > EEG_SCAN_MAX_RECORDINGS) return fail("%s: R=%lld recordings unsupported (1..%d)", what, (long long)R, EEG_SCAN_MAX_RECORDINGS);
+    if (total_bins < 1 || total_bins >= ((int64_t)1 << 31)) return fail("%s: total_bins=%lld unsupported (1..2^31-1)", what, (long long)total_bins);
+    return 0;
+}
+int eeg_dcrnn_scan_timeline(const float* probs, int64_t P, const int64_t* clip_table, const int64_t* clip_off, const int64_t* bin_off, int64_t R,
+                            int64_t total_bins, int x_steps, int window, int agg, float* timeline, int32_t* cover, void* stream) {
+    if (probs == nullptr || clip_table == nullptr || clip_off == nullptr || bin_off == nullptr) return fail("scan_timeline: null probs / clip_table / clip_off / bin_off");
+    if (timeline == nullptr || cover == nullptr) return fail("scan_timeline: null timeline / cover");
+    if (scan_shape("scan_timeline", R, total_bins)) return 1;
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("scan_timeline: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (x_steps < 1 || window < 1) return fail("scan_timeline: x_steps=%d, window=%d (both >= 1)", x_steps, window);
+    if (agg != 0 && agg != 1) return fail("scan_timeline: agg=%d (0 = mean, 1 = max)", agg);
+    if ((((uintptr_t)probs | (uintptr_t)timeline | (uintptr_t)cover) & 3) != 0 || (((uintptr_t)clip_table | (uintptr_t)clip_off | (uintptr_t)bin_off) & 7) != 0)
+        return fail("scan_timeline: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("scan_timeline", scan_timeline_kernel, dim3((unsigned)((total_bins + 255) / 256)), dim3(256), 0, S_(stream), probs, (long long)P,
+                 reinterpret_cast<const long long*>(clip_table), reinterpret_cast<const long long*>(clip_off), reinterpret_cast<const long long*>(bin_off),
+                 (int)R, (long long)total_bins, x_steps, window, agg, timeline, cover);
+    return check_launch("scan_timeline");
+}
+int eeg_dcrnn_scan_events(const float* timeline, const int32_t* cover, const int64_t* bin_off, int64_t R, int64_t total_bins, int smooth_bins,
+                          float th_on, float th_off, int merge_gap, int min_bins, int E_max, float* smoothed, int32_t* events, int32_t* event_count,
+                          void* stream) {
+    if (timeline == nullptr || cover == nullptr || bin_off == nullptr) return fail("scan_events: null timeline / cover / bin_off");
+    if (smoothed == nullptr || events == nullptr || event_count == nullptr) return fail("scan_events: null smoothed / events / event_count");
+    if (scan_shape("scan_events", R, total_bins)) return 1;
+    if (smooth_bins < 1 || smooth_bins % 2 == 0 || smooth_bins > kScanMaxSmoothBins)
+        return fail("scan_events: smooth_bins=%d unsupported (odd, 1..%d)", smooth_bins, kScanMaxSmoothBins);
+    if (!(th_on == th_on) || !(th_off == th_off)) return fail("scan_events: a threshold is NaN");
+    if (th_off > th_on) return fail("scan_events: th_off=%g above th_on=%g", (double)th_off, (double)th_on);
+    if (merge_gap < 0 || min_bins < 1) return fail("scan_events: merge_gap=%d (>= 0), min_bins=%d (>= 1)", merge_gap, min_bins);
+    if (E_max < 1 || (long long)R * E_max >= (1ll << 30)) return fail("scan_events: E_max=%d events per recording unsupported (>= 1, R*E_max < 2^30)", E_max);
+    if ((((uintptr_t)timeline | (uintptr_t)cover | (uintptr_t)smoothed | (uintptr_t)events | (uintptr_t)event_count) & 3) != 0 || ((uintptr_t)bin_off & 7) != 0)
+        return fail("scan_events: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("scan_events", scan_events_kernel, dim3((unsigned)R), dim3(kScanThreads), kScanEventsLds, S_(stream), timeline, cover,
+                 reinterpret_cast<const long long*>(bin_off), (long long)total_bins, (smooth_bins - 1) / 2, th_on, th_off, merge_gap, min_bins, E_max,
+                 smoothed, events, event_count);
+    return check_launch("scan_events");
+}
+int eeg_dcrnn_event_scores(const int32_t* events, const int32_t* event_count, int E_max, const int32_t* ref, const int32_t* ref_count, int A_max,
+                           const int32_t* cover, const int64_t* bin_off, int64_t R, int64_t total_bins, int64_t* record, int64_t* rec_records,
+                           void* stream) {
+    if (events == nullptr || event_count == nullptr || ref == nullptr || ref_count == nullptr) return fail("event_scores: null events / event_count / ref / ref_count");
+    if (cover == nullptr || bin_off == nullptr || record == nullptr || rec_records == nullptr) return fail("event_scores: null cover / bin_off / record / rec_records");
+    if (scan_shape("event_scores", R, total_bins)) return 1;
+    if (E_max < 1 || (long long)R * E_max >= (1ll << 30)) return fail("event_scores: E_max=%d events per recording unsupported (>= 1, R*E_max < 2^30)", E_max);
+    if (A_max < 1 || (long long)R * A_max >= (1ll << 30)) return fail("event_scores: A_max=%d reference events per recording unsupported (>= 1, R*A_max < 2^30)", A_max);
+    if ((((uintptr_t)events | (uintptr_t)event_count | (uintptr_t)ref | (uintptr_t)ref_count | (uintptr_t)cover) & 3) != 0 ||
+        (((uintptr_t)bin_off | (uintptr_t)record | (uintptr_t)rec_records) & 7) != 0)
+        return fail("event_scores: pointers must be aligned to their element size");
+    hipStream_t st = S_(stream);
+    long long* recs = reinterpret_cast<long long*>(rec_records);
+    EEG_LAUNCH_P("event_scores", event_scores_kernel, dim3((unsigned)R), dim3(kScanThreads), kScanThreads * sizeof(long long), st, events, event_count, E_max,
+                 ref, ref_count, A_max, cover, reinterpret_cast<const long long*>(bin_off), (long long)total_bins, recs);
+    if (int rc = check_launch("event_scores")) return rc;
+    EEG_LAUNCH_P("event_scores_total", event_scores_total_kernel, dim3(1), dim3(kScanThreads), kScanThreads * sizeof(long long), st, recs, (int)R,
+                 reinterpret_cast<long long*>(record));
+    return check_launch("event_scores_total");
 }
 
 /* ---- occlusion maps: the variants of one window, their scores ------------------------------------- */

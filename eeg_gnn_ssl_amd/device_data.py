@@ -333,6 +333,88 @@ def clip_table_classification(rec_ids, seizure_times, seizure_idx, clip_len_s, f
     return _table(rec_ids, rows[:, 0], rows[:, 1], 0)
 
 
+# Whole recordings (scan.py): the strided windows of every recording as one table, their clip labels, annotations as bin intervals.
+def clip_table_scan(rec_samples, x_steps: int, stride_steps: int, window: int, cover_tail: bool = True):
+    """The sliding windows of whole recordings as one clip table.  Recording r has S_r = rec_samples[r] // window whole steps (a step
+    is one bin of `window` samples); with T = x_steps and s = stride_steps (1 <= s <= T) it gets no clip if S_r < T, else the
+    K_r = (S_r - T) // s + 1 clips starting at the steps 0, s, 2s, .. and -- cover_tail, (S_r - T) % s != 0 -- one more starting at
+    S_r - T, so that every whole step is covered.  -> (table (P, 4) int64 of rows (r, start_step*window, T*window, 0), ordered by
+    recording, then start; clip_off (R + 1,) int64: the rows clip_off[r] .. clip_off[r+1] are recording r's)."""
+    t, s, w = int(x_steps), int(stride_steps), int(window)
+    if t < 1 or w < 1:
+        raise ValueError(f"clip_table_scan: x_steps={x_steps}, window={window} (both >= 1)")
+    if not 1 <= s <= t:
+        raise ValueError(f"clip_table_scan: stride_steps={stride_steps} outside 1..x_steps={t} (a larger stride leaves steps uncovered)")
+    samples = [int(v) for v in np.asarray(rec_samples).reshape(-1)]
+    if not samples or min(samples) < 0:
+        raise ValueError(f"clip_table_scan: rec_samples must name at least one recording, each >= 0 samples, got {samples[:8]}")
+    rows, off = [], [0]
+    for r, n in enumerate(samples):
+        steps = n // w
+        if steps >= t:
+            starts = list(range(0, steps - t + 1, s))
+            if cover_tail and (steps - t) % s != 0:
+                starts.append(steps - t)
+            rows += [(r, a * w, t * w, 0) for a in starts]
+        off.append(len(rows))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 4), np.asarray(off, dtype=np.int64)
+
+
+def clip_labels_detection(table, seizure_times, freq: int = 200):
+    """The reference's clip label (data/dataloader_detection.py, computeSliceMatrix) for every row of a clip table: with
+    start_window = x_start and end_window = x_start + x_samples, 1 where `not (end_window < int(t0*freq) or start_window >
+    int(t1*freq))` holds for some annotated (t0, t1) of the clip's recording (both boundary cases count as seizure), else 0.
+    seizure_times[r]: the (start_s, end_s) pairs of recording r.  -> (P,) float32"""
+    table = np.asarray(table.cpu() if torch.is_tensor(table) else table)
+    if table.ndim != 2 or table.shape[1] != 4:
+        raise ValueError(f"clip_labels_detection: table must be (P, 4) = (rec, x_start, x_samples, y_start), got {table.shape}")
+    labels = np.zeros(table.shape[0], dtype=np.float32)
+    for p, (rec, start_window, x_samples, _) in enumerate(table.tolist()):
+        if not 0 <= rec < len(seizure_times):
+            raise ValueError(f"clip_labels_detection: clip {p} names recording rec={rec}, seizure_times has {len(seizure_times)}")
+        end_window = start_window + x_samples
+        for t in seizure_times[rec]:
+            start_t, end_t = int(t[0] * freq), int(t[1] * freq)
+            if not ((end_window < start_t) or (start_window > end_t)):
+                labels[p] = 1.0
+                break
+    return labels
+
+
+def annotation_bins(seizure_times, rec_samples, window: int, freq: int = 200):
+    """Annotated (start_s, end_s) pairs per recording as half-open BIN intervals [floor(t0*freq/window), ceil(t1*freq/window)), clipped
+    to the recording's S_r = rec_samples[r] // window whole steps, empty ones dropped, overlapping or touching ones merged, sorted.
+    -> (ref (R, A_max, 2) int32, zero rows behind a recording's intervals, A_max >= 1; ref_count (R,) int32): what `ops.event_scores`
+    reads."""
+    samples = [int(v) for v in np.asarray(rec_samples).reshape(-1)]
+    if len(seizure_times) != len(samples) or not samples:
+        raise ValueError(f"annotation_bins: seizure_times names {len(seizure_times)} recordings, rec_samples {len(samples)}")
+    w = int(window)
+    if w < 1 or freq <= 0:
+        raise ValueError(f"annotation_bins: window={window}, freq={freq} (both positive)")
+    per_rec = []
+    for times, n in zip(seizure_times, samples):
+        steps = n // w
+        ivs = []
+        for t0, t1 in times:
+            a = min(max(int(np.floor(t0 * freq / w)), 0), steps)
+            b = min(max(int(np.ceil(t1 * freq / w)), 0), steps)
+            if b > a:
+                ivs.append((a, b))
+        merged = []
+        for a, b in sorted(ivs):
+            if merged and a <= merged[-1][1]:
+                merged[-1] = (merged[-1][0], max(merged[-1][1], b))
+            else:
+                merged.append((a, b))
+        per_rec.append(merged)
+    ref = np.zeros((len(samples), max(1, max(len(m) for m in per_rec)), 2), dtype=np.int32)
+    for r, m in enumerate(per_rec):
+        if m:
+            ref[r, :len(m)] = np.asarray(m, dtype=np.int32)
+    return ref, np.asarray([len(m) for m in per_rec], dtype=np.int32)
+
+
 class EpochSampler:
     """The epoch's shuffle and the position in it, on the device: `perm` (P,) int64, `cursor` (1,) int64, `epoch`.
 

@@ -13,7 +13,7 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    feature_moments, moments_record, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
+    feature_moments, moments_record, scan_timeline, scan_events, event_scores, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1784,6 +1785,110 @@ _define("feature_moments", "(Tensor raw, Tensor? lengths, Tensor? clip_w, Tensor
 _define("moments_record", "(Tensor scores, Tensor(a!) record) -> ()", _moments_record_impl, lambda *a: None)
 
 
+# ---- whole recordings: timeline, events, event scores (scan.py: Scanner; csrc/kernels_scan.h) ----------------------------------------
+SCAN_CHUNK_BINS = 2048                # EEG_SCAN_CHUNK_BINS: bins of a recording `scan_events` holds in LDS at a time
+SCAN_MAX_SMOOTH_BINS = 129            # EEG_SCAN_MAX_SMOOTH_BINS
+SCAN_MAX_RECORDINGS = 1 << 20         # EEG_SCAN_MAX_RECORDINGS
+SCAN_RECORD_WORDS = 10                # EEG_SCAN_RECORD_WORDS: int64 words of a score record
+SCAN_RECORD = ("n_ref", "n_hyp", "ref_hit", "hyp_hit", "covered_bins", "tp", "fp", "fn", "tn", "overflowed")
+SCAN_AGG = {"mean": 0, "max": 1}      # eeg_dcrnn_scan_timeline `agg`
+
+
+def _scan_tensor(what, name, t, dtype, shape, dev):
+    """the operands of the scan operators are read / written ON THE DEVICE as they are (None in shape: any extent >= 1)"""
+    ok = torch.is_tensor(t) and t.dtype == dtype and t.dim() == len(shape) and t.device == dev and t.is_contiguous() and \
+        all((v >= 1) if w is None else (v == w) for v, w in zip(t.shape, shape))
+    if not ok:
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        want = "(" + ", ".join("*" if w is None else str(w) for w in shape) + ("," if len(shape) == 1 else "") + ")"
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {want} on {dev}, got {got}")
+
+
+def _scan_bins(what, lib, bin_off, per_bin):
+    """(R, total_bins, device) of a scan operator from bin_off (R + 1,) and its first per-bin tensor"""
+    if not torch.is_tensor(per_bin) or per_bin.dim() != 1 or per_bin.numel() < 1:
+        got = f"{tuple(per_bin.shape)}" if torch.is_tensor(per_bin) else type(per_bin).__name__
+        raise ValueError(f"{what}: the per-bin tensors are (total_bins,) with total_bins >= 1 (ops.scan_buffers), got {got}")
+    dev = per_bin.device
+    if lib.is_device_build and not per_bin.is_cuda:
+        raise ValueError(f"{what}: the tensors are on {dev}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    _scan_tensor(what, "bin_off", bin_off, torch.int64, (None,), dev)
+    r = bin_off.numel() - 1
+    if not 1 <= r <= SCAN_MAX_RECORDINGS:
+        raise ValueError(f"{what}: bin_off has {bin_off.numel()} entries: R + 1 for 1..{SCAN_MAX_RECORDINGS} recordings")
+    if per_bin.numel() >= 1 << 31:
+        raise ValueError(f"{what}: total_bins={per_bin.numel()} bins; at most 2^31 - 1")
+    return r, int(per_bin.numel()), dev
+
+
+def _scan_timeline_impl(probs, clip_table, clip_off, bin_off, x_steps: int, window: int, agg: int, timeline, cover) -> None:
+    lib = _lib.get_lib()
+    what = "scan_timeline"
+    r, total, dev = _scan_bins(what, lib, bin_off, timeline)
+    _scan_tensor(what, "timeline", timeline, torch.float32, (total,), dev)
+    _scan_tensor(what, "cover", cover, torch.int32, (total,), dev)
+    _scan_tensor(what, "probs", probs, torch.float32, (None,), dev)
+    p = int(probs.numel())
+    if p > EVAL_MAX_CLIPS:
+        raise ValueError(f"{what}: P={p} clips exceed the limit of one pass, {EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    _scan_tensor(what, "clip_table", clip_table, torch.int64, (p, 4), dev)
+    _scan_tensor(what, "clip_off", clip_off, torch.int64, (r + 1,), dev)
+    if x_steps < 1 or window < 1:
+        raise ValueError(f"{what}: x_steps={x_steps}, window={window} (both >= 1)")
+    if agg not in (0, 1):
+        raise ValueError(f"{what}: agg={agg} (0 = mean, 1 = max)")
+    lib.call("eeg_dcrnn_scan_timeline", _p(probs), p, _p(clip_table), _p(clip_off), _p(bin_off), r, total, int(x_steps), int(window), int(agg),
+             _p(timeline), _p(cover), _stream(timeline))
+
+
+def _scan_events_impl(timeline, cover, bin_off, smooth_bins: int, th_on: float, th_off: float, merge_gap: int, min_bins: int, smoothed, events,
+                      event_count) -> None:
+    lib = _lib.get_lib()
+    what = "scan_events"
+    r, total, dev = _scan_bins(what, lib, bin_off, timeline)
+    _scan_tensor(what, "timeline", timeline, torch.float32, (total,), dev)
+    _scan_tensor(what, "cover", cover, torch.int32, (total,), dev)
+    _scan_tensor(what, "smoothed", smoothed, torch.float32, (total,), dev)
+    if not torch.is_tensor(events) or events.dim() != 3 or events.shape[1] < 1:
+        got = f"{tuple(events.shape)}" if torch.is_tensor(events) else type(events).__name__
+        raise ValueError(f"{what}: events must be (R, E_max, 2) int32 with E_max >= 1 (E_max < 1 holds no event), got {got}")
+    _scan_tensor(what, "events", events, torch.int32, (r, None, 2), dev)
+    _scan_tensor(what, "event_count", event_count, torch.int32, (r,), dev)
+    if smooth_bins < 1 or smooth_bins % 2 == 0 or smooth_bins > SCAN_MAX_SMOOTH_BINS:
+        raise ValueError(f"{what}: smooth_bins={smooth_bins} must be odd, 1..{SCAN_MAX_SMOOTH_BINS} (a centred window; 1 = no smoothing)")
+    if th_on != th_on or th_off != th_off:
+        raise ValueError(f"{what}: a threshold is NaN (th_on={th_on}, th_off={th_off})")
+    if th_off > th_on:
+        raise ValueError(f"{what}: th_off={th_off} above th_on={th_on} (hysteresis: on at th_on, off below th_off <= th_on)")
+    if merge_gap < 0 or min_bins < 1:
+        raise ValueError(f"{what}: merge_gap={merge_gap} (>= 0), min_bins={min_bins} (>= 1)")
+    lib.call("eeg_dcrnn_scan_events", _p(timeline), _p(cover), _p(bin_off), r, total, int(smooth_bins), float(th_on), float(th_off), int(merge_gap),
+             int(min_bins), int(events.shape[1]), _p(smoothed), _p(events), _p(event_count), _stream(timeline))
+
+
+def _event_scores_impl(events, event_count, ref, ref_count, cover, bin_off, record, rec_records) -> None:
+    lib = _lib.get_lib()
+    what = "event_scores"
+    r, total, dev = _scan_bins(what, lib, bin_off, cover)
+    _scan_tensor(what, "cover", cover, torch.int32, (total,), dev)
+    _scan_tensor(what, "events", events, torch.int32, (r, None, 2), dev)
+    _scan_tensor(what, "event_count", event_count, torch.int32, (r,), dev)
+    _scan_tensor(what, "ref", ref, torch.int32, (r, None, 2), dev)
+    _scan_tensor(what, "ref_count", ref_count, torch.int32, (r,), dev)
+    _scan_tensor(what, "record", record, torch.int64, (SCAN_RECORD_WORDS,), dev)
+    _scan_tensor(what, "rec_records", rec_records, torch.int64, (r, SCAN_RECORD_WORDS), dev)
+    lib.call("eeg_dcrnn_event_scores", _p(events), _p(event_count), int(events.shape[1]), _p(ref), _p(ref_count), int(ref.shape[1]), _p(cover),
+             _p(bin_off), r, total, _p(record), _p(rec_records), _stream(cover))
+
+
+_define("scan_timeline", "(Tensor probs, Tensor clip_table, Tensor clip_off, Tensor bin_off, int x_steps, int window, int agg, Tensor(a!) timeline, "
+        "Tensor(b!) cover) -> ()", _scan_timeline_impl, lambda *a: None)
+_define("scan_events", "(Tensor timeline, Tensor cover, Tensor bin_off, int smooth_bins, float th_on, float th_off, int merge_gap, int min_bins, "
+        "Tensor(a!) smoothed, Tensor(b!) events, Tensor(c!) event_count) -> ()", _scan_events_impl, lambda *a: None)
+_define("event_scores", "(Tensor events, Tensor event_count, Tensor ref, Tensor ref_count, Tensor cover, Tensor bin_off, Tensor(a!) record, "
+        "Tensor(b!) rec_records) -> ()", _event_scores_impl, lambda *a: None)
+
+
 # ---- occlusion maps on the device (interpret.py: occlusion_maps) -------------------------------------------------------------------
 OCCLUDE_MAX_LAYERS = 4       # EEG_OCCLUDE_MAX_LAYERS
 OCCLUDE_MAX_GROUPS = 64       # EEG_OCCLUDE_MAX_GROUPS
@@ -2785,6 +2890,141 @@ def moments_record(scores, record=None):
     if record is None:
         record = torch.zeros(MOMENTS_RECORD_WORDS, dtype=torch.float64, device=scores.device if torch.is_tensor(scores) else None)
     torch.ops.eeg_dcrnn.moments_record(scores, record)
+    return record
+
+
+class ScanBuffers:
+    """the tensors of one scan's post-processing (`scan_buffers`): bin_off (R + 1,) int64; timeline, smoothed (total_bins,) float32;
+    cover (total_bins,) int32; events (R, E_max, 2) int32; event_count (R,) int32; record (SCAN_RECORD_WORDS,) and rec_records (R,
+    SCAN_RECORD_WORDS) int64"""
+
+    def __init__(self, rec_steps, max_events: int, device, zeroed: bool = True):
+        steps = [int(v) for v in rec_steps]
+        if not 1 <= len(steps) <= SCAN_MAX_RECORDINGS or min(steps) < 0:
+            raise ValueError(f"scan_buffers: rec_steps names {len(steps)} recordings (1..{SCAN_MAX_RECORDINGS}) of >= 0 whole steps each")
+        off = [0]
+        for v in steps:
+            off.append(off[-1] + v)
+        if not 1 <= off[-1] < 1 << 31:
+            raise ValueError(f"scan_buffers: the recordings hold {off[-1]} whole steps in all (1..2^31-1): nothing to scan")
+        if int(max_events) < 1:
+            raise ValueError(f"scan_buffers: max_events={max_events}: E_max < 1 holds no event")
+        r, total = len(steps), off[-1]
+        self.bin_off = torch.tensor(off, dtype=torch.int64, device=device)
+        new = torch.zeros if zeroed else torch.empty                     # (the kernels write every element of every output)
+        self.timeline = new(total, dtype=torch.float32, device=device)
+        self.smoothed = new(total, dtype=torch.float32, device=device)
+        self.cover = new(total, dtype=torch.int32, device=device)
+        self.events = new((r, int(max_events), 2), dtype=torch.int32, device=device)
+        self.event_count = new(r, dtype=torch.int32, device=device)
+        self.record = new(SCAN_RECORD_WORDS, dtype=torch.int64, device=device)
+        self.rec_records = new((r, SCAN_RECORD_WORDS), dtype=torch.int64, device=device)
+
+
+def scan_buffers(rec_steps, max_events: int, device, zeroed: bool = True):
+    """The buffers of `scan_timeline` / `scan_events` / `event_scores` for recordings of rec_steps[r] whole steps (bins) each and at
+    most max_events events per recording, as a `ScanBuffers` (zeroed, or uninitialised: the kernels write every element); allocated
+    once per result by the caller (`scan.Scanner`)"""
+    return ScanBuffers(rec_steps, max_events, device, zeroed)
+
+
+def _monotone(what, name, t, last=None):
+    """host check (one small device-to-host copy) of an offset table: starts at 0, never decreases, ends at `last`"""
+    if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 2:
+        return None                                                      # (the operator refuses it by shape and dtype)
+    v = t.cpu().tolist()
+    if v[0] != 0 or any(b < a for a, b in zip(v, v[1:])) or (last is not None and v[-1] != last):
+        raise ValueError(f"{what}: {name} is not a monotone offset table from 0" + ("" if last is None else f" to {last}") +
+                         f" (first offending entries: {v[:8]})")
+    return v
+
+
+def scan_check_tables(clip_table, clip_off, bin_off, x_steps: int, window: int, num_clips=None, total_bins=None, what: str = "scan_timeline"):
+    """Host validation of the tables of a scan (device-to-host copies: call it once per table, `Scanner` does): bin_off and clip_off
+    monotone from 0 (to total_bins / P), and the rows of every recording name it, start at whole, strictly ascending steps and are all
+    x_steps*window samples long -- what `clip_table_scan` builds.  Anything else raises ValueError."""
+    _monotone(what, "bin_off", bin_off, total_bins)
+    off = _monotone(what, "clip_off", clip_off, num_clips)
+    if off is None or not torch.is_tensor(clip_table) or clip_table.dim() != 2 or clip_table.shape[1] != 4 or clip_table.dtype != torch.int64:
+        return
+    table = clip_table.cpu().numpy()
+    if off[-1] != table.shape[0]:
+        raise ValueError(f"{what}: clip_off ends at {off[-1]}, the table has {table.shape[0]} rows")
+    for r in range(len(off) - 1):
+        rows = table[off[r]:off[r + 1]]
+        if not len(rows):
+            continue
+        if (rows[:, 0] != r).any():
+            raise ValueError(f"{what}: rows {off[r]}..{off[r + 1]} of the table belong to recording {r} by clip_off and name another one")
+        if (rows[:, 2] != x_steps * window).any():
+            raise ValueError(f"{what}: the rows of recording {r} are not all x_steps*window = {x_steps * window} samples long (clip_table_scan)")
+        if (rows[:, 1] < 0).any() or (rows[:, 1] % window != 0).any() or (np.diff(rows[:, 1]) <= 0).any():
+            raise ValueError(f"{what}: the rows of recording {r} do not start at whole, ascending steps of {window} samples (clip_table_scan)")
+
+
+def _same_device(what, anchor_name, anchor, **tensors):
+    for name, t in tensors.items():
+        if torch.is_tensor(t) and torch.is_tensor(anchor) and t.device != anchor.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, {anchor_name} on {anchor.device}: one device")
+
+
+def scan_timeline(probs, clip_table, clip_off, bin_off, timeline, cover, *, x_steps: int, window: int, agg: str = "mean", validate: bool = True):
+    """The per-bin probability timeline of whole recordings from the probabilities of their overlapping clips (one bin = one step of
+    `window` samples).  probs (P,) float32, one per row of clip_table (P, 4) int64; recording r owns the rows clip_off[r] ..
+    clip_off[r+1] and the bins bin_off[r] .. bin_off[r+1] (`clip_table_scan`, `scan_buffers`).  Bin j of a recording is covered by its
+    rows with start_step <= j < start_step + x_steps -- found from the start steps in the table by binary search, a gather -- and
+    gets agg="mean": the float32 sum of their probabilities in ascending row order over float(cover), or agg="max": their maximum;
+    an uncovered bin gets 0 and cover 0.  Every element of timeline (total_bins,) float32 and cover (total_bins,) int32 is written.
+    validate: check the tables on the host first (`scan_check_tables`; two small copies).  Returns (timeline, cover)."""
+    if agg not in SCAN_AGG:
+        raise ValueError(f"scan_timeline: agg={agg!r} (one of {sorted(SCAN_AGG)})")
+    _same_device("scan_timeline", "timeline", timeline, probs=probs, clip_table=clip_table, clip_off=clip_off, bin_off=bin_off, cover=cover)
+    if validate:
+        scan_check_tables(clip_table, clip_off, bin_off, int(x_steps), int(window), probs.numel() if torch.is_tensor(probs) else None,
+                          timeline.numel() if torch.is_tensor(timeline) else None)
+    torch.ops.eeg_dcrnn.scan_timeline(probs, clip_table, clip_off, bin_off, int(x_steps), int(window), SCAN_AGG[agg], timeline, cover)
+    return timeline, cover
+
+
+def scan_thresholds(th_on, th_off=None):
+    """(th_on, th_off) rounded to float32 ONCE, as Python floats: the values the kernel compares with (th_off None: th_on)"""
+    on = float(th_on)
+    off = on if th_off is None else float(th_off)
+    if on != on or off != off:
+        raise ValueError(f"scan_events: a threshold is NaN (th_on={th_on}, th_off={th_off})")
+    if off > on:
+        raise ValueError(f"scan_events: th_off={off} above th_on={on} (hysteresis: on at th_on, off below th_off <= th_on)")
+    return float(np.float32(on)), float(np.float32(off))
+
+
+def scan_events(timeline, cover, bin_off, smoothed, events, event_count, *, smooth_bins: int = 1, th_on: float = 0.5, th_off=None,
+                merge_gap: int = 0, min_bins: int = 1, validate: bool = True):
+    """Seizure events of every recording from its timeline, one workgroup per recording, bins streamed through LDS in chunks of
+    SCAN_CHUNK_BINS.  Per recording: q_j = the float32 ascending sum of the timeline over the covered bins of [j-h, j+h] inside the
+    recording over their number, h = (smooth_bins-1)/2 (odd, <= SCAN_MAX_SMOOTH_BINS; 0 for an uncovered j) -> smoothed; state_j on if
+    q_j >= th_on, off if q_j < th_off or j is uncovered, else state_{j-1} (thresholds rounded to float32 once here); maximal runs of on
+    are events [onset, offset); a run at most merge_gap off bins behind the event before it is merged into it (chains); events shorter
+    than min_bins are then dropped.  events (R, E_max, 2) int32 in order with zero rows behind them, event_count (R,) int32 the TRUE
+    number -- it may exceed E_max, the rows behind E_max are never written.  Returns (smoothed, events, event_count); no host sync
+    with validate=False (validate: bin_off monotone, one small copy)."""
+    on, off = scan_thresholds(th_on, th_off)
+    _same_device("scan_events", "timeline", timeline, cover=cover, bin_off=bin_off, smoothed=smoothed, events=events, event_count=event_count)
+    if validate:
+        _monotone("scan_events", "bin_off", bin_off, timeline.numel() if torch.is_tensor(timeline) else None)
+    torch.ops.eeg_dcrnn.scan_events(timeline, cover, bin_off, int(smooth_bins), on, off, int(merge_gap), int(min_bins), smoothed, events, event_count)
+    return smoothed, events, event_count
+
+
+def event_scores(events, event_count, ref, ref_count, cover, bin_off, record, rec_records, *, validate: bool = True):
+    """Event- and bin-level scores of detected events against reference intervals (`annotation_bins`: ref (R, A_max, 2) int32 half-open
+    bin intervals, ref_count (R,) int32) as int64 words named by SCAN_RECORD: per recording in rec_records (R, SCAN_RECORD_WORDS), summed
+    in record: n_ref, n_hyp = min(event_count, E_max), ref_hit / hyp_hit (events of one side sharing a bin with one of the other),
+    covered_bins, tp / fp / fn / tn over the covered bins, overflowed (recordings with event_count > E_max).  Returns record."""
+    _same_device("event_scores", "cover", cover, events=events, event_count=event_count, ref=ref, ref_count=ref_count, bin_off=bin_off,
+                 record=record, rec_records=rec_records)
+    if validate:
+        _monotone("event_scores", "bin_off", bin_off, cover.numel() if torch.is_tensor(cover) else None)
+    torch.ops.eeg_dcrnn.event_scores(events, event_count, ref, ref_count, cover, bin_off, record, rec_records)
     return record
 
 

@@ -718,6 +718,15 @@ class TrainStep:
         return DeviceSSLEvaluator(self, dataset, batch_size, supports=supports, rank=rank, world=world, keep_predictions=keep_predictions,
                                   loss_batch=loss_batch)
 
+    def scanner(self, recordings, x_steps: int, stride_steps: int, batch_size: int = 256, supports=None, cover_tail: bool = True,
+                max_events: int = 64, freq: int = 200, rank: Optional[int] = None, world: Optional[int] = None):
+        """scan WHOLE recordings with this step's detector and data chain on the device (`scan.Scanner`): sliding windows of x_steps
+        steps every stride_steps, the evaluator's pass over them, then a per-second timeline, seizure events and event scores:
+        `sc = step.scanner(recordings, x_steps=60, stride_steps=12); res = sc.run(th_on=0.6, th_off=0.4, annotations=(ref, ref_count))`"""
+        from .scan import Scanner
+        return Scanner(self, recordings, x_steps, stride_steps, batch_size=batch_size, supports=supports, cover_tail=cover_tail,
+                       max_events=max_events, freq=freq, rank=rank, world=world)
+
     def fit_scaler(self, dataset, batch_size: int = 256):
         """Fit this step's input scaler on the device (`statistics.fit_scaler`): the mean and std of the un-standardised inputs the
         step's raw chain produces for `dataset` -- log|FFT| features, or with use_fft=False the samples -- over its clips (valid steps

@@ -497,6 +497,45 @@ int eeg_dcrnn_feature_moments(const float* raw, int B, int N, int T, int W, int 
                               const int64_t* cursor, int rank, int world, int64_t P, void* ws, double* scores, void* stream);
 int eeg_dcrnn_moments_record(const double* scores, int64_t P, double* record, void* stream);
 
+/* Whole recordings behind the detection head: a scan's per-bin timeline, seizure events from it, their scores.  A bin is one step of
+ * `window` samples.  R recordings; recording r owns the bins bin_off[r] .. bin_off[r+1] (int64 (R+1): prefix sums of the recordings'
+ * whole steps, total_bins = bin_off[R] < 2^31) of every flat per-bin buffer, and the rows clip_off[r] .. clip_off[r+1] (int64 (R+1)) of
+ * the clip table (int64 (P, 4) = (rec, x_start, x_samples, y_start), eeg_dcrnn_gather_records), whose rows start at ascending whole steps
+ * within a recording and are x_steps steps long.  All pointers are device memory.  No allocation, no host synchronisation, no atomics,
+ * every float sum in ascending index order; EVERY output element is written by EVERY launch, and every index derived from a table is
+ * clamped: whatever the tables hold, nothing is read or written outside the buffers as sized here.
+ *
+ * eeg_dcrnn_scan_timeline: probs (P) float32, one per table row -> timeline (total_bins) float32, cover (total_bins) int32.  Bin j of
+ * recording r is covered by the rows of r with start_step <= j < start_step + x_steps (start_step = x_start / window, read from the
+ * table; found by binary search: a gather).  agg 0: the float32 sum of the covering probabilities in ascending row order, divided by
+ * float(cover); agg 1: their maximum; an uncovered bin: value 0, cover 0.
+ *
+ * eeg_dcrnn_scan_events: per recording over its bins 0 .. S-1, one workgroup each, the bins streamed through LDS in chunks of
+ * EEG_SCAN_CHUNK_BINS: q_j = the float32 ascending sum of timeline_i over the COVERED i in [j-h, j+h] and [0, S), over their number,
+ * h = (smooth_bins - 1) / 2 (smooth_bins odd, 1 .. EEG_SCAN_MAX_SMOOTH_BINS; an uncovered j: 0) -> smoothed (total_bins); state_j = on
+ * if q_j >= th_on, off if q_j < th_off or j is uncovered, else state_{j-1} (state_{-1} off; th_off <= th_on); maximal runs of on are
+ * events [a, b); a run at most merge_gap off bins behind the event before it is merged into it (left to right, chains; 0 merges
+ * nothing); events shorter than min_bins are then dropped.  events (R, E_max, 2) int32 = (onset, offset exclusive) in order, zero rows
+ * behind them; event_count (R) int32 = the TRUE number of events of the recording, which may exceed E_max: such rows are not written.
+ *
+ * eeg_dcrnn_event_scores: events / event_count as above, ref (R, A_max, 2) int32 half-open reference intervals in bins, ref_count (R)
+ * int32 -> rec_records (R, EEG_SCAN_RECORD_WORDS) int64 per recording and record (EEG_SCAN_RECORD_WORDS) int64, their word-wise sum:
+ * 0 n_ref, 1 n_hyp = min(event_count, E_max), 2 ref_hit: reference events sharing a bin with a detected event, 3 hyp_hit: detected
+ * events sharing a bin with a reference event, 4 covered_bins, 5..8 tp, fp, fn, tn over the covered bins (positive inside a reference
+ * interval, predicted inside a detected event), 9 overflowed: recordings with event_count > E_max. */
+#define EEG_SCAN_CHUNK_BINS 2048
+#define EEG_SCAN_MAX_SMOOTH_BINS 129
+#define EEG_SCAN_RECORD_WORDS 10
+#define EEG_SCAN_MAX_RECORDINGS (1 << 20)
+int eeg_dcrnn_scan_timeline(const float* probs, int64_t P, const int64_t* clip_table, const int64_t* clip_off, const int64_t* bin_off, int64_t R,
+                            int64_t total_bins, int x_steps, int window, int agg, float* timeline, int32_t* cover, void* stream);
+int eeg_dcrnn_scan_events(const float* timeline, const int32_t* cover, const int64_t* bin_off, int64_t R, int64_t total_bins, int smooth_bins,
+                          float th_on, float th_off, int merge_gap, int min_bins, int E_max, float* smoothed, int32_t* events, int32_t* event_count,
+                          void* stream);
+int eeg_dcrnn_event_scores(const int32_t* events, const int32_t* event_count, int E_max, const int32_t* ref, const int32_t* ref_count, int A_max,
+                           const int32_t* cover, const int64_t* bin_off, int64_t R, int64_t total_bins, int64_t* record, int64_t* rec_records,
+                           void* stream);
+
 /* Occlusion maps on the device: group g of channels of clip b is overwritten with `fill` over the window of steps [t0, t0 + w) and the
  * map records how far the predicted probability drops.  All variants of a window start from the unoccluded clip's state at t0.
  *
