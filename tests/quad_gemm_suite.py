@@ -288,11 +288,11 @@ def reference(case, op, cotangents, dtype=torch.float64):
 _REF_CACHE = {}
 
 
-def cached_reference(name, t, b, seed, rps_sparse):
+def cached_reference(name, t, b, seed, rps_sparse, case=None):
     """the reference of a case at (T, B), computed once per process for the dense cotangent and -- SPARSE_CASES -- the sparse one"""
     key = (name, t, b, seed, rps_sparse)
     if key not in _REF_CACHE:
-        case = CASES[name]
+        case = case if case is not None else CASES[name]
         op = make_operands(case, t, b, seed)
         cots = [(op["w"], op["wsel"])]
         if rps_sparse is not None:
@@ -366,12 +366,14 @@ def assert_roles(ran, expect, what, exact=True):
     assert got == want, f"{what}: kernels that ran {got}, expected {want}"
 
 
-def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0, report=None, exact=True, dims=None):
+def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0, report=None, exact=True, dims=None, case=None,
+               grad_tol=GRAD_TOL):
     """One case: the layer on `device` against the float64 reference (hseq under assert_close, every gradient under
     assert_close_scaled(tol=5e-5)), after the proof that the expected kernels took its GEMMs.  sparse: the cotangent lives on three clips
     (first, last, and the one across the first row-split boundary of the case's quad TN kernel, read from the plan driver `exe`), so
-    that a row dropped, doubled or misplaced at a split or tile edge is measured against a few hundred rows' worth of gradient."""
-    case = CASES[name]
+    that a row dropped, doubled or misplaced at a split or tile edge is measured against a few hundred rows' worth of gradient.
+    case: a case of another table in this format (tests/split_gemm_suite.py), at the `dims` it names; grad_tol: its gradient bound."""
+    case = case if case is not None else CASES[name]
     t, b, r = dims if dims is not None else case_dims(case, rows_min)
     rps = None
     if exe is not None and name in SPARSE_CASES:  # (the reference of such a case carries both cotangents: one float64 forward)
@@ -379,7 +381,7 @@ def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0,
         rps = splits["gemm_tn_x"] if is_quad(roles["gemm_tn_x"]) else splits["gemm_tn_hg"]
         assert rps < r, (name, rps, r)
     assert rps is not None or not sparse
-    op, cots, ref_hseq, ref_grads = cached_reference(name, t, b, seed, rps)
+    op, cots, ref_hseq, ref_grads = cached_reference(name, t, b, seed, rps, case)
     which = 1 if sparse else 0
     run = run_layer(case, op, *cots[which], device)
     run()                                                                                 # (first call: allocations)
@@ -398,7 +400,7 @@ def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0,
         report[what] = errs
     ps.assert_close(hseq.cpu().numpy(), ref_hseq.numpy(), f"{what}: hseq")
     for k, g in grads.items():
-        ps.assert_close_scaled(g.detach().cpu().numpy(), ref_grads[which][k].numpy(), f"{what}: {k}", tol=GRAD_TOL)
+        ps.assert_close_scaled(g.detach().cpu().numpy(), ref_grads[which][k].numpy(), f"{what}: {k}", tol=grad_tol)
     if sparse:                                    # clips without a cotangent: not one bit of gradient reaches their inputs
         keep = sparse_clips(b, case["n"], rps)
         rest = [i for i in range(b) if i not in keep]

@@ -9,6 +9,7 @@ import parity_suite as ps
 import quad_gemm_suite as qg
 import seq_kernel_suite as sk
 import spec_plan_suite as sp
+import split_gemm_suite as sg
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -267,6 +268,42 @@ def test_quad_gemm_case_table(emulator, name):
         qg.check_case(name, "cpu", None, exact=False, dims=qg.emu_dims(qg.CASES[name]))
     finally:
         emulator.call("eeg_dcrnn_set_tuning", 2, 0)
+
+
+@pytest.mark.parametrize("name", list(sg.DCONV_CASES))
+def test_split_gemm_dconv_case_table(emulator, plan_driver, name):
+    """The dconv table of tests/split_gemm_suite.py (one call per reachable instance of the split GEMMs; on the MI355X:
+    tests/test_split_gemm.py) at emulator row counts (split_gemm_suite.emu_dims: at most 304 rows).  There every NN GEMM is planned
+    with the column block of 2 tiles, so the table's symbols are compared by kernel name and the instance with the plan driver's answer
+    for the emulator's call.  Same float64 reference, same tolerances."""
+    sg.check_dconv(name, "cpu", plan_driver, qg.EMU_CUS, dims=sg.emu_dims(sg.DCONV_CASES[name]["dims"]), exact=False)
+
+
+def test_split_gemm_dconv_sparse_cotangent(emulator, plan_driver):
+    """the widest case of the table with a cotangent on four clips: clip 0, the last one and the two across the row-split boundaries"""
+    sg.check_dconv("w6_o176", "cpu", plan_driver, qg.EMU_CUS, dims=sg.emu_dims(sg.DCONV_CASES["w6_o176"]["dims"]), exact=False, sparse=True)
+
+
+@pytest.mark.parametrize("name", list(sg.KNOB_CASES))
+def test_split_gemm_instances_only_dev_knobs_reach(emulator, plan_driver, name):
+    """gemm_nn_kernel<2, 32 | 20 | 16> (knob 0), gemm_tn_kernel<2 | 4 | 6> (knob 1) and the 8-wave gemm_tn_dma_kernel<2, *, *, 4>
+    (knob 14): one dconv call each, the instance proven by the recorder.  gemm_nn_kernel<6, 32 | 20 | 16> needs knob 0 AND more than
+    20 352 rows, which the emulator cannot afford; the MI355X suite loads the product library, which has no knobs: no test runs those
+    three (split_gemm_suite.KNOB_ONLY_NOT_RUN; tests/test_split_gemm.py holds that list against the selection rules)."""
+    dims, knobs, expect = sg.KNOB_CASES[name]
+    for key, value in knobs.items():
+        emulator.call("eeg_dcrnn_set_tuning", key, value)
+    try:
+        sg.check_dconv(name, "cpu", plan_driver, qg.EMU_CUS, dims=dims, expect=expect, knobs=knobs)
+    finally:
+        for key in knobs:
+            emulator.call("eeg_dcrnn_set_tuning", key, 0)
+
+
+@pytest.mark.parametrize("name", list(sg.BF3_CASES))
+def test_split_gemm_bf16_split_case_table(emulator, name):
+    """the opt-in bf16 split at every column-block width of gemm_nn_bf3_kernel, and the fp32 kernel on a dX of 19 tiles"""
+    sg.check_bf3_layer(name, "cpu")
 
 
 def test_training_tail_kernels():
