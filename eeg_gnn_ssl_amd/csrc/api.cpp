@@ -18,6 +18,7 @@
 #include "kernels_eval.h"
 #include "kernels_moments.h"
 #include "kernels_scan.h"
+#include "kernels_resample.h"
 #include "kernels_occlude.h"
 #include "kernels_data.h"
 #include "kernels_records.h"
@@ -582,6 +583,45 @@ int copy_floats(float* dst, const float* src, size_t n, hipStream_t st) {
     return platform_copy_floats(dst, src, n, st) ? 0 : fail("device copy failed");
 }
 
+}  // namespace
+
+// ---- Fourier resampling of whole recordings (kernels_resample.h): the lengths and the FFT passes of eeg_dcrnn_resample ----
+namespace {
+constexpr int kRsMaxChunk = 1024;                                        // channels of one pass over the workspace (grid.y)
+// the two chirp-z transforms of a (n_in -> n_out) resample: log2 of their FFT lengths; false: a length outside the limits
+bool rs_lengths(int64_t n_in, int64_t n_out, int& lm1, int& lm2) {
+    if (n_in < 2 || n_in > EEG_RESAMPLE_MAX_SAMPLES || n_out < 1 || n_out > EEG_RESAMPLE_MAX_SAMPLES) return false;
+    lm1 = rs_log2_len(n_in + std::min(n_in, n_out) / 2);                 // n_in inputs, the min(n_in, n_out) / 2 + 1 bins that are kept
+    lm2 = rs_log2_len(n_out / 2 + 1 + n_out - 1);
+    return lm1 <= kRsMaxBits && lm2 <= kRsMaxBits;
+}
+// buf[c][0 .. 2^lm) for `channels` rows: the forward transform alone (filt null), or the circular convolution with the filter whose
+// forward transform is filt (unscaled: 2^lm times the convolution)
+template <int MODE>
+int rs_pass(rs_c64* buf, long long stride, int channels, const rs_c64* filt, int lm, int lbits, int sbits, int gbits, hipStream_t st) {
+    const size_t lds = rs_pass_lds(lbits, gbits);
+    EEG_SET_MAX_LDS(rs_fft_pass_kernel<MODE>, kRsMaxLds);
+    EEG_LAUNCH_P("resample_fft", rs_fft_pass_kernel<MODE>, dim3((unsigned)(1u << (lm - lbits - gbits)), (unsigned)channels), dim3(kRsThreads), lds, st,
+                 buf, stride, filt, lm, lbits, sbits, gbits);
+    return check_launch("resample_fft");
+}
+int rs_transform(rs_c64* buf, long long stride, int channels, const rs_c64* filt, int lm, hipStream_t st) {
+    const RsPlan p = rs_plan(lm);
+    int sb[kRsMaxPasses], gb[kRsMaxPasses], rest = lm;
+    for (int i = 0; i < p.passes; ++i) {
+        rest -= p.bits[i];
+        sb[i] = rest;
+        gb[i] = p.passes == 1 ? 0 : kRsPassTileBits - p.bits[i];
+    }
+    const int last = p.passes - 1;
+    for (int i = 0; i < last; ++i)
+        if (int rc = rs_pass<kRsFwd>(buf, stride, channels, nullptr, lm, p.bits[i], sb[i], gb[i], st)) return rc;
+    if (filt == nullptr) return rs_pass<kRsFwd>(buf, stride, channels, nullptr, lm, p.bits[last], sb[last], gb[last], st);
+    if (int rc = rs_pass<kRsBoth>(buf, stride, channels, filt, lm, p.bits[last], sb[last], gb[last], st)) return rc;
+    for (int i = last - 1; i >= 0; --i)
+        if (int rc = rs_pass<kRsInv>(buf, stride, channels, nullptr, lm, p.bits[i], sb[i], gb[i], st)) return rc;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1457,6 +1497,65 @@ int eeg_dcrnn_event_scores(const int32_t* events, const int32_t* event_count, in
     EEG_LAUNCH_P("event_scores_total", event_scores_total_kernel, dim3(1), dim3(kScanThreads), kScanThreads * sizeof(long long), st, recs, (int)R,
                  reinterpret_cast<long long*>(record));
     return check_launch("event_scores_total");
+}
+
+/* ---- native-rate recordings to the model's rate: Fourier resampling of whole recordings -------------- */
+static_assert(EEG_RESAMPLE_MAX_SAMPLES == (1ll << (kRsMaxBits - 1)), "include/eeg_dcrnn.h and kernels_resample.h disagree");
+size_t eeg_dcrnn_resample_ws_bytes(int64_t n_in, int64_t n_out, int channels) {
+    int lm1, lm2;
+    if (channels < 1 || !rs_lengths(n_in, n_out, lm1, lm2)) return 0;
+    const size_t m1 = (size_t)1 << lm1, m2 = (size_t)1 << lm2;
+    return (m1 + m2 + (size_t)channels * std::max(m1, m2)) * sizeof(rs_c64);
+}
+int eeg_dcrnn_resample(const void* in, int in_f64, int channels, int64_t n_in, int64_t in_stride, int64_t n_out, float* out, int64_t out_stride,
+                       void* ws, size_t ws_bytes, void* stream) {
+    if (in == nullptr || out == nullptr || ws == nullptr) return fail("resample: null in / out / ws");
+    if (in_f64 != 0 && in_f64 != 1) return fail("resample: in_f64=%d (0 = float32, 1 = float64)", in_f64);
+    if (channels < 1) return fail("resample: channels=%d (>= 1)", channels);
+    int lm1, lm2;
+    if (n_in < 2 || n_in > EEG_RESAMPLE_MAX_SAMPLES) return fail("resample: n_in=%lld samples unsupported (2..%lld)", (long long)n_in, (long long)EEG_RESAMPLE_MAX_SAMPLES);
+    if (n_out < 1 || n_out > EEG_RESAMPLE_MAX_SAMPLES) return fail("resample: n_out=%lld samples unsupported (1..%lld)", (long long)n_out, (long long)EEG_RESAMPLE_MAX_SAMPLES);
+    if (!rs_lengths(n_in, n_out, lm1, lm2)) return fail("resample: n_in=%lld, n_out=%lld unsupported", (long long)n_in, (long long)n_out);
+    if (in_stride < n_in) return fail("resample: in_stride=%lld below n_in=%lld", (long long)in_stride, (long long)n_in);
+    if (out_stride < n_out) return fail("resample: out_stride=%lld below n_out=%lld", (long long)out_stride, (long long)n_out);
+    if (((uintptr_t)in & (in_f64 ? 7 : 3)) != 0 || ((uintptr_t)out & 3) != 0) return fail("resample: in / out must be aligned to their element size");
+    if (((uintptr_t)ws & 15) != 0) return fail("resample: ws must be 16-byte aligned");
+    const size_t m1 = (size_t)1 << lm1, m2 = (size_t)1 << lm2, mb = std::max(m1, m2);
+    const size_t one = (m1 + m2 + mb) * sizeof(rs_c64);
+    if (ws_bytes < one) return fail("resample: ws_bytes=%zu below the %zu bytes of one channel (eeg_dcrnn_resample_ws_bytes(n_in, n_out, 1))", ws_bytes, one);
+    const int chunk = (int)std::min<size_t>({(size_t)channels, (size_t)kRsMaxChunk, (ws_bytes / sizeof(rs_c64) - m1 - m2) / mb});
+    hipStream_t st = S_(stream);
+    rs_c64* h1 = reinterpret_cast<rs_c64*>(ws);
+    rs_c64* h2 = h1 + m1;
+    rs_c64* buf = h2 + m2;
+    const long long Nx = n_in, num = n_out, N = std::min(Nx, num), K = num / 2 + 1;
+    auto blocks = [](size_t n) { return (unsigned)((n + kRsThreads - 1) / kRsThreads); };
+    // the spectra of the two chirp filters, shared by the channels
+    EEG_LAUNCH_P("resample_filter", rs_filter_kernel, dim3(blocks(m1)), dim3(kRsThreads), 0, st, h1, (long long)m1, Nx, Nx, N / 2 + 1, +1);
+    if (int rc = check_launch("resample_filter")) return rc;
+    if (int rc = rs_transform(h1, 0, 1, nullptr, lm1, st)) return rc;
+    EEG_LAUNCH_P("resample_filter", rs_filter_kernel, dim3(blocks(m2)), dim3(kRsThreads), 0, st, h2, (long long)m2, num, K, num, -1);
+    if (int rc = check_launch("resample_filter")) return rc;
+    if (int rc = rs_transform(h2, 0, 1, nullptr, lm2, st)) return rc;
+    for (int c0 = 0; c0 < channels; c0 += chunk) {
+        const int nc = std::min(chunk, channels - c0);
+        if (in_f64)
+            EEG_LAUNCH_P("resample_load", rs_load_kernel<double>, dim3(blocks(m1), (unsigned)nc), dim3(kRsThreads), 0, st,
+                         static_cast<const double*>(in) + (size_t)c0 * in_stride, (long long)in_stride, Nx, buf, (long long)mb, (long long)m1);
+        else
+            EEG_LAUNCH_P("resample_load", rs_load_kernel<float>, dim3(blocks(m1), (unsigned)nc), dim3(kRsThreads), 0, st,
+                         static_cast<const float*>(in) + (size_t)c0 * in_stride, (long long)in_stride, Nx, buf, (long long)mb, (long long)m1);
+        if (int rc = check_launch("resample_load")) return rc;
+        if (int rc = rs_transform(buf, (long long)mb, nc, h1, lm1, st)) return rc;
+        EEG_LAUNCH_P("resample_bridge", rs_bridge_kernel, dim3(blocks(m2), (unsigned)nc), dim3(kRsThreads), 0, st, buf, (long long)mb, Nx, num,
+                     1.0 / (double)m1, (long long)m2);
+        if (int rc = check_launch("resample_bridge")) return rc;
+        if (int rc = rs_transform(buf, (long long)mb, nc, h2, lm2, st)) return rc;
+        EEG_LAUNCH_P("resample_store", rs_store_kernel, dim3(blocks((size_t)num), (unsigned)nc), dim3(kRsThreads), 0, st, buf, (long long)mb, num,
+                     1.0 / ((double)m2 * (double)Nx), out + (size_t)c0 * out_stride, (long long)out_stride);
+        if (int rc = check_launch("resample_store")) return rc;
+    }
+    return 0;
 }
 
 /* ---- occlusion maps: the variants of one window, their scores ------------------------------------- */

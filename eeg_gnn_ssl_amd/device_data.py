@@ -25,7 +25,8 @@ signal buffer, a clip is a row (rec, x_start, x_samples, y_start) of an int64 ta
 the step's batch -- raw signals (B, N, Tx*W), the SSL target (B, N, Ty*W), lengths, labels -- in front of the unchanged raw chain.
 The SSL target is then no pool of its own, a classification clip needs no host padding, and overlapping or strided clips cost a
 table row each.  `clip_table_detection` / `clip_table_ssl` / `clip_table_classification` restate the three loaders' arithmetic.
-Both data sets hand their batch over through one method, `gather`.
+Both data sets hand their batch over through one method, `gather`.  Recordings that still have their native sampling rates go
+through `RecordingDataset.from_native_rate`: each is resampled on the device straight into the signal buffer (resample.py).
 
 Class imbalance.  `BalancedEpochSampler` draws a balanced epoch out of the whole resident pool -- every epoch anew, or once per run
 as the reference's detection loader does -- into a permutation shorter than the pool, which the gathers take as it is;
@@ -244,6 +245,19 @@ class RecordingDataset:
                 raise ValueError(f"RecordingDataset: y must be the contiguous labels ({table.shape[0]},) on {dev}, float32 (detection) or int64 "
                                  f"(classification), got {got}")
         self.y = y
+
+    @classmethod
+    def from_native_rate(cls, recordings, sample_freqs, clip_table, y=None, *, window: int, x_steps: int, y_steps: int = 0, to_freq=200, device=None):
+        """the data set over recordings that still have their NATIVE sampling rates (sample_freqs[r] Hz): each is uploaded and resampled
+        to `to_freq` Hz on the device, straight into the padded layout (`resample.resample_recordings`; the reference's offline
+        resample_signals.py); the clip table counts samples at `to_freq`.  Sugar over the (signals, rec_table=, num_channels=) form."""
+        from .resample import resample_recordings
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        recordings = list(recordings)
+        signals, rec_table = resample_recordings(recordings, sample_freqs, to_freq=to_freq, device=device)      # (refuses an empty list)
+        n = int((recordings[0] if torch.is_tensor(recordings[0]) else np.asarray(recordings[0])).shape[0])
+        return cls(signals, clip_table, y, window=window, x_steps=x_steps, y_steps=y_steps, rec_table=rec_table, num_channels=n)
 
     def __len__(self):
         return self.clip_table.shape[0]

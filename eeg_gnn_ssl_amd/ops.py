@@ -13,7 +13,7 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    feature_moments, moments_record, scan_timeline, scan_events, event_scores, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
+    feature_moments, moments_record, scan_timeline, scan_events, event_scores, resample, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -1887,6 +1887,66 @@ _define("scan_events", "(Tensor timeline, Tensor cover, Tensor bin_off, int smoo
         "Tensor(a!) smoothed, Tensor(b!) events, Tensor(c!) event_count) -> ()", _scan_events_impl, lambda *a: None)
 _define("event_scores", "(Tensor events, Tensor event_count, Tensor ref, Tensor ref_count, Tensor cover, Tensor bin_off, Tensor(a!) record, "
         "Tensor(b!) rec_records) -> ()", _event_scores_impl, lambda *a: None)
+
+
+# ---- native-rate recordings to the model's rate (resample.py; the reference's data/resample_signals.py:38-43) -------------------------
+RESAMPLE_MAX_SAMPLES = 1 << 22       # EEG_RESAMPLE_MAX_SAMPLES
+
+
+def _resample_lengths(what, n_in: int, n_out: int):
+    if not 2 <= n_in <= RESAMPLE_MAX_SAMPLES:
+        raise ValueError(f"{what}: {n_in} input samples per channel; 2..{RESAMPLE_MAX_SAMPLES} (EEG_RESAMPLE_MAX_SAMPLES) are supported")
+    if not 1 <= n_out <= RESAMPLE_MAX_SAMPLES:
+        raise ValueError(f"{what}: n_out={n_out} output samples per channel; 1..{RESAMPLE_MAX_SAMPLES} (EEG_RESAMPLE_MAX_SAMPLES) are supported")
+
+
+def resample_into(x, out, workspace_bytes=None, what: str = "resample"):
+    """rows of x (N, L) float32 / float64 (row stride >= L) -> the rows of out (N, n_out) float32 (row stride >= n_out), both on the
+    device; the workspace comes from the caching allocator, all channels at once unless `workspace_bytes` caps it (never below one
+    channel's need: the channels then run in chunks, same bits).  Everything is checked before the launch."""
+    lib = _lib.get_lib()
+    for name, t, dtypes in (("x", x, (torch.float32, torch.float64)), ("out", out, (torch.float32,))):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype not in dtypes:
+            got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be a 2-D (channels, samples) tensor of {' or '.join(str(d) for d in dtypes)}, got {got}")
+        if t.shape[0] < 1 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{what}: the rows of {name} must be contiguous with a row stride of at least the row length, got shape "
+                             f"{tuple(t.shape)} with strides {tuple(t.stride())}")
+    if lib.is_device_build and not x.is_cuda:
+        raise ValueError(f"{what}: x is on {x.device}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    if out.device != x.device or out.shape[0] != x.shape[0]:
+        raise ValueError(f"{what}: out is {tuple(out.shape)} on {out.device} for x {tuple(x.shape)} on {x.device}")
+    if x.requires_grad:
+        raise ValueError(f"{what}: x requires grad; resampling has no gradient formula (detach it)")
+    n, n_in, n_out = int(x.shape[0]), int(x.shape[1]), int(out.shape[1])
+    _resample_lengths(what, n_in, n_out)
+    one = int(lib.query("eeg_dcrnn_resample_ws_bytes", n_in, n_out, 1))
+    ws_bytes = int(lib.query("eeg_dcrnn_resample_ws_bytes", n_in, n_out, n))
+    if one == 0 or ws_bytes == 0:
+        raise ValueError(f"{what}: the library refuses {n} channels of {n_in} -> {n_out} samples")
+    if workspace_bytes is not None:
+        if int(workspace_bytes) < one:
+            raise ValueError(f"{what}: workspace_bytes={workspace_bytes} is below the {one} bytes one channel of {n_in} -> {n_out} samples needs")
+        ws_bytes = min(ws_bytes, int(workspace_bytes))
+    ws = _new((ws_bytes + 15) // 16 * 2, x, torch.float64)
+    lib.call("eeg_dcrnn_resample", _p(x), 1 if x.dtype == torch.float64 else 0, n, n_in, int(x.stride(0)) if n > 1 else n_in, n_out, _p(out),
+             int(out.stride(0)) if n > 1 else n_out, _p(ws), ws_bytes, _stream(x))
+    return out
+
+
+def _resample_impl(x, n_out: int, workspace_bytes: Optional[int] = None):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"resample: x must be a 2-D (channels, samples) tensor, got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    if x.shape[0] >= 1:
+        _resample_lengths("resample", int(x.shape[1]), int(n_out))
+    return resample_into(x, _new((x.shape[0], int(n_out)), x), workspace_bytes)
+
+
+def _resample_fake(x, n_out, workspace_bytes=None):
+    return x.new_empty((x.shape[0], n_out), dtype=torch.float32)
+
+
+_define("resample", "(Tensor x, int n_out, int? workspace_bytes=None) -> Tensor", _resample_impl, _resample_fake)
 
 
 # ---- occlusion maps on the device (interpret.py: occlusion_maps) -------------------------------------------------------------------

@@ -536,6 +536,26 @@ int eeg_dcrnn_event_scores(const int32_t* events, const int32_t* event_count, in
                            const int32_t* cover, const int64_t* bin_off, int64_t R, int64_t total_bins, int64_t* record, int64_t* rec_records,
                            void* stream);
 
+/* Native-rate recordings to the model's rate on the device: the Fourier resampling of whole recordings (the reference's offline step,
+ * data/resample_signals.py:38-43 -> data/data_utils.py:158-170 `resampleData` = scipy.signal.resample over the whole recording, on the
+ * float64 signals of `getEDFsignals`).  Per channel row x of n_in samples, in float64:
+ *   X = rfft(x);  N = min(n_out, n_in);  Y[0 .. N/2] = X[0 .. N/2], zero above;  N even: Y[N/2] *= 2 (n_out < n_in) or 0.5 (n_in < n_out);
+ *   y = irfft(Y, n_out) * n_out / n_in, rounded once to float32 on the store.
+ * Any lengths (prime ones included): both transforms are chirp-z transforms on power-of-two float64 complex FFTs of M1 >= n_in + N/2
+ * and M2 >= n_out/2 + n_out points (csrc/kernels_resample.h).  No atomics, a fixed order of operations: a channel's output bits depend
+ * on that channel's samples and (n_in, n_out) alone -- not on the channel count, the chunking or what the workspace held.
+ *
+ * eeg_dcrnn_resample: in (channels rows of n_in samples, row c at in + c * in_stride elements; float32, or float64 with in_f64 = 1)
+ * -> out + c * out_stride .. + n_out float32; nothing else of out is written (padding behind a row keeps its bits).  2 <= n_in <=
+ * EEG_RESAMPLE_MAX_SAMPLES, 1 <= n_out <= EEG_RESAMPLE_MAX_SAMPLES, strides >= the lengths.  ws: 16-byte aligned device memory of
+ * ws_bytes; eeg_dcrnn_resample_ws_bytes(n_in, n_out, channels) runs all channels at once, anything down to
+ * eeg_dcrnn_resample_ws_bytes(n_in, n_out, 1) runs them in chunks with the same bits (what bounds the memory of an hour-long
+ * recording); less is refused.  eeg_dcrnn_resample_ws_bytes returns 0 for a shape the call would refuse. */
+#define EEG_RESAMPLE_MAX_SAMPLES (1ll << 22)
+size_t eeg_dcrnn_resample_ws_bytes(int64_t n_in, int64_t n_out, int channels);
+int eeg_dcrnn_resample(const void* in, int in_f64, int channels, int64_t n_in, int64_t in_stride, int64_t n_out, float* out, int64_t out_stride,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* Occlusion maps on the device: group g of channels of clip b is overwritten with `fill` over the window of steps [t0, t0 + w) and the
  * map records how far the predicted probability drops.  All variants of a window start from the unoccluded clip's state at t0.
  *
