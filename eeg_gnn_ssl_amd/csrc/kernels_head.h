@@ -197,13 +197,13 @@ __device__ __forceinline__ void cls_head_loss_body(const float* __restrict__ z, 
                 for (int c = 1; c < C; ++c) mx = fmaxf(mx, dl[c]);
                 float se = 0.f;
                 for (int c = 0; c < C; ++c) se += expf(dl[c] - mx);
-                const float lse = mx + logf(se);
+                const float lg = logf(se);                       // (mx and lg stay apart: ce_row_lse of kernels_tail.h says why)
                 const long long tl = reinterpret_cast<const long long*>(targets)[b];
                 const bool t_ok = tl >= 0 && tl < (long long)C;
                 const int t = t_ok ? (int)tl : -1;
-                term = lse - (t_ok ? dl[t] : __builtin_nanf(""));
+                term = (mx - (t_ok ? dl[t] : __builtin_nanf(""))) + lg;
                 for (int c = 0; c < C; ++c) {
-                    const float g = expf(dl[c] - lse) - (c == t ? 1.f : 0.f);
+                    const float g = expf((dl[c] - mx) - lg) - (c == t ? 1.f : 0.f);
                     dl[c] = (kMode == kClipMultiply ? u * g : g) / div;
                 }
                 if (kMode == kClipMultiply) term = u * term;

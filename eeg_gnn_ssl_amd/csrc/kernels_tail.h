@@ -10,18 +10,24 @@ namespace eeg {
 // The per-clip terms of the two criteria, shared by the training kernels below and by the evaluation pass (kernels_eval.h:
 // eval_scores_kernel), so that a clip's evaluation loss is the training criterion of that clip as a batch of one, bit for bit.
 __device__ __forceinline__ float bce_logits_term(float v, float t) { return fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v))); }
-// log-sum-exp of one row of C logits
-__device__ __forceinline__ float ce_row_lse(const float* __restrict__ r, int C) {
+// log-sum-exp of one row of C logits, kept in its two parts: the row's maximum and lg = log sum_c exp(r[c] - mx), 0 <= lg <= log C.
+// Nothing adds them: mx + lg rounds to an ulp of |mx| -- 1e-3 at logits of 1e4, 4e-6 at 50 -- and that error would go into every
+// softmax entry and into the clip's loss.  The differences r[c] - mx are formed first (exact or of the size of the result) and the small
+// part comes off them, as in a log-softmax.
+struct RowLse { float mx, lg; };
+__device__ __forceinline__ RowLse ce_row_lse(const float* __restrict__ r, int C) {
     float mx = r[0];
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, r[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(r[c] - mx);
-    return mx + logf(se);
+    return RowLse{mx, logf(se)};
 }
+// softmax entry of logit v of that row
+__device__ __forceinline__ float ce_softmax(float v, const RowLse& l) { return expf((v - l.mx) - l.lg); }
 // a label outside 0..C-1 (torch: a device-side assert that ends the process) makes the LOSS NaN instead of reading logits out of bounds
-__device__ __forceinline__ float ce_logits_term(const float* __restrict__ r, int C, long long tl, float lse) {
+__device__ __forceinline__ float ce_logits_term(const float* __restrict__ r, int C, long long tl, const RowLse& l) {
     const bool t_ok = tl >= 0 && tl < (long long)C;
-    return lse - (t_ok ? r[(int)tl] : __builtin_nanf(""));
+    return (l.mx - (t_ok ? r[(int)tl] : __builtin_nanf(""))) + l.lg;
 }
 
 // nn.BCEWithLogitsLoss() (mean) on logits (B,), targets y (B,): loss[0], dlogits = (sigmoid(x)-y)/B.
@@ -51,12 +57,12 @@ __global__ void ce_logits_kernel(const float* __restrict__ x, const long long* _
     float acc = 0.f;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
         const float* r = x + (size_t)i * C;
-        const float lse = ce_row_lse(r, C);
+        const RowLse lse = ce_row_lse(r, C);
         // a label outside 0..C-1: the loss is NaN (ce_logits_term); the gradient of that clip is the softmax alone
         const long long tl = y[i];
         const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
         acc += ce_logits_term(r, C, tl, lse);
-        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (expf(r[c] - lse) - (c == t ? 1.f : 0.f)) / (float)B;
+        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (ce_softmax(r[c], lse) - (c == t ? 1.f : 0.f)) / (float)B;
     }
     sm[threadIdx.x] = acc;
     __syncthreads();
@@ -101,11 +107,11 @@ __global__ void ce_logits_w_kernel(const float* __restrict__ x, const long long*
             continue;
         }
         const float* r = x + (size_t)i * C;
-        const float lse = ce_row_lse(r, C);
+        const RowLse lse = ce_row_lse(r, C);
         const long long tl = y[i];                                  // (a label outside 0..C-1 on a clip that counts: NaN, as ce_logits_kernel)
         const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
         acc += ce_logits_term(r, C, tl, lse);
-        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (expf(r[c] - lse) - (c == t ? 1.f : 0.f)) / div;
+        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (ce_softmax(r[c], lse) - (c == t ? 1.f : 0.f)) / div;
     }
     sm[threadIdx.x] = acc;
     __syncthreads();
@@ -154,11 +160,11 @@ __global__ void ce_logits_cw_kernel(const float* __restrict__ x, const long long
             continue;
         }
         const float* r = x + (size_t)i * C;
-        const float lse = ce_row_lse(r, C);
+        const RowLse lse = ce_row_lse(r, C);
         const long long tl = y[i];
         const int t = (tl >= 0 && tl < (long long)C) ? (int)tl : -1;
         acc += u * ce_logits_term(r, C, tl, lse);
-        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (u * (expf(r[c] - lse) - (c == t ? 1.f : 0.f))) / div;
+        for (int c = 0; c < C; ++c) dx[(size_t)i * C + c] = (u * (ce_softmax(r[c], lse) - (c == t ? 1.f : 0.f))) / div;
     }
     sm[threadIdx.x] = acc;
     __syncthreads();
