@@ -305,8 +305,9 @@ def cached_reference(name, t, b, seed, rps_sparse, case=None):
 
 
 # ---- the layer under test -------------------------------------------------------------------------------------------------------
-def run_layer(case, op, w, wsel, device):
-    """ops.dcgru_layer forward + backward on `device` -> (hseq, gradients, the function that repeats it)"""
+def run_layer(case, op, w, wsel, device, need_dx=True):
+    """ops.dcgru_layer forward + backward on `device` -> (hseq, gradients, the function that repeats it).  need_dx=False: x carries no
+    requires_grad and no dX comes back -- a first layer (the spectral form takes input widths other than 64 only without dX)"""
     import ctypes
     from eeg_gnn_ssl_amd import _lib, ops
     n, h, m = case["n"], case["h"], hops(case)
@@ -328,7 +329,7 @@ def run_layer(case, op, w, wsel, device):
     wd, wseld = w.to(device), wsel.to(device)
 
     def run():
-        x = xb.detach().requires_grad_(True)
+        x = xb.detach().requires_grad_(need_dx)
         q = {k: v.detach().requires_grad_(True) for k, v in par.items()}
         h0d = h0.detach().requires_grad_(True) if h0 is not None else None
         if basis is None:
@@ -339,7 +340,9 @@ def run_layer(case, op, w, wsel, device):
             hseq, hsel = out.hseq, out.hsel
         _loss(hseq, hsel if lengths is not None else None, wd, wseld).backward()
         run.hsel = hsel.detach() if lengths is not None else None                         # (the state at each clip's last step, as returned)
-        grads = dict(dX=x.grad.transpose(0, 1) if case["bm"] else x.grad, dWg=q["wg"].grad, dbg=q["bg"].grad, dWc=q["wc"].grad, dbc=q["bc"].grad)
+        grads = dict(dWg=q["wg"].grad, dbg=q["bg"].grad, dWc=q["wc"].grad, dbc=q["bc"].grad)
+        if need_dx:
+            grads["dX"] = x.grad.transpose(0, 1) if case["bm"] else x.grad
         if h0d is not None:
             grads["dh0"] = h0d.grad
         return hseq.detach(), grads
@@ -367,12 +370,13 @@ def assert_roles(ran, expect, what, exact=True):
 
 
 def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0, report=None, exact=True, dims=None, case=None,
-               grad_tol=GRAD_TOL):
+               grad_tol=GRAD_TOL, need_dx=True):
     """One case: the layer on `device` against the float64 reference (hseq under assert_close, every gradient under
     assert_close_scaled(tol=5e-5)), after the proof that the expected kernels took its GEMMs.  sparse: the cotangent lives on three clips
     (first, last, and the one across the first row-split boundary of the case's quad TN kernel, read from the plan driver `exe`), so
     that a row dropped, doubled or misplaced at a split or tile edge is measured against a few hundred rows' worth of gradient.
-    case: a case of another table in this format (tests/split_gemm_suite.py), at the `dims` it names; grad_tol: its gradient bound."""
+    case: a case of another table in this format (tests/split_gemm_suite.py), at the `dims` it names; grad_tol: its gradient bound;
+    need_dx=False: the layer is not asked for dX (run_layer)."""
     case = case if case is not None else CASES[name]
     t, b, r = dims if dims is not None else case_dims(case, rows_min)
     rps = None
@@ -383,7 +387,7 @@ def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0,
     assert rps is not None or not sparse
     op, cots, ref_hseq, ref_grads = cached_reference(name, t, b, seed, rps, case)
     which = 1 if sparse else 0
-    run = run_layer(case, op, *cots[which], device)
+    run = run_layer(case, op, *cots[which], device, need_dx=need_dx)
     run()                                                                                 # (first call: allocations)
     out = {}
     ran = ps.kernels_run(lambda: out.update(res=run()))
@@ -401,7 +405,7 @@ def check_case(name, device, rows_min, cus=None, exe=None, sparse=False, seed=0,
     ps.assert_close(hseq.cpu().numpy(), ref_hseq.numpy(), f"{what}: hseq")
     for k, g in grads.items():
         ps.assert_close_scaled(g.detach().cpu().numpy(), ref_grads[which][k].numpy(), f"{what}: {k}", tol=grad_tol)
-    if sparse:                                    # clips without a cotangent: not one bit of gradient reaches their inputs
+    if sparse and need_dx:                        # clips without a cotangent: not one bit of gradient reaches their inputs
         keep = sparse_clips(b, case["n"], rps)
         rest = [i for i in range(b) if i not in keep]
         assert not grads["dX"][:, rest].any(), f"{what}: dX of a clip without a cotangent is not zero"

@@ -9,6 +9,7 @@ import parity_suite as ps
 import quad_gemm_suite as qg
 import seq_kernel_suite as sk
 import spec_plan_suite as sp
+import spec_walk_suite as sw
 import split_gemm_suite as sg
 
 
@@ -84,6 +85,19 @@ def test_spectral_case_runs_the_planned_kernels(emulator, plan_driver, adj3d, na
     """tests/spec_plan_suite.py: every kernel instance the plans of csrc/spec_launch.h can return, each proven through the event recorder
     to take the launches it is planned for (here also under the dev knobs; tests/test_spec_plans.py is the MI355X twin)"""
     sp.check_case(name, "cpu", adj3d, plan_driver, sp.EMU_CUS, set_knob=lambda key, value: emulator.call("eeg_dcrnn_set_tuning", key, value))
+
+
+@pytest.mark.parametrize("name", list(sw.TWINS))
+def test_spectral_walk_twin(emulator, plan_driver, name):
+    """The twins of tests/spec_walk_suite.py: at the emulator's 4 CUs (grid 8) about 110 rows per frequency of 19 nodes already give a
+    gemm_nnf_kernel workgroup four or five chunks, a reused stage and a frequency boundary inside its range; the grouped NN kernels get
+    a whole tile, a cut one and a short last one in one range; the fused TN a 16-row last split; the planar grouped TN (dev knob 23)
+    two splits.  Same checker as on the MI355X (tests/test_spec_walk.py), the states asserted for 4 CUs, same float64 reference and
+    tolerances.  What these catch: a wrong stage, range, boundary or row index.  What they cannot: anything about waits and arrival
+    order -- the emulator executes a DMA the moment it is requested, so a wait that is too weak or a stage overwritten too early passes
+    here.  That is left to the MI355X cases."""
+    sw.check_case(name, "cpu", plan_driver, sp.EMU_CUS, cases=sw.TWINS,
+                  set_knob=lambda key, value: emulator.call("eeg_dcrnn_set_tuning", key, value))
 
 
 def test_spectral_basis_and_shared_support_detection(adj3d):
