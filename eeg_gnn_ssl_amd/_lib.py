@@ -138,6 +138,9 @@ _SIGNATURES = {
     # native-rate recordings to the model's rate: Fourier resampling of whole recordings into rows the caller places
     "eeg_dcrnn_resample_ws_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "eeg_dcrnn_resample": (c_int, [_FP, c_int, c_int, c_int64, c_int64, c_int64, _FP, c_int64, _FP, c_size_t, c_void_p]),
+    # EDF payload bytes -> physical signals of the selected channels; chan_off / gain / offset are HOST arrays
+    "eeg_dcrnn_edf_decode": (c_int, [_FP, c_size_t, c_int64, c_int64, c_int64, c_int, POINTER(c_int64), POINTER(ctypes.c_double), POINTER(ctypes.c_double),
+                                     c_int, _FP, c_int64, c_void_p]),
     # occlusion maps: the B*G variants of one window (inputs, initial states, lengths), then their scores; `hext` is a host pointer table
     "eeg_dcrnn_occlude_expand": (c_int, [_FP, POINTER(c_void_p), c_int, _FP, _FP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                          _FP, _FP, _FP, c_void_p]),

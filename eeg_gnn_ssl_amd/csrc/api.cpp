@@ -19,6 +19,7 @@
 #include "kernels_moments.h"
 #include "kernels_scan.h"
 #include "kernels_resample.h"
+#include "kernels_edf.h"
 #include "kernels_occlude.h"
 #include "kernels_data.h"
 #include "kernels_records.h"
@@ -1556,6 +1557,45 @@ int eeg_dcrnn_resample(const void* in, int in_f64, int channels, int64_t n_in, i
         if (int rc = check_launch("resample_store")) return rc;
     }
     return 0;
+}
+
+/* ---- EDF payload -> physical signals: the int16 samples of the selected signals, scaled in float64 (kernels_edf.h) ---------- */
+static_assert(EEG_EDF_MAX_CHANNELS == kEdfMaxChannels && EEG_EDF_MAX_CHANNELS == kMaxNodes, "include/eeg_dcrnn.h and kernels_edf.h disagree");
+int eeg_dcrnn_edf_decode(const void* payload, size_t payload_bytes, int64_t num_records, int64_t R, int64_t n, int channels, const int64_t* chan_off,
+                         const double* gain, const double* offset, int out_f64, void* out, int64_t out_stride, void* stream) {
+    if (payload == nullptr || chan_off == nullptr || gain == nullptr || offset == nullptr || out == nullptr)
+        return fail("edf_decode: null payload / chan_off / gain / offset / out");
+    if (((uintptr_t)payload & 1) != 0) return fail("edf_decode: payload must be 2-byte aligned (an odd address)");
+    if (out_f64 != 0 && out_f64 != 1) return fail("edf_decode: out_f64=%d (0 = float32, 1 = float64)", out_f64);
+    if (channels < 1 || channels > EEG_EDF_MAX_CHANNELS) return fail("edf_decode: channels=%d unsupported (1..%d)", channels, EEG_EDF_MAX_CHANNELS);
+    if (num_records < 1) return fail("edf_decode: num_records=%lld (>= 1)", (long long)num_records);
+    if (n < 1 || n > kEdfMaxN) return fail("edf_decode: n=%lld samples per record unsupported (1..%lld)", (long long)n, kEdfMaxN);
+    if (R < n) return fail("edf_decode: R=%lld int16 per record below n=%lld", (long long)R, (long long)n);
+    if (num_records > (int64_t)((1ull << 62) / (uint64_t)R) || (uint64_t)num_records * (uint64_t)R > (uint64_t)(payload_bytes / 2))
+        return fail("edf_decode: payload_bytes=%zu below the 2 * num_records * R = 2 * %lld * %lld bytes of whole records", payload_bytes,
+                    (long long)num_records, (long long)R);
+    EdfChannels ch = {};
+    for (int c = 0; c < channels; ++c) {
+        if (chan_off[c] < 0 || chan_off[c] > R - n)
+            return fail("edf_decode: chan_off[%d]=%lld + n=%lld outside a record of R=%lld", c, (long long)chan_off[c], (long long)n, (long long)R);
+        ch.off[c] = chan_off[c];
+        ch.gain[c] = gain[c];
+        ch.offset[c] = offset[c];
+    }
+    const long long L = (long long)num_records * n;                      // <= num_records * R < 2^62
+    if (out_stride < L) return fail("edf_decode: out_stride=%lld below the row length num_records * n = %lld", (long long)out_stride, L);
+    if (((uintptr_t)out & (out_f64 ? 7 : 3)) != 0) return fail("edf_decode: out must be aligned to its element size");
+    const long long tiles = (L + kEdfTile - 1) / kEdfTile;
+    if (tiles > 0x7fffffffll) return fail("edf_decode: num_records * n = %lld samples per channel exceed the grid", L);
+    hipStream_t st = S_(stream);
+    const dim3 grid((unsigned)tiles, (unsigned)channels);
+    if (out_f64)
+        EEG_LAUNCH_P("edf_decode", edf_decode_kernel<double>, grid, dim3(kEdfThreads), 0, st, static_cast<const int16_t*>(payload), (long long)num_records,
+                     (long long)R, (long long)n, ch, static_cast<double*>(out), (long long)out_stride);
+    else
+        EEG_LAUNCH_P("edf_decode", edf_decode_kernel<float>, grid, dim3(kEdfThreads), 0, st, static_cast<const int16_t*>(payload), (long long)num_records,
+                     (long long)R, (long long)n, ch, static_cast<float*>(out), (long long)out_stride);
+    return check_launch("edf_decode");
 }
 
 /* ---- occlusion maps: the variants of one window, their scores ------------------------------------- */

@@ -26,7 +26,8 @@ the step's batch -- raw signals (B, N, Tx*W), the SSL target (B, N, Ty*W), lengt
 The SSL target is then no pool of its own, a classification clip needs no host padding, and overlapping or strided clips cost a
 table row each.  `clip_table_detection` / `clip_table_ssl` / `clip_table_classification` restate the three loaders' arithmetic.
 Both data sets hand their batch over through one method, `gather`.  Recordings that still have their native sampling rates go
-through `RecordingDataset.from_native_rate`: each is resampled on the device straight into the signal buffer (resample.py).
+through `RecordingDataset.from_native_rate`: each is resampled on the device straight into the signal buffer (resample.py); EDF files
+go through `RecordingDataset.from_edf`, which decodes their payload bytes on the device in front of that (edf.py).
 
 Class imbalance.  `BalancedEpochSampler` draws a balanced epoch out of the whole resident pool -- every epoch anew, or once per run
 as the reference's detection loader does -- into a permutation shorter than the pool, which the gathers take as it is;
@@ -257,6 +258,20 @@ class RecordingDataset:
         recordings = list(recordings)
         signals, rec_table = resample_recordings(recordings, sample_freqs, to_freq=to_freq, device=device)      # (refuses an empty list)
         n = int((recordings[0] if torch.is_tensor(recordings[0]) else np.asarray(recordings[0])).shape[0])
+        return cls(signals, clip_table, y, window=window, x_steps=x_steps, y_steps=y_steps, rec_table=rec_table, num_channels=n)
+
+    @classmethod
+    def from_edf(cls, paths, clip_table, y=None, *, window: int, x_steps: int, y_steps: int = 0, channels=None, to_freq=200, device=None):
+        """the data set over EDF FILES (paths, bytes or uint8 arrays): each file's payload bytes are uploaded, the selected channels
+        (default utils.INCLUDED_CHANNELS, the reference's order) decoded and resampled to `to_freq` Hz on the device, straight into
+        the padded layout (`edf.load_edf_recordings`); the clip table counts samples at `to_freq`.  Sugar over the (signals,
+        rec_table=, num_channels=) form."""
+        from . import utils
+        from .edf import load_edf_recordings
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        signals, rec_table, info = load_edf_recordings(paths, channels=channels, to_freq=to_freq, device=device)     # (refuses an empty list)
+        n = len(utils.INCLUDED_CHANNELS) if channels is None else len(list(channels))
         return cls(signals, clip_table, y, window=window, x_steps=x_steps, y_steps=y_steps, rec_table=rec_table, num_channels=n)
 
     def __len__(self):

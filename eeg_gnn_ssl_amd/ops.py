@@ -13,12 +13,13 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    feature_moments, moments_record, scan_timeline, scan_events, event_scores, resample, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
+    feature_moments, moments_record, scan_timeline, scan_events, event_scores, resample, edf_decode, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -1947,6 +1948,89 @@ def _resample_fake(x, n_out, workspace_bytes=None):
 
 
 _define("resample", "(Tensor x, int n_out, int? workspace_bytes=None) -> Tensor", _resample_impl, _resample_fake)
+
+
+# ---- EDF recordings decoded on the device (edf.py; the reference's data/data_utils.py getEDFsignals) ---------------------------------
+EDF_MAX_CHANNELS = 32       # EEG_EDF_MAX_CHANNELS
+EDF_MAX_N = 1 << 30         # samples per data record of a selected signal
+_EDF_DTYPES = (torch.float64, torch.float32)
+
+
+def _edf_int(what, name, v, low):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < low:
+        raise ValueError(f"{what}: {name}={v!r} must be an integer >= {low}")
+    return int(v)
+
+
+def _edf_args(what, payload, num_records, R, n, chan_off, gain, offset):
+    """the checks shared by the operator, its fake implementation and `edf_decode_into`: -> (num_records, R, n, chan_off, gain, offset)"""
+    if not torch.is_tensor(payload) or payload.dtype != torch.uint8 or payload.dim() != 1 or payload.stride(0) != 1:
+        got = f"{payload.dtype} {tuple(payload.shape)}" if torch.is_tensor(payload) else type(payload).__name__
+        raise ValueError(f"{what}: payload must be a 1-D contiguous torch.uint8 tensor (the bytes behind the EDF header), got {got}")
+    num_records, R, n = _edf_int(what, "num_records", num_records, 1), _edf_int(what, "R", R, 1), _edf_int(what, "n", n, 1)
+    if n > EDF_MAX_N:
+        raise ValueError(f"{what}: n={n} samples per record; 1..{EDF_MAX_N} are supported")
+    chan_off, gain, offset = list(chan_off), list(gain), list(offset)
+    if not 1 <= len(chan_off) <= EDF_MAX_CHANNELS:
+        raise ValueError(f"{what}: {len(chan_off)} channels; 1..{EDF_MAX_CHANNELS} (EEG_EDF_MAX_CHANNELS) are supported")
+    if len(gain) != len(chan_off) or len(offset) != len(chan_off):
+        raise ValueError(f"{what}: {len(gain)} gains and {len(offset)} offsets for {len(chan_off)} channels")
+    for c, o in enumerate(chan_off):
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or o < 0 or o + n > R:
+            raise ValueError(f"{what}: chan_off[{c}]={o!r} + n={n} lies outside a record of R={R} int16")
+    for name, vals in (("gain", gain), ("offset", offset)):
+        for c, v in enumerate(vals):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+                raise ValueError(f"{what}: {name}[{c}]={v!r} must be a finite number")
+    if payload.numel() < 2 * num_records * R:
+        raise ValueError(f"{what}: payload of {payload.numel()} bytes is shorter than num_records={num_records} whole records of R={R} int16 "
+                         f"({2 * num_records * R} bytes)")
+    return num_records, R, n, [int(o) for o in chan_off], [float(g) for g in gain], [float(o) for o in offset]
+
+
+def edf_decode_into(payload, num_records, R, n, chan_off, gain, offset, out, what: str = "edf_decode"):
+    """the selected channels of an EDF payload ON THE DEVICE -> the rows of out (C, num_records * n) float64 / float32 (row stride >= the
+    row length, so `out` may be a strided view of a larger buffer): out[c, r * n + j] = gain[c] * (offset[c] + int16 at payload index
+    r * R + chan_off[c] + j), float64 arithmetic, rounded once for a float32 `out`.  Everything is checked before the launch."""
+    lib = _lib.get_lib()
+    num_records, R, n, chan_off, gain, offset = _edf_args(what, payload, num_records, R, n, chan_off, gain, offset)
+    if lib.is_device_build and not payload.is_cuda:
+        raise ValueError(f"{what}: payload is on {payload.device}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    if payload.data_ptr() % 2 != 0:
+        raise ValueError(f"{what}: payload starts at an odd address; the int16 samples must be 2-byte aligned")
+    C, L = len(chan_off), num_records * n
+    if not torch.is_tensor(out) or out.dim() != 2 or out.dtype not in _EDF_DTYPES:
+        got = f"{out.dtype} {tuple(out.shape)}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"{what}: out must be a 2-D (channels, samples) tensor of torch.float64 or torch.float32, got {got}")
+    if tuple(out.shape) != (C, L) or out.device != payload.device:
+        raise ValueError(f"{what}: out is {tuple(out.shape)} on {out.device}; {C} channels of num_records * n = {L} samples on {payload.device} are decoded")
+    if out.stride(1) != 1 or (C > 1 and out.stride(0) < L):
+        raise ValueError(f"{what}: the rows of out must be contiguous with a row stride of at least the row length, got shape "
+                         f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+    lib.call("eeg_dcrnn_edf_decode", _p(payload), payload.numel(), num_records, R, n, C, (ctypes.c_int64 * C)(*chan_off), (ctypes.c_double * C)(*gain),
+             (ctypes.c_double * C)(*offset), 1 if out.dtype == torch.float64 else 0, _p(out), int(out.stride(0)) if C > 1 else L, _stream(payload))
+    return out
+
+
+def _edf_out_dtype(what, out_dtype):
+    dtype = torch.float64 if out_dtype is None else out_dtype
+    if dtype not in _EDF_DTYPES:
+        raise ValueError(f"{what}: out_dtype={out_dtype!r}; torch.float64 or torch.float32")
+    return dtype
+
+
+def _edf_decode_impl(payload, num_records, R, n, chan_off, gain, offset, out_dtype=None):
+    dtype = _edf_out_dtype("edf_decode", out_dtype)
+    num_records, R, n, chan_off, gain, offset = _edf_args("edf_decode", payload, num_records, R, n, chan_off, gain, offset)
+    return edf_decode_into(payload, num_records, R, n, chan_off, gain, offset, _new((len(chan_off), num_records * n), payload, dtype))
+
+
+def _edf_decode_fake(payload, num_records, R, n, chan_off, gain, offset, out_dtype=None):
+    return payload.new_empty((len(chan_off), num_records * n), dtype=_edf_out_dtype("edf_decode", out_dtype))
+
+
+_define("edf_decode", "(Tensor payload, int num_records, int R, int n, int[] chan_off, float[] gain, float[] offset, ScalarType? out_dtype=None) -> Tensor",
+        _edf_decode_impl, _edf_decode_fake)
 
 
 # ---- occlusion maps on the device (interpret.py: occlusion_maps) -------------------------------------------------------------------

@@ -6,8 +6,8 @@ The number of output samples follows the reference's rule, `num = to_freq * int(
 float, and a recording whose length is not a whole number of seconds is squeezed as a whole (`resampled_length`).  A recording whose
 `sample_freq == to_freq` is not resampled at all: it is copied as given (resample_signals.py:38).
 
-Decoding the EDF file, ordering its channels and reading the annotation files stay on the host; what is uploaded is the native-rate
-(channels, L) array."""
+What is uploaded here is the decoded native-rate (channels, L) array; EDF files themselves go through edf.py, which uploads their
+payload bytes and decodes them on the device in front of this pass (`load_edf_recordings`, `RecordingDataset.from_edf`)."""
 from __future__ import annotations
 
 import math

@@ -556,6 +556,23 @@ size_t eeg_dcrnn_resample_ws_bytes(int64_t n_in, int64_t n_out, int channels);
 int eeg_dcrnn_resample(const void* in, int in_f64, int channels, int64_t n_in, int64_t in_stride, int64_t n_out, float* out, int64_t out_stride,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* EDF recordings decoded on the device: the int16 payload of an EDF file -> the physical signals of the selected channels (the
+ * reference's `getEDFsignals`, data/data_utils.py, through EDFlib's readSignal).  The payload (everything behind the header) lies in
+ * device memory as it is in the file: num_records records of R little-endian int16 each; selected channel c has n samples per record,
+ * the first at int16 index chan_off[c] of the record.  Per sample, in float64,
+ *   out[c * out_stride + r * n + j] = gain[c] * (offset[c] + (double)payload_i16[r * R + chan_off[c] + j])
+ * with gain = (pmax - pmin) / (dmax - dmin), offset = pmax / gain - dmax computed by the caller (EDFlib's arithmetic): one correctly
+ * rounded add, then one correctly rounded multiply; out_f64 = 0 rounds that value once to float32.  chan_off / gain / offset are HOST
+ * arrays of `channels` entries; they travel in the kernel argument (no device table, no copy).  One launch, no workspace, no atomics;
+ * nothing outside the payload's num_records * R int16 is read (a lane reads the two bytes of its own sample only, at any parity of R,
+ * chan_off and the payload address) and nothing outside the `channels` rows of num_records * n elements is written.
+ * Refused, naming the argument: null pointers, an odd payload address, channels outside 1..EEG_EDF_MAX_CHANNELS, num_records < 1,
+ * n outside 1..2^30, payload_bytes < 2 * num_records * R, chan_off[c] + n > R (or a negative chan_off), out_stride < num_records * n,
+ * out not aligned to its element. */
+#define EEG_EDF_MAX_CHANNELS 32
+int eeg_dcrnn_edf_decode(const void* payload, size_t payload_bytes, int64_t num_records, int64_t R, int64_t n, int channels, const int64_t* chan_off,
+                         const double* gain, const double* offset, int out_f64, void* out, int64_t out_stride, void* stream);
+
 /* Occlusion maps on the device: group g of channels of clip b is overwritten with `fill` over the window of steps [t0, t0 + w) and the
  * map records how far the predicted probability drops.  All variants of a window start from the unoccluded clip's state at t0.
  *
