@@ -9,6 +9,7 @@ from .device_data import (BalancedEpochSampler, DeviceDataset, EpochSampler, Rec
                           clip_table_ssl, layout_recordings, clip_table_scan, clip_labels_detection, annotation_bins)
 from .evaluation import DeviceEvaluator, DeviceSSLEvaluator     # noqa: F401
 from .scan import Scanner, ScanResult, scores_from_scan_record     # noqa: F401
+from .bootstrap import BootstrapResult, bootstrap_scores, paired_difference     # noqa: F401
 from .interpret import OcclusionResult, occlusion_maps     # noqa: F401
 from .statistics import ScalerFit, fit_scaler     # noqa: F401
 from .resample import resample_recording, resample_recordings, resampled_length     # noqa: F401
@@ -22,6 +23,6 @@ __all__ = ["DCGRUCell", "DiffusionGraphConv", "DCRNNEncoder", "DCGRUDecoder",
            "DCRNNModel_classification", "DCRNNModel_nextTimePred", "DeviceDataset", "EpochSampler", "BalancedEpochSampler", "RecordingDataset", "clip_table_detection",
            "clip_table_ssl", "clip_table_classification", "layout_recordings", "DeviceEvaluator", "DeviceSSLEvaluator", "OcclusionResult",
            "occlusion_maps", "ScalerFit", "fit_scaler", "clip_table_scan", "clip_labels_detection", "annotation_bins", "Scanner", "ScanResult",
-           "scores_from_scan_record", "resample_recording", "resample_recordings", "resampled_length", "EdfHeader", "read_edf_header",
+           "scores_from_scan_record", "BootstrapResult", "bootstrap_scores", "paired_difference", "resample_recording", "resample_recordings", "resampled_length", "EdfHeader", "read_edf_header",
            "select_channels", "read_seizure_times", "read_markers_detection", "read_markers_ssl", "read_markers_classification", "recording_ids",
            "decode_edf", "load_edf_recordings", "ops", "utils"]

@@ -123,6 +123,12 @@ _SIGNATURES = {
     "eeg_dcrnn_eval_scores": (c_int, [_FP, _FP, c_int, _FP, _FP, c_int, c_int, c_int, c_int, c_int64, _FP, _FP, c_void_p]),
     "eeg_dcrnn_eval_metrics_ws_bytes": (c_size_t, [c_int64, c_int]),
     "eeg_dcrnn_eval_metrics": (c_int, [_FP, _FP, c_int, _FP, c_int64, c_int, c_int, ctypes.c_double, _FP, _FP, c_void_p]),
+    # the clustered bootstrap of the scores: counts (Philox draws), then one int64 record per replicate
+    "eeg_dcrnn_boot_counts": (c_int, [ctypes.c_uint64, c_int64, c_int64, _FP, c_void_p]),
+    "eeg_dcrnn_boot_ws_bytes": (c_size_t, [c_int64]),
+    "eeg_dcrnn_boot_detection": (c_int, [_FP, _FP, _FP, _FP, c_int64, c_int64, c_int64, _FP, c_int64, ctypes.c_double, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_boot_classification": (c_int, [_FP, _FP, _FP, c_int64, c_int, c_int64, c_int64, _FP, c_int64, _FP, _FP, c_void_p]),
+    "eeg_dcrnn_boot_records": (c_int, [_FP, c_int64, c_int, _FP, c_int64, _FP, c_void_p]),
     # the SSL evaluation pass: per-clip masked-MAE sums behind the decoder, then the pass's float64 record
     "eeg_dcrnn_ssl_eval_scores": (c_int, [_FP, _FP, _FP, _FP, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_float, c_float, _FP, _FP,
                                           c_void_p]),

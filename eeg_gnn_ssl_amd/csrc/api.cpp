@@ -16,6 +16,7 @@
 #include "diffuse_launch.h"
 #include "kernels_diffuse.h"
 #include "kernels_eval.h"
+#include "kernels_boot.h"
 #include "kernels_moments.h"
 #include "kernels_scan.h"
 #include "kernels_resample.h"
@@ -1342,6 +1343,129 @@ int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_byt
     EEG_LAUNCH_P("eval_metrics", eval_scan_kernel, dim3(1), dim3(kEvalScanThreads), 4 * kEvalScanThreads * sizeof(long long), st, keys, probs, lab,
                  losses, (int)P, search ? 1 : 0, thresh, neg_before, rec);
     return check_launch("eval_scan");
+}
+
+/* ---- the clustered bootstrap of the scores: counts, one record per replicate ---------------------- */
+static_assert(EEG_BOOT_MAX_GROUPS == kBootMaxGroups && EEG_BOOT_MAX_REPLICATES == kBootMaxReplicates && EEG_BOOT_DET_WORDS == kBootDetWords &&
+              EEG_BOOT_MAX_CLASSES == kBootMaxClasses && EEG_BOOT_MAX_RECORD_WORDS == kBootMaxRecordWords && EEG_BOOT_LDS_GROUPS == kBootLdsGroups,
+              "include/eeg_dcrnn.h and kernels_boot.h disagree");
+static int boot_chunk(int64_t P) { return (int)((P + kBootThreads - 1) / kBootThreads); }
+// the arguments every bootstrap entry shares; max_cluster < 0: the entry has no clips (boot_counts, boot_records)
+static int boot_shape(const char* what, int64_t G, int64_t n_boot, int64_t max_cluster) {
+    if (G < 1 || G > EEG_BOOT_MAX_GROUPS) return fail("%s: G=%lld clusters unsupported (1..%d)", what, (long long)G, EEG_BOOT_MAX_GROUPS);
+    if (n_boot < 1 || n_boot > EEG_BOOT_MAX_REPLICATES) return fail("%s: n_boot=%lld replicates unsupported (1..%d)", what, (long long)n_boot, EEG_BOOT_MAX_REPLICATES);
+    if (max_cluster >= 0 && (max_cluster < 1 || G * max_cluster >= (1ll << 31)))
+        return fail("%s: max_cluster=%lld clips in the largest of G=%lld clusters (>= 1, G * max_cluster < 2^31: a replicate's weight fits 31 bits)", what,
+                    (long long)max_cluster, (long long)G);
+    return 0;
+}
+int eeg_dcrnn_boot_counts(uint64_t seed, int64_t G, int64_t n_boot, int32_t* counts, void* stream) {
+    if (counts == nullptr) return fail("boot_counts: null counts");
+    if (boot_shape("boot_counts", G, n_boot, -1)) return 1;
+    if (((uintptr_t)counts & 3) != 0) return fail("boot_counts: pointers must be aligned to their element size");
+    const int bins = G < kBootCountBins ? (int)G : kBootCountBins;
+    const size_t lds = (size_t)((bins + 1) / 2) * sizeof(unsigned long long);
+    EEG_SET_MAX_LDS(boot_counts_kernel, lds);
+    EEG_LAUNCH_P("boot_counts", boot_counts_kernel, dim3((unsigned)n_boot + 1, (unsigned)ceil_div((int)G, bins)), dim3(kBootCountThreads), lds, S_(stream),
+                 (unsigned long long)seed, (int)G, bins, counts);
+    return check_launch("boot_counts");
+}
+size_t eeg_dcrnn_boot_ws_bytes(int64_t P) {
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return 0;
+    return sizeof(unsigned long long) * (size_t)eval_npad(P) + sizeof(unsigned) * ((size_t)boot_chunk(P) * kBootThreads + 2);
+}
+// keys (npad 64-bit words, filled) -> sorted ascending: the network of eeg_dcrnn_eval_metrics
+static int boot_sort(unsigned long long* keys, int npad, hipStream_t st) {
+    const int tile = kEvalSortTile, ntile = npad > tile ? npad / tile : 1;
+    const size_t tile_lds = (size_t)tile * sizeof(unsigned long long);
+    EEG_LAUNCH_P("boot_sort_tile", boot_sort_tile_kernel, dim3(ntile), dim3(kEvalSortThreads), tile_lds, st, keys, npad, 2, npad < tile ? npad : tile);
+    if (check_launch("boot_sort_tile")) return 1;
+    const int step_grid = ceil_div(npad / 2, kEvalSortThreads * kEvalStepPairs);
+    for (int k = 2 * tile; k <= npad && k > 0; k <<= 1) {
+        for (int j = k >> 1; j >= tile; j >>= 1) {
+            EEG_LAUNCH_P("boot_sort_step", boot_sort_step_kernel, dim3(step_grid), dim3(kEvalSortThreads), 0, st, keys, npad, j, k);
+            if (check_launch("boot_sort_step")) return 1;
+        }
+        EEG_LAUNCH_P("boot_sort_tile", boot_sort_tile_kernel, dim3(ntile), dim3(kEvalSortThreads), tile_lds, st, keys, npad, k, k);
+        if (check_launch("boot_sort_tile")) return 1;
+    }
+    return 0;
+}
+int eeg_dcrnn_boot_detection(const float* probs, const float* labels, const int32_t* groups, const float* losses, int64_t P, int64_t G,
+                             int64_t max_cluster, const int32_t* counts, int64_t n_boot, double thresh, void* ws, int64_t* records, void* stream) {
+    if (probs == nullptr || labels == nullptr || counts == nullptr || records == nullptr) return fail("boot_detection: null probs / labels / counts / records");
+    if (ws == nullptr) return fail("boot_detection: null workspace (eeg_dcrnn_boot_ws_bytes)");
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("boot_detection: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (boot_shape("boot_detection", G, n_boot, max_cluster)) return 1;
+    if (groups == nullptr && G != P) return fail("boot_detection: groups is null (every clip its own cluster) and G=%lld is not P=%lld", (long long)G, (long long)P);
+    if (!(thresh == thresh)) return fail("boot_detection: thresh is NaN");
+    if ((((uintptr_t)probs | (uintptr_t)labels | (uintptr_t)groups | (uintptr_t)losses | (uintptr_t)counts) & 3) != 0 ||
+        (((uintptr_t)ws | (uintptr_t)records) & 7) != 0)
+        return fail("boot_detection: pointers must be aligned to their element size");
+    hipStream_t st = S_(stream);
+    const int npad = eval_npad(P), chunk = boot_chunk(P);
+    unsigned long long* keys = static_cast<unsigned long long*>(ws);
+    unsigned* packed = reinterpret_cast<unsigned*>(keys + npad);
+    int* split = reinterpret_cast<int*>(packed + (size_t)chunk * kBootThreads);
+    EEG_LAUNCH_P("boot_keys", boot_keys_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, probs, labels, (int)P, npad, keys);
+    if (check_launch("boot_keys")) return 1;
+    if (boot_sort(keys, npad, st)) return 1;
+    EEG_LAUNCH_P("boot_pack", boot_pack_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, keys, groups, (int)P, (int)G, chunk, thresh, packed, split);
+    if (check_launch("boot_pack")) return 1;
+    long long* rec = reinterpret_cast<long long*>(records);
+    if (G <= kBootLdsGroups) {
+        const size_t lds = kBootScratchBytes + (size_t)G * sizeof(int);
+        EEG_SET_MAX_LDS(boot_detection_kernel<true>, lds);
+        EEG_LAUNCH_P("boot_detection", boot_detection_kernel<true>, dim3((unsigned)n_boot + 1), dim3(kBootThreads), lds, st, packed, split, counts, groups,
+                     losses, (int)P, (int)G, chunk, rec);
+    } else {
+        EEG_LAUNCH_P("boot_detection", boot_detection_kernel<false>, dim3((unsigned)n_boot + 1), dim3(kBootThreads), (size_t)kBootScratchBytes, st, packed,
+                     split, counts, groups, losses, (int)P, (int)G, chunk, rec);
+    }
+    return check_launch("boot_detection");
+}
+int eeg_dcrnn_boot_classification(const float* probs, const int64_t* labels, const int32_t* groups, int64_t P, int C, int64_t G, int64_t max_cluster,
+                                  const int32_t* counts, int64_t n_boot, void* ws, int64_t* records, void* stream) {
+    if (probs == nullptr || labels == nullptr || counts == nullptr || records == nullptr) return fail("boot_classification: null probs / labels / counts / records");
+    if (ws == nullptr) return fail("boot_classification: null workspace (eeg_dcrnn_boot_ws_bytes)");
+    if (C < 2 || C > EEG_BOOT_MAX_CLASSES) return fail("boot_classification: C=%d classes unsupported (2..%d)", C, EEG_BOOT_MAX_CLASSES);
+    if (P < 1 || P > EEG_EVAL_MAX_CLIPS) return fail("boot_classification: P=%lld clips unsupported (1..%d)", (long long)P, EEG_EVAL_MAX_CLIPS);
+    if (boot_shape("boot_classification", G, n_boot, max_cluster)) return 1;
+    if (groups == nullptr && G != P) return fail("boot_classification: groups is null (every clip its own cluster) and G=%lld is not P=%lld", (long long)G, (long long)P);
+    if ((((uintptr_t)probs | (uintptr_t)groups | (uintptr_t)counts) & 3) != 0 || (((uintptr_t)labels | (uintptr_t)ws | (uintptr_t)records) & 7) != 0)
+        return fail("boot_classification: pointers must be aligned to their element size");
+    hipStream_t st = S_(stream);
+    const int npad = eval_npad(P), chunk = boot_chunk(P), cells = C * C;
+    unsigned long long* keys = static_cast<unsigned long long*>(ws);
+    unsigned* packed = reinterpret_cast<unsigned*>(keys + npad);
+    EEG_LAUNCH_P("boot_cell_keys", boot_cell_keys_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, probs, reinterpret_cast<const long long*>(labels), (int)P,
+                 C, npad, keys);
+    if (check_launch("boot_cell_keys")) return 1;
+    if (boot_sort(keys, npad, st)) return 1;
+    EEG_LAUNCH_P("boot_pack_cells", boot_pack_cells_kernel, dim3(ceil_div((int)P, 256)), dim3(256), 0, st, keys, groups, (int)P, (int)G, chunk, packed);
+    if (check_launch("boot_pack_cells")) return 1;
+    long long* rec = reinterpret_cast<long long*>(records);
+    const size_t head = (size_t)kBootMaxClasses * kBootMaxClasses * sizeof(unsigned long long);
+    if (G <= kBootLdsGroups) {
+        const size_t lds = head + (size_t)G * sizeof(int);
+        EEG_SET_MAX_LDS(boot_cells_kernel<true>, lds);
+        EEG_LAUNCH_P("boot_classification", boot_cells_kernel<true>, dim3((unsigned)n_boot + 1), dim3(kBootThreads), lds, st, packed, counts, (int)P, (int)G,
+                     cells, chunk, rec);
+    } else {
+        EEG_LAUNCH_P("boot_classification", boot_cells_kernel<false>, dim3((unsigned)n_boot + 1), dim3(kBootThreads), head, st, packed, counts, (int)P, (int)G,
+                     cells, chunk, rec);
+    }
+    return check_launch("boot_classification");
+}
+int eeg_dcrnn_boot_records(const int64_t* rec_records, int64_t G, int K, const int32_t* counts, int64_t n_boot, int64_t* records, void* stream) {
+    if (rec_records == nullptr || counts == nullptr || records == nullptr) return fail("boot_records: null rec_records / counts / records");
+    if (K < 1 || K > EEG_BOOT_MAX_RECORD_WORDS) return fail("boot_records: K=%d words per record unsupported (1..%d)", K, EEG_BOOT_MAX_RECORD_WORDS);
+    if (boot_shape("boot_records", G, n_boot, -1)) return 1;
+    if (((uintptr_t)counts & 3) != 0 || (((uintptr_t)rec_records | (uintptr_t)records) & 7) != 0)
+        return fail("boot_records: pointers must be aligned to their element size");
+    EEG_LAUNCH_P("boot_records", boot_records_kernel, dim3((unsigned)n_boot + 1), dim3(kBootRecordThreads), kBootRecordThreads * sizeof(unsigned long long),
+                 S_(stream), reinterpret_cast<const long long*>(rec_records), counts, (int)G, K, reinterpret_cast<long long*>(records));
+    return check_launch("boot_records");
 }
 
 /* ---- the SSL evaluation pass: per-clip masked MAE, the pass's record ------------------------------ */

@@ -277,6 +277,11 @@ class RecordingDataset:
     def __len__(self):
         return self.clip_table.shape[0]
 
+    def clip_groups(self):
+        """the recording of every clip (column 0 of the clip table) as (P,) int32 on the device: the by-recording clustering of
+        `bootstrap_scores` / `DeviceEvaluator.bootstrap`"""
+        return self.clip_table[:, 0].to(torch.int32).contiguous()
+
     @property
     def device(self):
         return self.signals.device

@@ -193,6 +193,22 @@ class DeviceEvaluator(_CapturedPass):
             model.train(was_training)
         return scores_from_record(self.record, st.task, best_thresh)
 
+    @torch.no_grad()
+    def bootstrap(self, groups=None, n_boot: int = 2000, seed: int = 0):
+        """Clustered-bootstrap replicates of the last pass's scores -> `BootstrapResult` (bootstrap.py).  groups: (P,) integer cluster
+        ids (`RecordingDataset.clip_groups()`: by recording) or None: every clip its own cluster.  Uses the pass's `probs`, `losses`,
+        the labels of the dataset and the threshold of the pass's record, and only reads them: `probs`, `losses`, `record` and the
+        captured graph stay as they are.  With several ranks every rank holds the all-reduced buffers and computes the same result,
+        with no communication."""
+        from .bootstrap import bootstrap_scores
+        if self.record is None:
+            raise ValueError("DeviceEvaluator.bootstrap: no pass has run yet (run() first)")
+        thresh = 0.5
+        if self.step.task == "detection":
+            thresh = float(self.record[_THRESH:_THRESH + 1].numpy().view(np.float64)[0])
+        return bootstrap_scores(self.probs, self.dataset.y, self.step.task, groups=groups, n_boot=n_boot, seed=seed, best_thresh=thresh,
+                                losses=self.losses)
+
 
 class DeviceSSLEvaluator(_CapturedPass):
     """`TrainStep.ssl_evaluator(dataset, batch_size, supports=None)`: the SSL evaluation pass (train_ssl.py:232-280) of the step's

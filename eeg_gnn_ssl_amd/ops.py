@@ -13,7 +13,8 @@ Operators (namespace `eeg_dcrnn`):
     dcgru_decoder (+ dcgru_decoder_bwd), cls_head (+ cls_head_bwd), rng_take_, dropout_mask, gather_last, corr_graph,
     fft_features (+ fft_features_len), fft_features_pair, augment_features, window_features (+ window_features_len), corr_graph_len, corr_graph_rows_len, window_features_pair, augment_windows, corr_graph_rows, bce_logits, ce_logits, masked_loss, cls_head_loss, pack_cells, clip_adam_,
     clip_adam_dev_, teacher_flags_, augment_draw_, epoch_keys, gather_clips, gather_records, eval_scores, eval_metrics, ssl_eval_scores, ssl_eval_metrics,
-    feature_moments, moments_record, scan_timeline, scan_events, event_scores, resample, edf_decode, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights.
+    feature_moments, moments_record, scan_timeline, scan_events, event_scores, resample, edf_decode, occlude_expand, occlusion_scores, bce_logits_cw, ce_logits_cw, cls_head_loss_cw, clip_weights,
+    boot_counts, boot_detection, boot_classification, boot_records.
 The functions below them are the Python conveniences the modules in model/ and train_step.py call.
 """
 from __future__ import annotations
@@ -3189,3 +3190,196 @@ def occlusion_scores(var_logits, base_logits, lengths, target, k: int, t0: int, 
     lowest index on ties.  The probabilities are evaluated in double from the float32 logits.  k == 0 also writes base_prob (B,) and
     (if given) the classes followed to target_out (B,) int64.  One launch, no allocation, no host synchronisation."""
     torch.ops.eeg_dcrnn.occlusion_scores(var_logits, base_logits, lengths, target, int(k), int(t0), maps, base_prob, target_out)
+
+
+# ---- the clustered bootstrap of the scores on the device (bootstrap.py; csrc/kernels_boot.h) ---------------------------------------
+BOOT_MAX_GROUPS = 1 << 20             # EEG_BOOT_MAX_GROUPS: clusters of one call
+BOOT_MAX_REPLICATES = 65535           # EEG_BOOT_MAX_REPLICATES
+BOOT_DET_WORDS = 10                   # EEG_BOOT_DET_WORDS: int64 words of a replicate's detection record
+BOOT_MAX_CLASSES = 32                 # EEG_BOOT_MAX_CLASSES
+BOOT_MAX_RECORD_WORDS = 64            # EEG_BOOT_MAX_RECORD_WORDS: K of boot_records
+BOOT_LDS_GROUPS = 32768               # EEG_BOOT_LDS_GROUPS: the widest counts row a replicate's workgroup keeps in LDS
+BOOT_RECORD = ("weight", "pos", "neg", "auroc_num", "tp", "fp", "fn", "tn", "ap_bits", "loss_bits")     # the words of a detection record
+
+
+def _boot_counts_arg(what, lib, counts, g=None):
+    """(n_boot, G, device) of a counts tensor (n_boot + 1, G) int32"""
+    if not torch.is_tensor(counts) or counts.dim() != 2 or counts.dtype != torch.int32 or not counts.is_contiguous():
+        got = f"{counts.dtype} {tuple(counts.shape)}" if torch.is_tensor(counts) else type(counts).__name__
+        raise ValueError(f"{what}: counts must be a contiguous torch.int32 tensor of shape (n_boot + 1, G), got {got}")
+    if lib.is_device_build and not counts.is_cuda:
+        raise ValueError(f"{what}: the tensors are on {counts.device}; eeg_gnn_ssl_amd runs only on an MI355X (HIP) device and has no CPU path")
+    n_boot, width = int(counts.shape[0]) - 1, int(counts.shape[1])
+    if g is not None and width != g:
+        raise ValueError(f"{what}: counts rows are {width} wide, the clips name G={g} clusters")
+    if not 1 <= width <= BOOT_MAX_GROUPS:
+        raise ValueError(f"{what}: G={width} clusters outside 1..{BOOT_MAX_GROUPS} (EEG_BOOT_MAX_GROUPS)")
+    if not 1 <= n_boot <= BOOT_MAX_REPLICATES:
+        raise ValueError(f"{what}: n_boot={n_boot} replicates outside 1..{BOOT_MAX_REPLICATES} (EEG_BOOT_MAX_REPLICATES)")
+    return n_boot, width, counts.device
+
+
+def _boot_counts_impl(seed: int, counts) -> None:
+    lib = _lib.get_lib()
+    n_boot, g, _ = _boot_counts_arg("boot_counts", lib, counts)
+    if not 0 <= int(seed) < 1 << 63:
+        raise ValueError(f"boot_counts: seed={seed} outside 0..2^63-1")
+    lib.call("eeg_dcrnn_boot_counts", int(seed), g, n_boot, _p(counts), _stream(counts))
+
+
+def _boot_pool(what, probs, groups, counts, max_cluster):
+    """the checks the two clip-level operators share -> (lib, P, C, G, n_boot, device)"""
+    lib = _lib.get_lib()
+    if not torch.is_tensor(probs) or probs.dim() not in (1, 2) or probs.shape[0] < 1 or (probs.dim() == 2 and probs.shape[1] < 2):
+        got = f"{tuple(probs.shape)}" if torch.is_tensor(probs) else type(probs).__name__
+        raise ValueError(f"{what}: probs must be (P,) (detection) or (P, C) with C >= 2 (classification), got {got}")
+    p, c = int(probs.shape[0]), (1 if probs.dim() == 1 else int(probs.shape[1]))
+    if p > EVAL_MAX_CLIPS:
+        raise ValueError(f"{what}: P={p} clips exceed the limit of one call, {EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    n_boot, g, dev = _boot_counts_arg(what, lib, counts, None if groups is not None else p)
+    _scan_tensor(what, "probs", probs, torch.float32, (p,) if c == 1 else (p, c), dev)
+    if groups is not None:
+        _scan_tensor(what, "groups", groups, torch.int32, (p,), dev)
+    if int(max_cluster) < 1 or g * int(max_cluster) >= 1 << 31:
+        raise ValueError(f"{what}: G={g} clusters, the largest of {int(max_cluster)} clips: G * largest must stay below 2^31 (a replicate's weight "
+                         f"fits 31 bits); use fewer, smaller clusters")
+    return lib, p, c, g, n_boot, dev
+
+
+def _boot_ws(what, lib, ws, p, dev):
+    need = (int(lib.query("eeg_dcrnn_boot_ws_bytes", p)) + 7) // 8
+    if not torch.is_tensor(ws) or ws.dtype != torch.int64 or ws.dim() != 1 or ws.numel() < need or ws.device != dev or not ws.is_contiguous():
+        raise ValueError(f"{what}: ws must be a contiguous int64 vector of at least {need} entries on {dev} (ops.boot_workspace)")
+
+
+def _boot_detection_impl(probs, labels, groups, losses, counts, thresh: float, max_cluster: int, ws, records) -> None:
+    what = "boot_detection"
+    lib, p, c, g, n_boot, dev = _boot_pool(what, probs, groups, counts, max_cluster)
+    if c != 1:
+        raise ValueError(f"{what}: probs must be (P,), got {tuple(probs.shape)} (classification: ops.boot_classification)")
+    _scan_tensor(what, "labels", labels, torch.float32, (p,), dev)
+    if losses is not None:
+        _scan_tensor(what, "losses", losses, torch.float32, (p,), dev)
+    if thresh != thresh:
+        raise ValueError(f"{what}: thresh is NaN")
+    _boot_ws(what, lib, ws, p, dev)
+    _scan_tensor(what, "records", records, torch.int64, (n_boot + 1, BOOT_DET_WORDS), dev)
+    lib.call("eeg_dcrnn_boot_detection", _p(probs), _p(labels), _p(groups), _p(losses), p, g, int(max_cluster), _p(counts), n_boot, float(thresh),
+             _p(ws), _p(records), _stream(probs))
+
+
+def _boot_classification_impl(probs, labels, groups, counts, max_cluster: int, ws, records) -> None:
+    what = "boot_classification"
+    lib, p, c, g, n_boot, dev = _boot_pool(what, probs, groups, counts, max_cluster)
+    if not 2 <= c <= BOOT_MAX_CLASSES:
+        raise ValueError(f"{what}: probs must be (P, C) with 2 <= C <= {BOOT_MAX_CLASSES} (EEG_BOOT_MAX_CLASSES), got {tuple(probs.shape)}")
+    _scan_tensor(what, "labels", labels, torch.int64, (p,), dev)
+    _boot_ws(what, lib, ws, p, dev)
+    _scan_tensor(what, "records", records, torch.int64, (n_boot + 1, c * c), dev)
+    lib.call("eeg_dcrnn_boot_classification", _p(probs), _p(labels), _p(groups), p, c, g, int(max_cluster), _p(counts), n_boot, _p(ws), _p(records),
+             _stream(probs))
+
+
+def _boot_records_impl(rec_records, counts, records) -> None:
+    what = "boot_records"
+    lib = _lib.get_lib()
+    n_boot, g, dev = _boot_counts_arg(what, lib, counts)
+    if not torch.is_tensor(rec_records) or rec_records.dim() != 2 or not 1 <= rec_records.shape[1] <= BOOT_MAX_RECORD_WORDS:
+        got = f"{tuple(rec_records.shape)}" if torch.is_tensor(rec_records) else type(rec_records).__name__
+        raise ValueError(f"{what}: rec_records must be (G, K) int64 with 1 <= K <= {BOOT_MAX_RECORD_WORDS} (EEG_BOOT_MAX_RECORD_WORDS), got {got}")
+    k = int(rec_records.shape[1])
+    if int(rec_records.shape[0]) != g:
+        raise ValueError(f"{what}: counts rows are {g} wide, rec_records holds {int(rec_records.shape[0])} clusters")
+    _scan_tensor(what, "rec_records", rec_records, torch.int64, (g, k), dev)
+    _scan_tensor(what, "records", records, torch.int64, (n_boot + 1, k), dev)
+    lib.call("eeg_dcrnn_boot_records", _p(rec_records), g, k, _p(counts), n_boot, _p(records), _stream(counts))
+
+
+_define("boot_counts", "(int seed, Tensor(a!) counts) -> ()", _boot_counts_impl, lambda *a: None)
+_define("boot_detection", "(Tensor probs, Tensor labels, Tensor? groups, Tensor? losses, Tensor counts, float thresh, int max_cluster, Tensor(a!) ws, "
+        "Tensor(b!) records) -> ()", _boot_detection_impl, lambda *a: None)
+_define("boot_classification", "(Tensor probs, Tensor labels, Tensor? groups, Tensor counts, int max_cluster, Tensor(a!) ws, Tensor(b!) records) -> ()",
+        _boot_classification_impl, lambda *a: None)
+_define("boot_records", "(Tensor rec_records, Tensor counts, Tensor(a!) records) -> ()", _boot_records_impl, lambda *a: None)
+
+
+def boot_counts(num_groups: int, n_boot: int, seed: int, device):
+    """The resampling counts of a clustered bootstrap: (n_boot + 1, G) int32 on `device`.  Row 0 is ones (the point estimate); row r >= 1
+    is a multinomial draw of G cluster indices with replacement -- draw j is word j % 4 of Philox4x32-10 at the counter (lo(j / 4),
+    hi(j / 4), r, 4) under key `seed` and names cluster (word * G) >> 32 (bias at most G / 2^32 per cluster).  A function of (G, n_boot,
+    seed) alone: every rank and every run draws the same counts.  One launch, no host synchronisation."""
+    g, n = int(num_groups), int(n_boot)
+    if not 1 <= g <= BOOT_MAX_GROUPS:
+        raise ValueError(f"boot_counts: G={g} clusters outside 1..{BOOT_MAX_GROUPS} (EEG_BOOT_MAX_GROUPS)")
+    if not 1 <= n <= BOOT_MAX_REPLICATES:
+        raise ValueError(f"boot_counts: n_boot={n} replicates outside 1..{BOOT_MAX_REPLICATES} (EEG_BOOT_MAX_REPLICATES)")
+    if not 0 <= int(seed) < 1 << 63:
+        raise ValueError(f"boot_counts: seed={seed} outside 0..2^63-1")
+    counts = torch.empty((n + 1, g), dtype=torch.int32, device=device)
+    torch.ops.eeg_dcrnn.boot_counts(int(seed), counts)
+    return counts
+
+
+def boot_workspace(num_clips: int, device):
+    """the scratch of `boot_detection` / `boot_classification` for a pool of `num_clips` clips (eeg_dcrnn_boot_ws_bytes)"""
+    if not 1 <= int(num_clips) <= EVAL_MAX_CLIPS:
+        raise ValueError(f"boot_workspace: P={num_clips} clips outside 1..{EVAL_MAX_CLIPS} (EEG_EVAL_MAX_CLIPS)")
+    return torch.empty((int(_lib.get_lib().query("eeg_dcrnn_boot_ws_bytes", int(num_clips))) + 7) // 8, dtype=torch.int64, device=device)
+
+
+def boot_check_groups(what, groups, num_clips: int, num_groups: int):
+    """Host check of a clustering (one small copy): groups (P,) int32 with 0 <= groups[i] < G.  -> the clips of the largest cluster
+    (groups None: every clip its own cluster, 1)."""
+    if groups is None:
+        if int(num_groups) != int(num_clips):
+            raise ValueError(f"{what}: groups is None (every clip its own cluster): counts rows must be P={num_clips} wide, got {num_groups}")
+        return 1
+    if not torch.is_tensor(groups) or groups.dtype != torch.int32 or tuple(groups.shape) != (int(num_clips),):
+        got = f"{groups.dtype} {tuple(groups.shape)}" if torch.is_tensor(groups) else type(groups).__name__
+        raise ValueError(f"{what}: groups must be a torch.int32 tensor of shape ({int(num_clips)},), got {got}")
+    lo, hi = int(groups.min()), int(groups.max())
+    if lo < 0 or hi >= int(num_groups):
+        raise ValueError(f"{what}: groups holds cluster ids {lo}..{hi}, outside 0..G-1 = {int(num_groups) - 1}")
+    return int(torch.bincount(groups.long(), minlength=1).max())
+
+
+def boot_detection(probs, labels, groups, counts, thresh: float = 0.5, losses=None, *, ws=None, max_cluster: Optional[int] = None):
+    """One int64 record per replicate of a clustered bootstrap of the detection scores: (n_boot + 1, BOOT_DET_WORDS), the words of
+    BOOT_RECORD.  probs / labels (P,) float32, groups (P,) int32 cluster ids or None (every clip its own cluster), counts (n_boot + 1,
+    G) int32 (`boot_counts`, or explicit), losses (P,) float32 or None.  Clip i weighs counts[r, groups[i]] in replicate r; the words
+    are the weighted forms of `eval_metrics`' N, n_pos, n_neg, AUROC numerator and tp / fp / fn / tn at (double)prob > thresh, the bits
+    of the float64 average precision and of sum_i w_i * loss_i.  Integer words reproduce bit for bit.  max_cluster: the clips of the
+    largest cluster when the caller has validated `groups` already (else checked here on the host: one small copy)."""
+    g = int(counts.shape[1]) if torch.is_tensor(counts) and counts.dim() == 2 else 0
+    if max_cluster is None:
+        max_cluster = boot_check_groups("boot_detection", groups, probs.shape[0] if torch.is_tensor(probs) else 0, g)
+    if ws is None and torch.is_tensor(probs) and 1 <= probs.shape[0] <= EVAL_MAX_CLIPS:
+        ws = boot_workspace(probs.shape[0], probs.device)
+    records = torch.empty((int(counts.shape[0]) if g else 1, BOOT_DET_WORDS), dtype=torch.int64, device=counts.device if g else None)
+    torch.ops.eeg_dcrnn.boot_detection(probs, labels, groups, losses, counts, float(thresh), int(max_cluster), ws, records)
+    return records
+
+
+def boot_classification(probs, labels, groups, counts, *, ws=None, max_cluster: Optional[int] = None):
+    """The weighted confusion matrix of every replicate: (n_boot + 1, C * C) int64, row = label, column = the first arg-max of the row of
+    probs (P, C) float32 (`eval_metrics`' rule; a row it counts as bad is left out).  labels (P,) int64; groups / counts / max_cluster
+    as `boot_detection`.  2 <= C <= BOOT_MAX_CLASSES."""
+    g = int(counts.shape[1]) if torch.is_tensor(counts) and counts.dim() == 2 else 0
+    if max_cluster is None:
+        max_cluster = boot_check_groups("boot_classification", groups, probs.shape[0] if torch.is_tensor(probs) else 0, g)
+    if ws is None and torch.is_tensor(probs) and 1 <= probs.shape[0] <= EVAL_MAX_CLIPS:
+        ws = boot_workspace(probs.shape[0], probs.device)
+    c = int(probs.shape[1]) if torch.is_tensor(probs) and probs.dim() == 2 else 1
+    records = torch.empty((int(counts.shape[0]) if g else 1, c * c), dtype=torch.int64, device=counts.device if g else None)
+    torch.ops.eeg_dcrnn.boot_classification(probs, labels, groups, counts, int(max_cluster), ws, records)
+    return records
+
+
+def boot_records(rec_records, counts):
+    """records[r, k] = sum_g counts[r, g] * rec_records[g, k]: the replicates of per-cluster integer records (G, K) int64, e.g.
+    `ScanResult.rec_records` with one record per recording.  (n_boot + 1, K) int64, K <= BOOT_MAX_RECORD_WORDS."""
+    n = int(counts.shape[0]) if torch.is_tensor(counts) and counts.dim() == 2 else 1
+    k = int(rec_records.shape[1]) if torch.is_tensor(rec_records) and rec_records.dim() == 2 else 1
+    records = torch.empty((n, k), dtype=torch.int64, device=counts.device if torch.is_tensor(counts) else None)
+    torch.ops.eeg_dcrnn.boot_records(rec_records, counts, records)
+    return records

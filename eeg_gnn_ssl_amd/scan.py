@@ -75,6 +75,13 @@ class ScanResult:
         return OrderedDict([("clip_probs", self.clip_probs[c]), ("timeline", self.timeline[b]), ("cover", self.cover[b]),
                             ("smoothed", self.smoothed[b]), ("events", self.events[r, :counts[r]])])
 
+    def bootstrap(self, n_boot: int = 2000, seed: int = 0, groups=None):
+        """Bootstrap replicates of the scan's scores -> `BootstrapResult` (bootstrap.py): the R recordings are resampled with
+        replacement -- or patients, through groups (R,) integer ids 0..G-1 --, a replicate's record is the weighted sum of
+        `rec_records` (`ops.boot_records`) and its scores are `scores_from_scan_record` of that sum.  Needs annotations."""
+        from .bootstrap import bootstrap_scan
+        return bootstrap_scan(self, n_boot=n_boot, seed=seed, groups=groups)
+
     def events_seconds(self):
         """the detected events as a host list of (rec, onset_s, offset_s)"""
         _, _, counts = self._offsets()

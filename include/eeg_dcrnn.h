@@ -444,6 +444,47 @@ size_t eeg_dcrnn_eval_metrics_ws_bytes(int64_t P, int C);
 int eeg_dcrnn_eval_metrics(const float* probs, const void* labels, int label_bytes, const float* losses, int64_t P, int C, int search,
                            double thresh, void* ws, int64_t* record, void* stream);
 
+/* The clustered bootstrap of the evaluator's scores on the device.  A replicate r is a row of int32 counts over G clusters; clip i of
+ * cluster groups[i] (int32, 0..G-1; NULL: every clip its own cluster, G = P) weighs counts[r, groups[i]], and every score of the
+ * replicate is the weighted form of the score eeg_dcrnn_eval_metrics computes.  Row 0 of the drawn counts is all ones: record 0 is
+ * the point estimate.  1 <= G <= EEG_BOOT_MAX_GROUPS, 1 <= n_boot <= EEG_BOOT_MAX_REPLICATES, P <= EEG_EVAL_MAX_CLIPS; counts and
+ * records have n_boot + 1 rows.  max_cluster: the clips of the largest cluster as the caller counted them, G * max_cluster < 2^31
+ * (a row of drawn counts sums to G, so a replicate's weight fits 31 bits and 2 * W+ * W- fits int64).  A cluster id outside 0..G-1
+ * is the caller's to refuse; the kernels count it as cluster 0 and never read outside a counts row.  No allocation, no host
+ * synchronisation; integer arithmetic and float64 sums in a fixed order: a record reproduces bit for bit.
+ *
+ * eeg_dcrnn_boot_counts: counts (n_boot + 1, G).  Row r >= 1 is a multinomial draw of G cluster indices with replacement: draw j is
+ * word j % 4 of Philox4x32-10 at the counter words (lo(j / 4), hi(j / 4), r, 4) under key seed (the counter layout of
+ * eeg_dcrnn_epoch_keys with a stream word of its own) and names cluster (uint64(word) * G) >> 32; integer atomics in LDS.
+ *
+ * eeg_dcrnn_boot_detection: probs / labels float32 (P,), losses (P,) float32 or NULL.  ws: eeg_dcrnn_boot_ws_bytes(P) bytes, 8-byte
+ * aligned.  One sort per call (64-bit words: the key of eeg_dcrnn_eval_metrics above the clip index, the same bitonic network), one
+ * packed 32-bit word per sorted clip (cluster id, label, run start) and the sorted index of the threshold split, then one workgroup
+ * per replicate; its counts row sits in LDS for G <= EEG_BOOT_LDS_GROUPS and is read from memory above.  records (n_boot + 1,
+ * EEG_BOOT_DET_WORDS) int64: 0 total weight, 1 / 2 weighted positives / negatives, 3 the AUROC numerator sum_v posw(v) * (2 *
+ * negw_below(v) + negw(v)) over the runs v of equal probability, 4..7 tp, fp, fn, tn at (double)prob > thresh, 8 the bits of the
+ * float64 average precision sum_v posw(v) / W+ * tp(v) / (tp(v) + fp(v)) with tp(v), fp(v) the weights at prob >= v (NaN without a
+ * positive), 9 the bits of the float64 sum_i w_i * loss_i in pool order (0 without losses).
+ *
+ * eeg_dcrnn_boot_classification: probs (P, C) float32, labels int64, 2 <= C <= EEG_BOOT_MAX_CLASSES; records (n_boot + 1, C * C) int64
+ * weighted confusion matrices (row = label, column = the first arg-max; a row eeg_dcrnn_eval_metrics counts as bad is left out).
+ *
+ * eeg_dcrnn_boot_records: records[r, k] = sum_g counts[r, g] * rec_records[g, k] for rec_records (G, K) int64 (one integer record per
+ * cluster, e.g. the rec_records of eeg_dcrnn_event_scores), 1 <= K <= EEG_BOOT_MAX_RECORD_WORDS, int64 arithmetic modulo 2^64. */
+#define EEG_BOOT_MAX_GROUPS (1 << 20)
+#define EEG_BOOT_MAX_REPLICATES 65535
+#define EEG_BOOT_DET_WORDS 10
+#define EEG_BOOT_MAX_CLASSES 32
+#define EEG_BOOT_MAX_RECORD_WORDS 64
+#define EEG_BOOT_LDS_GROUPS 32768
+int eeg_dcrnn_boot_counts(uint64_t seed, int64_t G, int64_t n_boot, int32_t* counts, void* stream);
+size_t eeg_dcrnn_boot_ws_bytes(int64_t P);
+int eeg_dcrnn_boot_detection(const float* probs, const float* labels, const int32_t* groups, const float* losses, int64_t P, int64_t G,
+                             int64_t max_cluster, const int32_t* counts, int64_t n_boot, double thresh, void* ws, int64_t* records, void* stream);
+int eeg_dcrnn_boot_classification(const float* probs, const int64_t* labels, const int32_t* groups, int64_t P, int C, int64_t G, int64_t max_cluster,
+                                  const int32_t* counts, int64_t n_boot, void* ws, int64_t* records, void* stream);
+int eeg_dcrnn_boot_records(const int64_t* rec_records, int64_t G, int K, const int32_t* counts, int64_t n_boot, int64_t* records, void* stream);
+
 /* The SSL evaluation pass (train_ssl.py:232-280) on the device.
  *
  * eeg_dcrnn_ssl_eval_scores: one launch behind the decoder of every step of a pass over a pool of P clips in order, the twin of
